@@ -18,14 +18,20 @@ Steps are PIPELINED: every rank keeps --streams (default 16) device-resident cop
 unless the caller set it: the runtime's default of 4 serialises streams that share a hardware queue -- its own hardware queue, and step k runs
 on copy k mod streams without a host synchronisation between steps (the K timed steps are bracketed by barrier + synchronize as the
 contract says): solve times are heavy-tailed (median 27 factorisation passes, slowest of a batch 100-300), so a step that waits for its
-last instance leaves the GPU idle for half of its duration.  After the timed region the SAME process measures `--sync-steps` synchronous
+last instance leaves the GPU idle for half of its duration.  With --full, after the timed region the SAME process measures `--sync-steps` synchronous
 steps (one launch alone on the GPU, HIP events on the launch stream): that is the per-launch kernel time the roofline is computed from.
 
 `value` is measured with the REFERENCE's solver configuration (obca_reference_opts: IPOPT's second-order correction max_soc = 4, recalc_y = "yes" as ParkingSignedDist.jl:41
 sets it, least-squares initial multipliers; the quadcopter call: obca_quadcopter_reference_opts).  The library's throughput defaults (those switches off: a fifth fewer passes
 per solve) are the secondary leg `config.fast_options`; `--fast-options` times them instead.
 
-Extra objects in the JSON line:
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what `value` needs: it makes the batch, warms up, times the K steps, validates the result of the last
+step and prints the line.  `--dump-outputs DIR` writes that result, the arrays a caller of Batch.download / QuadBatch.download receives, as DIR/<name>.npy (float64;
+ragged per-instance arrays zero-padded; a fixed, seeded sample of the instances if they exceed 60 MiB, with their indices in DIR/instance.npy).  Everything else
+the line can carry -- the synchronous steps and the roofline, the CPU baselines, the other option set, the other configs, the batch lottery, the host-pointer rate, the
+bit-equality checks -- runs with `--full` only (each leg can still be skipped with its --no-* option).
+
+Extra objects in the JSON line with --full:
   roofline     : dominant kernel (obca_parking_ipm_kernel / obca_quad_ipm_kernel), one launch alone on the GPU, HIP events on its stream.  SURVEY 8d Model B (the condensed KKT
                  solve these kernels are): algorithmic work = executed fp64 flops per factorisation pass x passes reported by the kernel, against 78.6 TFLOP/s (fp64 vector =
                  matrix peak) -> `bound` "mfma", `achieved`, `frac`; algorithmic HBM bytes = the I/O of the solves only (`algorithmic_bytes_io_only`, ~21.6 KB per solve).
@@ -340,6 +346,36 @@ def validated_mask(cfg, rows, shared, out, N):
     return ok
 
 
+DUMP_BYTES = 60 << 20      # --dump-outputs: data bytes in all (the .npy files stay below 64 MB)
+
+
+def caller_arrays(out, widths=None):
+    """a download (Batch.download / QuadBatch.download) as float64 arrays with the instance as first axis; the per-instance lp / np / sl of a ragged batch zero-padded to
+    widths[name] rows"""
+    res = {}
+    for k, v in out.items():
+        if widths and k in widths:
+            p = np.zeros((len(v), widths[k], np.shape(v[0])[1]))
+            for i, x in enumerate(v):
+                p[i, :np.shape(x)[0]] = x
+            v = p
+        res[k] = np.asarray(v, dtype=np.float64)
+    return res
+
+
+def dump_outputs(d, res):
+    """DIR/<name>.npy for every array of `res`; beyond DUMP_BYTES in all, the same fixed, seeded sample of the instances of every array (their indices: DIR/instance.npy)"""
+    os.makedirs(d, exist_ok=True)
+    B = len(res["exitflag"])
+    per = sum(v.nbytes for v in res.values()) / B
+    if per * B > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(SEED).choice(B, int(DUMP_BYTES // (per + 8)), replace=False))
+        res = {k: v[keep] for k, v in res.items()}
+        res["instance"] = keep.astype(np.float64)
+    for k, v in res.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
 def device_batches(cfg, rows, shared, B, N, nS, local):
     """nS device-resident copies of one host batch, each with its own context / HIP stream"""
     import obca_amd
@@ -499,7 +535,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL; gloo lets several ranks share one GPU for a functional test)")
     ap.add_argument("--streams", type=int, default=16, help="device-resident copies of the batch, each on its own HIP stream (1 = synchronous steps)")
-    ap.add_argument("--sync-steps", type=int, default=6, help="synchronous steps measured after the timed region for the per-launch kernel time of the roofline")
+    ap.add_argument("--sync-steps", type=int, default=6, help="--full: synchronous steps measured after the timed region for the per-launch kernel time of the roofline")
     ap.add_argument("--warm-start", default="primitive", choices=["primitive", "hybrid"], help="config 2 only: line/arc/line primitives (default) or the reference's "
                     "pipeline main.jl:216-248 -- Hybrid A* path, velocity smoother, resampling (planned on the host cores before the timed region)")
     ap.add_argument("--seed-offset", type=int, default=0, help="diagnostic: shift the seed of the job's batch")
@@ -514,6 +550,9 @@ def main():
     ap.add_argument("--ipopt-options", action="store_true", help="(accepted for old job scripts: the reference's IPOPT configuration is the default now)")
     ap.add_argument("--no-ipopt-leg", "--no-options-leg", dest="no_ipopt_leg", action="store_true", help="skip config.fast_options (the same batch with the other option set)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip config.other_configs (compact rates of BASELINE configs 3, 4 and 5, each with its CPU leg)")
+    ap.add_argument("--full", action="store_true", help="every leg beside `value`: synchronous steps and roofline (with the rocprofv3 --pmc passes), CPU baselines, the other "
+                    "option set, configs 3-5, the batch lottery, the host-pointer rate, the bit-equality checks (without it: `value` alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the results of the last timed step as DIR/<name>.npy (float64, below 64 MB in all)")
     a = ap.parse_args()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and not a.single_process:
         # `python bench.py --gpus N` without a launcher: start one rank per GPU ourselves (the contract's launch line), so that an 8-GPU run cannot be lost to a missing torchrun
@@ -526,7 +565,12 @@ def main():
         raise SystemExit(subprocess.call(cmd, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))))
     if a.pmc_child:
         a.steps, a.warmup, a.streams, a.sync_steps, a.no_cpu_baseline, a.no_pmc, a.no_host_rate, a.no_distinct, a.no_ipopt_leg, a.no_other_configs = 1, 0, 1, 1, True, True, True, True, True, True
+        a.full = True
+    if not a.full:
+        a.no_cpu_baseline = a.no_pmc = a.no_host_rate = a.no_distinct = a.no_ipopt_leg = a.no_other_configs = True
     if a.single_process:
+        if a.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs writes the results of the device-resident steps; --single-process has none")
         return single_process(a)
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != a.gpus:
@@ -611,16 +655,18 @@ def main():
         bq.sync()
     fence()
     dt = time.perf_counter() - t0
+    out = batches[(a.steps - 1) % nS].download()      # the result of the last timed step
     # ---- per-launch kernel time: synchronous steps of copy 0, one launch alone on the GPU, HIP events on the launch stream (outside the timed region)
     ipm_ms, dws_ms, sync_s = [], [], []
-    for k in range(max(1, a.sync_steps)):
-        ts0 = time.perf_counter(); batches[0].solve(opts=run_opts, sync=True); sync_s.append(time.perf_counter() - ts0)
-        m = batches[0].kernel_ms()
-        if quad:
-            ipm_ms.append(m)
-        else:
-            ipm_ms.append(m[0]); dws_ms.append(m[1])
-    fence()
+    if a.full:
+        for k in range(max(1, a.sync_steps)):
+            ts0 = time.perf_counter(); batches[0].solve(opts=run_opts, sync=True); sync_s.append(time.perf_counter() - ts0)
+            m = batches[0].kernel_ms()
+            if quad:
+                ipm_ms.append(m)
+            else:
+                ipm_ms.append(m[0]); dws_ms.append(m[1])
+        fence()
     if a.pmc_child:
         return
     # ---- what a caller of the drop-in gets (outside the timed region, never `value`): the host-pointer entry point on 16 384 host-array instances, PCIe included
@@ -669,24 +715,25 @@ def main():
         solved = sum(dval[k % nS] for k in range(a.steps))
         distinct = dict(solves_per_s=round(solved / dtd, 1), batches=nS, instances=nS * B, validated=dval, longest_solve_passes=dmaxp,
                         note="every stream holds a different batch of the same distribution (other seeds): the timed steps cover their stragglers too; never `value`")
-    # ---- results: every copy solved the same inputs and must hold the same bits
-    outs = [bq.download() for bq in batches[:min(nS, a.steps + a.warmup)]]
-    out = outs[0]
     other_leg = None; others = None
     if rank == 0 and world == 1 and not a.no_ipopt_leg:
         other_leg = options_leg(cfg, rows, shared, B, N, nS, local, max(8, min(a.steps, 40)), out, not fast)
     if rank == 0 and world == 1 and cfg == 2 and not a.no_other_configs:
         others = [other_config_line(c_, local, other_prepared[c_], other_cpu.get(c_)) for c_ in (3, 4, 5)]
-    same = all(np.array_equal(o["info"], out["info"]) and np.array_equal(np.asarray(o["xp"]), np.asarray(out["xp"])) for o in outs[1:])
-    # ---- and the same bits after a kernel has left a large pattern in the registers, LDS and scratch of every CU (until the end of round 5 the parking
-    # kernels' termination test read LDS words nothing had written).  A report in `config`, never a condition of the line.
-    try:
-        from obca_amd import diag      # (a diagnostic library of its own, libobca_diag.so: nothing of it is in the product library)
-        diag.leave_pattern(batches[0].ctx, 15, 1e30)
-        batches[0].solve(opts=run_opts, sync=True); o_ = batches[0].download()
-        after_pattern = bool(np.array_equal(o_["info"], out["info"]) and np.array_equal(np.asarray(o_["xp"]), np.asarray(out["xp"])))
-    except Exception as e:      # noqa: BLE001 -- a diagnostic must not cost the line
-        after_pattern = "not run: %r" % (e,)
+    same = after_pattern = None
+    if a.full:
+        # ---- every copy solved the same inputs and must hold the same bits
+        outs = [bq.download() for bq in batches[:min(nS, a.steps + a.warmup)]]
+        same = all(np.array_equal(o["info"], out["info"]) and np.array_equal(np.asarray(o["xp"]), np.asarray(out["xp"])) for o in outs)
+        # ---- and the same bits after a kernel has left a large pattern in the registers, LDS and scratch of every CU (until the end of round 5 the parking
+        # kernels' termination test read LDS words nothing had written).  A report in `config`, never a condition of the line.
+        try:
+            from obca_amd import diag      # (a diagnostic library of its own, libobca_diag.so: nothing of it is in the product library)
+            diag.leave_pattern(batches[0].ctx, 15, 1e30)
+            batches[0].solve(opts=run_opts, sync=True); o_ = batches[0].download()
+            after_pattern = bool(np.array_equal(o_["info"], out["info"]) and np.array_equal(np.asarray(o_["xp"]), np.asarray(out["xp"])))
+        except Exception as e:      # noqa: BLE001 -- a diagnostic must not cost the line
+            after_pattern = "not run: %r" % (e,)
     # ---- gather the full result tuple of every instance on rank 0 (one gather), validate there: a solve counts only if exitflag == 1 AND the
     # returned trajectory passes the a-posteriori checker (obca_amd/validate.py, pure numpy, outside the timed region)
     T = lambda x: np.transpose(np.asarray(x), (0, 2, 1)).reshape(B, -1)
@@ -708,12 +755,19 @@ def main():
             allrows = {}; o = 0
             for k in keys:
                 w = rows[k].shape[1]; allrows[k] = g[:, o:o + w]; o += w
-    stats = torch.tensor([dt, float(np.mean(ipm_ms)), float(same)], dtype=torch.float64)
+    if a.dump_outputs:      # the result of the last timed step; every rank's slice gathered on rank 0 (one gather per array)
+        res = caller_arrays(out, None if quad else {"lp": M_max, "np": 4 * nOb_max, "sl": nOb_max})
+        for k, v in list(res.items()) if world > 1 else ():
+            g = sharding.gather_rows(v.reshape(B, -1), B_total, rank, world, 0)
+            res[k] = None if g is None else g.reshape((B_total,) + v.shape[1:])
+        if rank == 0:
+            dump_outputs(a.dump_outputs, res)
     if dist is not None:
-        g = stats.cuda() if a.backend == "nccl" else stats.clone()
+        g = torch.tensor([dt, float(same is not False)], dtype=torch.float64)
+        g = g.cuda() if a.backend == "nccl" else g
         tmax = g[0:1].clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        smin = g[2:3].clone(); dist.all_reduce(smin, op=dist.ReduceOp.MIN)
-        dt = float(tmax.item()); same = bool(smin.item() > 0.5)
+        smin = g[1:2].clone(); dist.all_reduce(smin, op=dist.ReduceOp.MIN)
+        dt = float(tmax.item()); same = bool(smin.item() > 0.5) if a.full else None
     if rank == 0:
         Bt = B_total; N1 = N + 1
         if quad:
@@ -738,55 +792,56 @@ def main():
             conv_flag = int((ef == 1).sum())
         conv_all = int(okv.sum())
         iters = info[:, 1]; passes_all = float((info[:, 1] + info[:, 6]).sum())
-        passes0 = float((out["info"][:, 1] + out["info"][:, 6]).sum())      # passes of ONE launch of rank 0's batch (the launch the HIP events timed)
-        k_ms = float(np.median(ipm_ms))
-        if quad:
-            f_pass = F_PASS_QUAD; kernel = "obca_quad_ipm_kernel"
-            b_pass = b_iter_quad(N) * float(out["info"][:, 1].sum()) / max(1.0, passes0)      # per pass = per iteration x iterations / passes of this launch
-        else:
-            if cfg == 5:
-                nb_mean = float(np.mean([len(np.ravel(v)) for v in vOb])); f_pass = f_pass_parking(N, nb_mean)
-                b_pass = float(np.mean([b_pass_parking(N, len(np.ravel(v)), int(np.sum(v))) for v in vOb]))
+        if a.full:
+            passes0 = float((out["info"][:, 1] + out["info"][:, 6]).sum())      # passes of ONE launch of rank 0's batch (the launch the HIP events timed)
+            k_ms = float(np.median(ipm_ms))
+            if quad:
+                f_pass = F_PASS_QUAD; kernel = "obca_quad_ipm_kernel"
+                b_pass = b_iter_quad(N) * float(out["info"][:, 1].sum()) / max(1.0, passes0)      # per pass = per iteration x iterations / passes of this launch
             else:
-                f_pass = f_pass_parking(N, len(np.ravel(vOb))); b_pass = b_pass_parking(N, len(np.ravel(vOb)), int(np.sum(vOb)))
-            kernel = "obca_parking_ipm_kernel"
-        tflops = passes0 * f_pass / (k_ms * 1e-3) / 1e12
-        traffic, tsrc = (None, "skipped (--no-pmc)") if a.no_pmc or world > 1 else live_pmc_traffic(kernel, cfg, B, fast)
-        fp64_frac = tflops / FP64_PEAK_TFLOPS
-        # SURVEY 8d, Model B (the condensed variant these kernels are): executed flops; HBM bytes = I/O only -- the problem data in and the result tuple out, once per solve
-        io_bytes = B * (IO_BYTES_PER_SOLVE_QUAD if quad else io_bytes_parking(N, vOb, cfg == 5))
-        io_gbs = io_bytes / (k_ms * 1e-3) / 1e9
-        impl_bytes = passes0 * b_pass                                 # what the IMPLEMENTATION streams per launch by its own model: not the algorithm's bytes
-        impl_gbs = impl_bytes / (k_ms * 1e-3) / 1e9
-        step_s = dt / a.steps
-        roof = {"bound": "mfma",
-                "achieved": round(tflops, 3), "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(fp64_frac, 5),
-                "traffic": traffic, "traffic_source": tsrc,
-                "bound_detail": "SURVEY 8d Model B (condensed KKT solve): ALGORITHMIC work = executed fp64 flops per factorisation pass x the passes the kernel reports; algorithmic HBM bytes = the "
-                                "I/O of the solves only (algorithmic_bytes_io_only), a fraction ~1e-4 of the HBM roof -- so the flop roof is the one `frac` is quoted on: fp64 vector = fp64 matrix "
-                                "peak 78.6 TFLOP/s (the parking kernel issues no MFMA; the quadcopter sweep does).  `frac` is for ONE launch alone on the GPU (HIP events = rocprofv3 --stats); "
-                                "a lone launch ends with its slowest instance (3-4 x the mean number of passes), see `regime_of_value` for the pipelined load `value` is measured at",
-                "model": "SURVEY 8d Model B", "kernel": kernel, "kernel_ms": round(k_ms, 3), "kernel_ms_all": [round(x, 3) for x in ipm_ms],
-                "kernel_timing": "HIP events on the launch stream around the interior-point launches of ONE synchronous step of rank 0's batch, measured in this process after the "
-                                 "timed region (median of %d); nothing else runs on the GPU" % len(ipm_ms),
-                "passes_per_launch": int(passes0), "flops_per_pass_model": f_pass, "fp64_tflops": round(tflops, 3), "fp64_frac": round(fp64_frac, 5),
-                "algorithmic_bytes_io_only": int(io_bytes), "hbm_io_only_gbs": round(io_gbs, 3), "hbm_io_only_frac": round(io_gbs / HBM_PEAK_GBS, 7),
-                "implementation_bytes": int(impl_bytes), "implementation_bytes_per_pass_model": b_pass, "implementation_hbm_gbs": round(impl_gbs, 1),
-                "implementation_hbm_frac": round(impl_gbs / HBM_PEAK_GBS, 5),
-                "implementation_note": "implementation_* = the kernel's own streaming model (every array of the per-instance state x the times a factorisation pass reads / writes it, DESIGN.md "
-                                       "section 5): what the code moves because an instance's state (0.2 MB) does not fit the LDS share of its CU, NOT algorithmic bytes.  The working set of a "
-                                       "resident batch (1 024 x 0.2 MB = 205 MB) is about the size of the 256 MiB Infinity Cache and FETCH_SIZE / WRITE_SIZE count fabric requests including MALL "
-                                       "hits (MI355X_MICROARCH.md, HBM), so much of `traffic` never reaches HBM and the 8 TB/s roof does not bind it",
-                "regime_of_value": {"note": "the same work over the wall time of a pipelined step (%d launches in flight): device utilisation in the regime `value` is measured in, not a kernel roofline" % nS,
-                                    "fp64_tflops": round(passes0 * f_pass / step_s / 1e12, 3), "fp64_frac": round(passes0 * f_pass / step_s / 1e12 / FP64_PEAK_TFLOPS, 5),
-                                    "implementation_hbm_gbs": round(impl_bytes / step_s / 1e9, 1), "implementation_hbm_frac": round(impl_bytes / step_s / 1e9 / HBM_PEAK_GBS, 5)}}
-        if traffic is not None:     # measured bytes of one launch over the kernel time / the pipelined step time of THIS run
-            roof.update(traffic_over_io_only=round(traffic / io_bytes, 1), traffic_over_implementation_model=round(traffic / impl_bytes, 3),
-                        traffic_gbs_one_launch=round(traffic / (k_ms * 1e-3) / 1e9, 1), traffic_frac_of_hbm_peak_one_launch=round(traffic / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
-            roof["regime_of_value"].update(traffic_gbs=round(traffic / step_s / 1e9, 1), traffic_frac_of_hbm_peak=round(traffic / step_s / 1e9 / HBM_PEAK_GBS, 4))
-        if not quad:
-            sched = batches[0].last_schedule()
-            roof.update(ipm_launches_per_step=sched[0], slice_passes=sched[1], dualws_kernel_ms=round(float(np.median(dws_ms)), 3))
+                if cfg == 5:
+                    nb_mean = float(np.mean([len(np.ravel(v)) for v in vOb])); f_pass = f_pass_parking(N, nb_mean)
+                    b_pass = float(np.mean([b_pass_parking(N, len(np.ravel(v)), int(np.sum(v))) for v in vOb]))
+                else:
+                    f_pass = f_pass_parking(N, len(np.ravel(vOb))); b_pass = b_pass_parking(N, len(np.ravel(vOb)), int(np.sum(vOb)))
+                kernel = "obca_parking_ipm_kernel"
+            tflops = passes0 * f_pass / (k_ms * 1e-3) / 1e12
+            traffic, tsrc = (None, "skipped (--no-pmc)") if a.no_pmc or world > 1 else live_pmc_traffic(kernel, cfg, B, fast)
+            fp64_frac = tflops / FP64_PEAK_TFLOPS
+            # SURVEY 8d, Model B (the condensed variant these kernels are): executed flops; HBM bytes = I/O only -- the problem data in and the result tuple out, once per solve
+            io_bytes = B * (IO_BYTES_PER_SOLVE_QUAD if quad else io_bytes_parking(N, vOb, cfg == 5))
+            io_gbs = io_bytes / (k_ms * 1e-3) / 1e9
+            impl_bytes = passes0 * b_pass                                 # what the IMPLEMENTATION streams per launch by its own model: not the algorithm's bytes
+            impl_gbs = impl_bytes / (k_ms * 1e-3) / 1e9
+            step_s = dt / a.steps
+            roof = {"bound": "mfma",
+                    "achieved": round(tflops, 3), "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(fp64_frac, 5),
+                    "traffic": traffic, "traffic_source": tsrc,
+                    "bound_detail": "SURVEY 8d Model B (condensed KKT solve): ALGORITHMIC work = executed fp64 flops per factorisation pass x the passes the kernel reports; algorithmic HBM bytes = the "
+                                    "I/O of the solves only (algorithmic_bytes_io_only), a fraction ~1e-4 of the HBM roof -- so the flop roof is the one `frac` is quoted on: fp64 vector = fp64 matrix "
+                                    "peak 78.6 TFLOP/s (the parking kernel issues no MFMA; the quadcopter sweep does).  `frac` is for ONE launch alone on the GPU (HIP events = rocprofv3 --stats); "
+                                    "a lone launch ends with its slowest instance (3-4 x the mean number of passes), see `regime_of_value` for the pipelined load `value` is measured at",
+                    "model": "SURVEY 8d Model B", "kernel": kernel, "kernel_ms": round(k_ms, 3), "kernel_ms_all": [round(x, 3) for x in ipm_ms],
+                    "kernel_timing": "HIP events on the launch stream around the interior-point launches of ONE synchronous step of rank 0's batch, measured in this process after the "
+                                     "timed region (median of %d); nothing else runs on the GPU" % len(ipm_ms),
+                    "passes_per_launch": int(passes0), "flops_per_pass_model": f_pass, "fp64_tflops": round(tflops, 3), "fp64_frac": round(fp64_frac, 5),
+                    "algorithmic_bytes_io_only": int(io_bytes), "hbm_io_only_gbs": round(io_gbs, 3), "hbm_io_only_frac": round(io_gbs / HBM_PEAK_GBS, 7),
+                    "implementation_bytes": int(impl_bytes), "implementation_bytes_per_pass_model": b_pass, "implementation_hbm_gbs": round(impl_gbs, 1),
+                    "implementation_hbm_frac": round(impl_gbs / HBM_PEAK_GBS, 5),
+                    "implementation_note": "implementation_* = the kernel's own streaming model (every array of the per-instance state x the times a factorisation pass reads / writes it, DESIGN.md "
+                                           "section 5): what the code moves because an instance's state (0.2 MB) does not fit the LDS share of its CU, NOT algorithmic bytes.  The working set of a "
+                                           "resident batch (1 024 x 0.2 MB = 205 MB) is about the size of the 256 MiB Infinity Cache and FETCH_SIZE / WRITE_SIZE count fabric requests including MALL "
+                                           "hits on gfx950, so much of `traffic` never reaches HBM and the 8 TB/s roof does not bind it",
+                    "regime_of_value": {"note": "the same work over the wall time of a pipelined step (%d launches in flight): device utilisation in the regime `value` is measured in, not a kernel roofline" % nS,
+                                        "fp64_tflops": round(passes0 * f_pass / step_s / 1e12, 3), "fp64_frac": round(passes0 * f_pass / step_s / 1e12 / FP64_PEAK_TFLOPS, 5),
+                                        "implementation_hbm_gbs": round(impl_bytes / step_s / 1e9, 1), "implementation_hbm_frac": round(impl_bytes / step_s / 1e9 / HBM_PEAK_GBS, 5)}}
+            if traffic is not None:     # measured bytes of one launch over the kernel time / the pipelined step time of THIS run
+                roof.update(traffic_over_io_only=round(traffic / io_bytes, 1), traffic_over_implementation_model=round(traffic / impl_bytes, 3),
+                            traffic_gbs_one_launch=round(traffic / (k_ms * 1e-3) / 1e9, 1), traffic_frac_of_hbm_peak_one_launch=round(traffic / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
+                roof["regime_of_value"].update(traffic_gbs=round(traffic / step_s / 1e9, 1), traffic_frac_of_hbm_peak=round(traffic / step_s / 1e9 / HBM_PEAK_GBS, 4))
+            if not quad:
+                sched = batches[0].last_schedule()
+                roof.update(ipm_launches_per_step=sched[0], slice_passes=sched[1], dualws_kernel_ms=round(float(np.median(dws_ms)), 3))
         line = {
             "metric": "OBCA NLP solves/sec (N=80, 3 obs, batch) at 1/2/4/8 MI355X vs IPOPT-CPU", "value": round(conv_all * a.steps / dt, 2), "unit": "solves/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
@@ -795,25 +850,27 @@ def main():
                        "sharding": f"one host batch of {B_total} instances made on rank 0, scattered over {world} rank(s) (one scatter), solved device-resident, full result tuples "
                                    f"gathered on rank 0 (one gather) and validated there; no collective inside the timed region",
                        "streams": nS, "timed_region_s": round(dt, 3), "converged": conv_all, "exitflag_ok": conv_flag, "instances": B_total,
-                       "exitflag2": int((ef == 2).sum()), "copies_bit_identical": bool(same), "same_bits_after_foreign_pattern_on_the_cus": after_pattern, "mean_iterations": round(float(iters.mean()), 2), "max_iterations": int(iters.max()),
+                       "exitflag2": int((ef == 2).sum()), "mean_iterations": round(float(iters.mean()), 2), "max_iterations": int(iters.max()),
                        "p95_iterations": float(np.percentile(iters, 95)), "mean_passes": round(passes_all / B_total, 2),
-                       "single_batch_sync_solves_per_s": round(conv_all / world / float(np.median(sync_s)), 1),
-                       "single_batch_sync_note": "one batch issued and waited for (reset + DualMultWS + interior point, inputs resident): what a caller without several batches in flight gets",
                        "planning": None if not needs_planner(cfg, a.warm_start == "hybrid") else {
                            "seconds": round(t_plan, 2), "instances_per_rank": B, "host_cpus_visible": os.cpu_count(), "host_cpus_effective": effective_cpus(),
                            "end_to_end_solves_per_s": round(conv_all / (t_plan + dt / a.steps), 1),
                            "note": "warm starts of this config come from the host-side planner (Hybrid A* on the library's threads / 3-D A*), run ONCE before the timed region, "
                                    "every rank for its own slice; end_to_end = validated solves of one batch / (planning + one step): the planner, not the solve, bounds a "
                                    "pipeline that plans every instance afresh; never `value`"},
-                       "distinct_batches": distinct,
-                       "options": OPTION_NAMES[(C["kind"], fast)],
-                       ("reference_options" if fast else "fast_options"): other_leg,
-                       "other_configs": others,
-                       "host_pointer": host_rate,
-                       "host_pointer_note": "obca_parking_signed_dist_batch on host arrays (the entry point the Julia shim binds): packing, PCIe both ways, kernels, unpacking; never `value`"},
-            "roofline": roof,
-            "cpu_baseline": cpu,
+                       "options": OPTION_NAMES[(C["kind"], fast)]},
         }
+        if a.full:
+            line["config"].update({
+                "copies_bit_identical": bool(same), "same_bits_after_foreign_pattern_on_the_cus": after_pattern,
+                "single_batch_sync_solves_per_s": round(conv_all / world / float(np.median(sync_s)), 1),
+                "single_batch_sync_note": "one batch issued and waited for (reset + DualMultWS + interior point, inputs resident): what a caller without several batches in flight gets",
+                "distinct_batches": distinct,
+                ("reference_options" if fast else "fast_options"): other_leg,
+                "other_configs": others,
+                "host_pointer": host_rate,
+                "host_pointer_note": "obca_parking_signed_dist_batch on host arrays (the entry point the Julia shim binds): packing, PCIe both ways, kernels, unpacking; never `value`"})
+            line.update(roofline=roof, cpu_baseline=cpu)
         print(json.dumps(line))
     if dist is not None:
         dist.destroy_process_group()

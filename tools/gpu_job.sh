@@ -5,10 +5,10 @@
 #   stamp        git revision + md5 of the library + kernel symbols
 #   tests        pytest -m gpu (the whole GPU suite, parity first -- tests/conftest.py orders it), the census files of the tolerant tests
 #   smoke        __graft_entry__.smoke()
-#   bench        the default bench line (value, roofline with live PMC traffic, cpu_baseline, other configs)
+#   bench        the full bench line (bench.py --full: value, roofline with live PMC traffic, cpu_baseline, other configs)
 #   bench20      the driver's invocation: --gpus 1 --steps 20 --warmup 5
 #   quick        a short default-config line without the side legs (A/B of kernel changes): value, kernel_ms, single-batch rate
-#   cfg3 cfg4 cfg5   bench.py --config C
+#   cfg3 cfg4 cfg5   bench.py --full --config C
 #   stats        rocprofv3 --kernel-trace --stats of synchronous steps, configs 2 and 4 (kernel_stats.csv)
 #   pmc          FETCH_SIZE / WRITE_SIZE passes of both IPM kernels (separate passes, as MI355X_MICROARCH.md prescribes)
 #   sq           SQ counter groups of the parking kernel (tools/pmc_sq.sh) ; mfma: the quadcopter kernel's MFMA counters
@@ -21,7 +21,7 @@
 TAG=$1; shift
 export TMPDIR=/tmp
 R=$PWD; O=$R/gpurun_out/$TAG; C=$R/obca_amd/csrc; mkdir -p $O
-LEAN="--no-cpu-baseline --no-pmc --no-host-rate --no-distinct --no-ipopt-leg --no-other-configs"
+LEAN="--full --no-cpu-baseline --no-pmc --no-host-rate --no-distinct --no-ipopt-leg --no-other-configs"
 summ() { python - "$@" <<'PY'
 import json, sys
 for f in sys.argv[1:]:
@@ -41,16 +41,16 @@ for STEP in "$@"; do
     stamp) { echo "revision: $(cat $R/.revision 2>/dev/null)"; echo "library: $(md5sum $C/libobca_hip.so | cut -c1-12)"; rocminfo | grep -E "Uuid: +GPU"; /opt/rocm/lib/llvm/bin/llvm-nm -C --defined-only $C/libobca_hip.so 2>/dev/null | grep -i "ipm_kernel" | head -4; } > $O/STAMP.txt; cat $O/STAMP.txt ;;
     tests) timeout 1800 python -m pytest tests -m gpu -q -s 2>&1 | tail -60 > $O/pytest_gpu.log; tail -25 $O/pytest_gpu.log | cut -c1-400; cp gpurun_out/parity_census_*.txt $O/ 2>/dev/null ;;
     smoke) timeout 300 python __graft_entry__.py smoke 2>&1 | tail -1 | tee $O/smoke.log ;;
-    bench) timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err; summ $O/bench.json ;;
+    bench) timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err; summ $O/bench.json ;;
     bench20) timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_line.json 2> $O/bench_driver_line.err; summ $O/bench_driver_line.json ;;
     quick) timeout 300 python bench.py --steps 40 --warmup 8 $LEAN > $O/bench_quick.json 2> $O/bench_quick.err; summ $O/bench_quick.json ;;
     sched) # scheduling experiments on the pipelined default line: more streams in flight; the two-launch schedule forced for resident batches (OBCA_SLICE_ALWAYS)
       for S in 4 6 8 12; do timeout 300 python bench.py --steps 60 --warmup 12 --streams $S $LEAN > $O/bench_streams$S.json 2> $O/bench_streams$S.err; echo "streams $S"; summ $O/bench_streams$S.json; done
       for S in 4 8; do for P in 4 8; do OBCA_SLICE_ALWAYS=1 OBCA_SLICE_PASSES=$P timeout 300 python bench.py --steps 60 --warmup 12 --streams $S $LEAN > $O/bench_slice${P}_streams$S.json 2> $O/bench_slice${P}_streams$S.err; echo "sliced $P passes, streams $S"; summ $O/bench_slice${P}_streams$S.json; done; done ;;
-    cfg3|cfg4|cfg5) CF=${STEP#cfg}; timeout 900 python bench.py --config $CF --no-host-rate --steps 60 > $O/bench_cfg$CF.json 2> $O/bench_cfg$CF.err; summ $O/bench_cfg$CF.json ;;
+    cfg3|cfg4|cfg5) CF=${STEP#cfg}; timeout 900 python bench.py --full --config $CF --no-host-rate --steps 60 > $O/bench_cfg$CF.json 2> $O/bench_cfg$CF.err; summ $O/bench_cfg$CF.json ;;
     stats) cd /tmp
       timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_sync -o t -- python $R/bench.py --steps 8 --warmup 2 --streams 1 --sync-steps 4 $LEAN > $O/bench_sync_under_rocprof.json 2> $O/stats_sync.err
-      timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_quad -o t -- python $R/bench.py --config 4 --steps 4 --warmup 1 --streams 1 --sync-steps 2 --no-cpu-baseline --no-pmc --no-host-rate --no-ipopt-leg > $O/bench_quad_sync_under_rocprof.json 2> $O/stats_quad.err
+      timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_quad -o t -- python $R/bench.py --full --config 4 --steps 4 --warmup 1 --streams 1 --sync-steps 2 --no-cpu-baseline --no-pmc --no-host-rate --no-ipopt-leg > $O/bench_quad_sync_under_rocprof.json 2> $O/stats_quad.err
       cd $R; for f in $(find $O/stats_sync $O/stats_quad -name "*kernel_stats.csv"); do echo $f; head -6 $f | cut -c1-200; done ;;
     pmc) cd /tmp
       for K in FETCH_SIZE WRITE_SIZE; do
