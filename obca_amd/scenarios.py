@@ -249,6 +249,18 @@ def make_batch(sc, B, N=80, seed=20260925, goal_jitter=False, planner=None, work
                 ego=EGO.copy(), XYbounds=XYBOUNDS.copy())
 
 
+# short hops into the slot of the backwards scenario: from these starts the NLP is solvable down to N = 3 (N = 2 leaves it too few degrees of freedom)
+HOP_STARTS = np.array([[-3.0, 7.0, 0.0, 0.0], [-3.3, 7.2, 0.05, 0.0], [-2.7, 6.8, -0.05, 0.0], [-3.5, 7.5, 0.0, 0.0], [0.0, 2.3, np.pi / 2, 0.0], [-2.5, 7.4, 0.1, 0.0]])
+
+
+def make_hop_batch(N, starts=HOP_STARTS):
+    """the backwards scenario from starts a short hop before the slot, with warm_start_backwards: the instances of the shortest horizons"""
+    x0 = np.array(starts, float); B = len(x0)
+    A, b, vrows = scenario_hrep(BACKWARDS)
+    Ts, xWS, uWS = zip(*(warm_start_backwards(x0[i], BACKWARDS["xF"], N) for i in range(B)))
+    return dict(x0=x0, xF=np.tile(BACKWARDS["xF"], (B, 1)), Ts=np.array(Ts), xWS=np.stack(xWS), uWS=np.stack(uWS), A=A, b=b, vOb=vrows, N=N, L=L_WHEELBASE,
+                ego=EGO.copy(), XYbounds=XYBOUNDS.copy())
+
 # ---------------------------------------------------------------- quadcopter scenario (mainQuadcopter.jl:36-54, 131-138)
 QUAD_X0 = np.array([1, 1, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0.0])
 QUAD_XF = np.array([9, 3, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0.0])

@@ -1439,13 +1439,14 @@ static int parking_solve(int dist, int N, double Ts, double L, const double ego[
     int iters = r.iters;
     int retry = !ef && (r.status == ST_ERROR || r.status == ST_USERLIMIT);
     if (retry && dist && ref_constraints(&p, &l, z, 0)) { ef = 1; retry = 0; }       /* ParkingDist.jl:259-260, :284-285 */
+    int nreg = r.nreg;                                                  /* regularisations of the whole call, like the iterations (the kernels' info[6]) */
     if (retry) {
         /* second attempt from the last iterate (ParkingSignedDist.jl:259-263) */
         double *z2 = xcalloc(l.len, sizeof(double));
         memcpy(z2, z, sizeof(double) * l.nprimal);
         result_t r2;
         ipm_solve(&p, &l, &o, z2, &r2);
-        iters += r2.iters;
+        iters += r2.iters; nreg += r2.nreg;
         if (r2.status == ST_OPTIMAL) { ef = 1; memcpy(z, z2, sizeof(double) * l.len); r = r2; }
         else {
             if (r2.obj == r2.obj) { memcpy(z, z2, sizeof(double) * l.len); r = r2; }
@@ -1461,7 +1462,7 @@ static int parking_solve(int dist, int N, double Ts, double L, const double ego[
     memcpy(np, z + l.mu, sizeof(double) * 4 * nOb * (N + 1));
     if (slp) memcpy(slp, z + l.sl, sizeof(double) * nOb * (N + 1));
     *exitflag = ef;
-    if (info) { info[0] = r.status; info[1] = iters; info[2] = r.obj; info[3] = r.pinf; info[4] = r.dinf; info[5] = r.mu; info[6] = r.nreg; info[7] = r.t; }
+    if (info) { info[0] = r.status; info[1] = iters; info[2] = r.obj; info[3] = r.pinf; info[4] = r.dinf; info[5] = r.mu; info[6] = nreg; info[7] = r.t; }
     if (g_zfull) {
         memcpy(g_zfull, z, sizeof(double) * l.len);
         for (int k = 0; k <= N; k++) for (int q = 0; q < p.M; q++) { g_zfull[l.lam + k * p.M + q] /= p.rn[q]; g_zfull[l.zlam + k * p.M + q] *= p.rn[q]; }

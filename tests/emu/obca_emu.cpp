@@ -22,6 +22,8 @@ void emu_race_begin() {} void emu_race_buffer(const char *, const void *, long, 
 #endif
 static int g_csoc_len = 0;      // doubles of the c_soc buffer (0: as long as the iterate; the HIP host code allocates zxL - pi of the batch's largest layout)
 extern "C" void emu_set_csoc_len(int n) { g_csoc_len = n; }
+static int g_dsoc_len = 0;      // doubles of the correction's direction buffer (0: as long as the iterate; the HIP host code allocates zxL of the batch's largest layout, o_csoc)
+extern "C" void emu_set_dsoc_len(int n) { g_dsoc_len = n; }
 
 struct Scratch { double *z, *zn, *d, *as, *rs, *oc, *csoc, *dsoc; };
 static void alloc_scratch(int N, int len, Scratch &s) {
@@ -31,7 +33,7 @@ static void alloc_scratch(int N, int len, Scratch &s) {
 #endif
     s.z = (double *)calloc(len, 8); s.zn = (double *)calloc(len, 8); s.d = (double *)calloc(len, 8);
     s.as = (double *)calloc((size_t)(N + 1) * OB_AS, 8); s.rs = (double *)calloc((size_t)(N + 1) * OB_RS, 8);
-    s.oc = (double *)calloc((size_t)(N + 1) * OB_NOBMAX * OB_OC, 8); s.csoc = (double *)calloc(g_csoc_len ? g_csoc_len : len, 8); s.dsoc = (double *)calloc(len, 8);      // (c_soc: the equality rows, fewer than len)
+    s.oc = (double *)calloc((size_t)(N + 1) * OB_NOBMAX * OB_OC, 8); s.csoc = (double *)calloc(g_csoc_len ? g_csoc_len : len, 8); s.dsoc = (double *)calloc(g_dsoc_len ? g_dsoc_len : len, 8);      // (c_soc: the equality rows, fewer than len; d_soc: the primal-dual part below zxL)
 }
 static void free_scratch(Scratch &s) { free(s.z); free(s.zn); free(s.d); free(s.as); free(s.rs); free(s.oc); free(s.csoc); free(s.dsoc); }
 
@@ -139,7 +141,7 @@ static void emu_poison(int N, int len, Scratch &s, double *st) {
     if (m & 1) {
         for (int i = 0; i < len; i++) { s.zn[i] = nan_; s.d[i] = nan_; }
         for (int i = 0; i < (g_csoc_len ? g_csoc_len : len); i++) s.csoc[i] = nan_;
-        for (int i = 0; i < len; i++) s.dsoc[i] = nan_;
+        for (int i = 0; i < (g_dsoc_len ? g_dsoc_len : len); i++) s.dsoc[i] = nan_;
         for (size_t i = 0; i < (size_t)(N + 1) * OB_AS; i++) s.as[i] = nan_;
         for (size_t i = 0; i < (size_t)(N + 1) * OB_RS; i++) s.rs[i] = nan_;
         for (int i = 0; i < SL_SIZE; i++) st[i] = nan_;
@@ -167,7 +169,7 @@ int emu_solve(int N, const double *prob, const double *zinit, int len, const voi
     emu_race_begin();
     emu_race_buffer("iterate buffer A", s.z, len, 0, -1); emu_race_buffer("iterate buffer B", s.zn, len, 0, -1); emu_race_buffer("d", s.d, len, 0, -1);
     emu_race_buffer("as", s.as, (long)(N + 1) * OB_AS, OB_AS, -1); emu_race_buffer("rs", s.rs, (long)(N + 1) * OB_RS, OB_RS, RS_PAD);
-    emu_race_buffer("csoc", s.csoc, g_csoc_len ? g_csoc_len : len, 0, -1); emu_race_buffer("dsoc", s.dsoc, len, 0, -1); emu_race_buffer("slice record", st, SL_SIZE, 0, -1);
+    emu_race_buffer("csoc", s.csoc, g_csoc_len ? g_csoc_len : len, 0, -1); emu_race_buffer("dsoc", s.dsoc, g_dsoc_len ? g_dsoc_len : len, 0, -1); emu_race_buffer("slice record", st, SL_SIZE, 0, -1);
     struct RaceOff { ~RaceOff() { emu_race_end(); } } race_off_;
     solve_instance(N, ((const OptsAbi *)opts)->o, info, (gdbl *)st, 0, 0, ((const OptsAbi *)opts)->max_soc, ((const OptsAbi *)opts)->recalc_y, ((const OptsAbi *)opts)->lsq_init, ((const OptsAbi *)opts)->restoration);
     free(st);

@@ -61,7 +61,7 @@ def default_opts():
     return o
 
 
-def parking_signed_dist_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, dist=False, max_soc=0, recalc_y=0, lsq_init=0, restoration=0, **_):
+def parking_signed_dist_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, dist=False, max_soc=0, recalc_y=0, lsq_init=0, restoration=0, max_iter=None, **_):
     emu = load()
     x0 = np.reshape(x0, (-1, 4)); B = x0.shape[0]
     v = np.ravel(vOb).astype(int); nOb, M = len(v), int(v.sum()); Lz = P.layout(N, nOb, M)
@@ -69,6 +69,8 @@ def parking_signed_dist_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, rx, ry
     rl = P.row_lengths(A); An = A / rl[:, None]; bn = b / rl          # the kernels see unit-length rows (obca_hip.hip: batch_upload_range); lambda comes back rescaled
     g = np.array([(ego[0] + ego[2]) / 2, (ego[1] + ego[3]) / 2, (ego[0] + ego[2]) / 2, (ego[1] + ego[3]) / 2]); off = (ego[0] + ego[2]) / 2 - ego[2]
     eo = default_opts(); eo.max_soc = int(max_soc); eo.recalc_y = int(recalc_y); eo.lsq_init = int(lsq_init); eo.restoration = int(restoration); nsoc = np.zeros((B, 3), int)
+    if max_iter is not None:
+        eo.max_iter = int(max_iter)
     Tsv = np.broadcast_to(np.asarray(Ts, float), (B,))
     xp = np.zeros((B, 4, N + 1)); up = np.zeros((B, 2, N)); ts = np.zeros((B, N + 1)); ef = np.zeros(B, np.int32); info = np.zeros((B, 8))
     lps, nps, sls = [], [], []
@@ -93,13 +95,13 @@ def parking_signed_dist_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, rx, ry
     return dict(xp=xp, up=up, timeScale=ts, exitflag=ef, lp=lps, np=nps, sl=sls, info=info, iters=info[:, 1].astype(int), obj=info[:, 2], status=info[:, 0].astype(int), nsoc=nsoc)
 
 
-def quadcopter_signed_dist_batch(x0, xF, N, Ts, R, ob, xWS, timeWS, dual_ws=True, dist=False, max_soc=0, lsq_init=0, obj_scaling=0, **_):
+def quadcopter_signed_dist_batch(x0, xF, N, Ts, R, ob, xWS, timeWS, dual_ws=True, dist=False, max_soc=0, lsq_init=0, obj_scaling=0, max_iter=3000, **_):
     """the quadcopter kernel source (obca_quad_solver.h) as a host emulation, with the signature of obca_amd.quadcopter_signed_dist_batch"""
     emu = load()
     x0 = np.reshape(x0, (-1, 12)); B = x0.shape[0]; xF = np.reshape(xF, (-1, 12)); L = P.quad_layout(N); N1 = N + 1
     Tsv = np.broadcast_to(np.asarray(Ts, float), (B,)); tw = np.broadcast_to(np.asarray(timeWS, float), (B,))
     xp = np.zeros((B, 12, N1)); up = np.zeros((B, 4, N)); ts = np.zeros((B, N1)); ef = np.zeros(B, np.int32); info = np.zeros((B, 8)); lp = np.zeros((B, 30, N1)); sl = np.zeros((B, 5, N1))
-    eo = default_opts(); eo.max_iter = 3000; eo.dw_min = 1e-10; eo.max_soc = int(max_soc); eo.lsq_init = int(lsq_init); eo.obj_scaling = int(obj_scaling)            # QuadcopterSignedDist.jl:28-31 (obca_quadcopter_default_opts)
+    eo = default_opts(); eo.max_iter = int(max_iter); eo.dw_min = 1e-10; eo.max_soc = int(max_soc); eo.lsq_init = int(lsq_init); eo.obj_scaling = int(obj_scaling)            # QuadcopterSignedDist.jl:28-31 (obca_quadcopter_default_opts)
     for i in range(B):
         prob = P.pack_quad_problem(x0[i], xF[i], N, Tsv[i], R, ob, np.asarray(xWS[i], float).reshape(N1, 12), tw[i], dual_ws=int(bool(dual_ws)), dist=int(bool(dist)))
         z = np.zeros(L["len"])

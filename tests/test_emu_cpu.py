@@ -586,3 +586,51 @@ def test_block_restoration_in_the_kernels_follows_the_oracle(oracle):
         emu.emu_solve(C.c_int(N), dp(prob), dp(z0), C.c_int(L["len"]), C.byref(eo), dp(za), dp(ia))
         emu.emu_solve_sliced(C.c_int(N), dp(prob), dp(z0), C.c_int(L["len"]), C.byref(eo), C.c_int(5), dp(zb), dp(ib))
         assert ia[7] == 1 and np.array_equal(ia, ib) and np.array_equal(za, zb), (mode, ia, ib)
+
+
+def _horizon_edge_batch(N):
+    return S.make_hop_batch(N, S.HOP_STARTS[:2]) if N <= 7 else S.make_batch(S.BACKWARDS, 1, N, seed=N)
+
+
+@pytest.mark.parametrize("dist,N", [(0, 3), (1, 3), (0, 64), (0, 65), (1, 65), (0, 127), (0, 128)])
+def test_emu_full_solve_at_the_horizon_edges_matches_oracle(oracle, dist, N):
+    """CPU twin of tests/test_gpu_parity.py::test_parking_horizon_sweep_matches_oracle: full solves of the kernel source at the horizons where its loops change shape (a single
+    stage pair, one or two rounds of 64 lanes, every LDS array at OBCA_NMAX), iteration for iteration against the oracle"""
+    import emu_solver as E
+    bt = _horizon_edge_batch(N); B = len(bt["x0"])
+    xWS = bt["xWS"].copy(); xWS[:, 0, :] = bt["x0"]
+    out = E.parking_signed_dist_batch(bt["x0"], bt["xF"], N, bt["Ts"], bt["L"], bt["ego"], bt["XYbounds"], bt["vOb"], bt["A"], bt["b"], xWS[:, :, 0], xWS[:, :, 1], xWS[:, :, 2], 0, xWS,
+                                      bt["uWS"], dist=bool(dist))
+    for i in range(B):
+        r = oracle.parking_signed_dist(bt["x0"][i], bt["xF"][i], N, bt["Ts"][i], bt["L"], bt["ego"], bt["XYbounds"], bt["vOb"], bt["A"], bt["b"], xWS[i, :, 0], xWS[i, :, 1], xWS[i, :, 2], 0,
+                                       xWS[i], bt["uWS"][i], dist=dist)
+        assert out["exitflag"][i] == r["exitflag"] == 1 and out["status"][i] == r["status"] == 0 and out["iters"][i] == r["iters"] and out["info"][i, 6] == r["nreg"], (i, out["iters"][i], r["iters"])
+        assert np.abs(out["xp"][i] - r["xp"]).max() < 1e-8 and np.abs(out["up"][i] - r["up"]).max() < 1e-8 and abs(out["timeScale"][i, 0] - r["t"]) < 1e-10
+        assert abs(out["obj"][i] - r["obj"]) < 1e-10 * max(1.0, abs(r["obj"]))
+
+
+@pytest.mark.parametrize("N", [3, 65, 128])
+def test_emu_first_iterates_match_the_oracle_tightly(oracle, N):
+    """CPU twin of tests/test_gpu_parity.py::test_parking_first_iterates_match_the_oracle_tightly: max_iter = k <= 5 (both attempts stop at k, the point after 2k Newton steps),
+    both formulations, both option sets -- every returned quantity against the oracle to 1e-9 relative to max(1, |oracle|), the regularisation count exactly"""
+    import emu_solver as E
+    bt = _horizon_edge_batch(N)
+    xWS = bt["xWS"].copy(); xWS[:, 0, :] = bt["x0"]
+    for dist in (0, 1):
+        for ref in (0, 1):
+            kw = dict(max_soc=4, recalc_y=1, lsq_init=1, restoration=1) if ref else {}
+            for k in range(6):
+                out = E.parking_signed_dist_batch(bt["x0"], bt["xF"], N, bt["Ts"], bt["L"], bt["ego"], bt["XYbounds"], bt["vOb"], bt["A"], bt["b"], xWS[:, :, 0], xWS[:, :, 1],
+                                                  xWS[:, :, 2], 0, xWS, bt["uWS"], dist=bool(dist), max_iter=k, **kw)
+                oo = oracle.default_opts(); oo.max_iter = k
+                for n_, v_ in kw.items():
+                    setattr(oo, n_, v_)
+                for i in range(len(bt["x0"])):
+                    r = oracle.parking_signed_dist(bt["x0"][i], bt["xF"][i], N, bt["Ts"][i], bt["L"], bt["ego"], bt["XYbounds"], bt["vOb"], bt["A"], bt["b"], xWS[i, :, 0], xWS[i, :, 1],
+                                                   xWS[i, :, 2], 0, xWS[i], bt["uWS"][i], opts=oo, dist=dist)
+                    tag = (N, dist, ref, k, i)
+                    assert out["status"][i] == r["status"] == 1 and out["iters"][i] == r["iters"] == 2 * k and out["info"][i, 6] == r["nreg"], tag
+                    for q in ("xp", "up", "lp", "np", "sl", "timeScale"):
+                        assert np.abs(np.asarray(out[q][i]) - r[q]).max() < 1e-9 * max(1.0, np.abs(r[q]).max()), tag + (q,)
+                    for j, q in ((2, "obj"), (3, "pinf"), (4, "dinf"), (5, "mu")):
+                        assert abs(out["info"][i, j] - r[q]) < 1e-9 * max(1.0, abs(r[q])), tag + (q,)

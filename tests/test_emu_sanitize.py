@@ -43,6 +43,7 @@ def parking(tag, bt, N, idx, **kw):
         v, A, b = (bt["vOb"][i], bt["A"][i], bt["b"][i]) if ragged else (bt["vOb"], bt["A"], bt["b"])
         v_ = np.ravel(v).astype(int); Lz = E.P.layout(N, len(v_), int(v_.sum()))
         lib.emu_set_csoc_len(C.c_int(Lz["zxL"] - Lz["pi"]))                       # the size obca_hip.hip gives the c_soc buffer (for the batch's largest layout; per instance is stricter)
+        lib.emu_set_dsoc_len(C.c_int(Lz["zxL"]))                                  # ... and the correction's direction in front of it (o_csoc)
         o = E.parking_signed_dist_batch(bt["x0"][sl], bt["xF"][sl], N, Ts[sl], bt["L"], bt["ego"], bt["XYbounds"], v, A, b, xWS[sl, :, 0], xWS[sl, :, 1], xWS[sl, :, 2], 0, xWS[sl], bt["uWS"][sl], **kw)
         done.append((tag, i, int(o["iters"][0]), int(o["exitflag"][0])))
 
@@ -53,10 +54,18 @@ bt = S.make_batch(S.BACKWARDS, 4, 80); parking("backwards N=80", bt, 80, range(1
 bt = S.make_batch(S.BACKWARDS, 4, 13); parking("backwards N=13 (odd horizon)", bt, 13, range(2), **REF)
 mx = S.make_mixed_batch(12, 24, seed=5, min_obstacles=1, max_extra=13, rows=(3, 8), max_rows=64)
 parking("1-16 obstacles of up to 8 rows", mx, 24, range(6)); parking("1-16 obstacles, IPOPT configuration", mx, 24, range(3), **REF)
+bt = S.make_hop_batch(3, S.HOP_STARTS[:1]); parking("hop N=3 (a single stage pair)", bt, 3, range(1), **REF)
+bt = S.make_hop_batch(2, S.HOP_STARTS[:1]); parking("hop N=2 (too few degrees of freedom)", bt, 2, range(1))
+bt = S.make_batch(S.BACKWARDS, 1, 65); parking("backwards N=65 (two rounds of 64)", bt, 65, range(1), **REF)
+bt = S.make_batch(S.BACKWARDS, 1, 128); parking("backwards N=128 (OBCA_NMAX)", bt, 128, range(1))
 q = S.make_quad_batch(2, 12, seed=5)
 for kw in (dict(), dict(max_soc=4, lsq_init=1, obj_scaling=1)):
     o = E.quadcopter_signed_dist_batch(q["x0"], q["xF"], 12, q["Ts"], q["R"], q["ob"], q["xWS"], q["timeWS"], **kw)
     done.append(("quadcopter N=12 %%s" %% (kw or "",), 0, int(o["iters"][0]), int(o["exitflag"][0])))
+for Nq in (2, 4, 128):
+    q = S.make_quad_batch(1, Nq, seed=5)
+    o = E.quadcopter_signed_dist_batch(q["x0"], q["xF"], Nq, q["Ts"], q["R"], q["ob"], q["xWS"], q["timeWS"])
+    done.append(("quadcopter N=%%d" %% Nq, 0, int(o["iters"][0]), int(o["exitflag"][0])))
 for d in done:
     print("SOLVED", *d)
 if variant == "race":
@@ -82,7 +91,8 @@ def test_no_cross_lane_hazard_through_hbm_between_two_drains():
     solved = [l for l in r.stdout.splitlines() if l.startswith("SOLVED")]
     hazards = [l for l in r.stdout.splitlines() if l.startswith("HAZARD")]
     summary = [l for l in r.stdout.splitlines() if l.startswith("SUMMARY")][0].split()
-    assert len(solved) >= 20 and sum(int(l.split()[-1]) == 1 for l in solved) >= len(solved) - 2, solved      # the solves are real ones (exit flag 1)
+    meant = [l for l in solved if " N=2 " not in l]                     # (the N = 2 solves are known to fail: too few degrees of freedom)
+    assert len(solved) >= 20 and sum(int(l.split()[-1]) == 1 for l in meant) >= len(meant) - 2, solved      # the solves are real ones (exit flag 1)
     assert int(summary[4]) > 10_000_000, summary                     # the log saw the traffic (tens of millions of accesses)
     assert int(summary[6]) > 0, summary                              # ... including the stores to the dummy slot of the Riccati record, the one shared word by design
     assert not hazards, "\n".join(hazards)
