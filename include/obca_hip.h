@@ -165,6 +165,24 @@ int obca_batch_last_schedule(const obca_batch *bt, int *ipm_launches, int *slice
 int obca_batch_download(obca_batch *bt, double *xp, double *up, double *timeScale, int *exitflag, double *lp, double *np,
                         double *slp, double *info);
 int obca_batch_scratch_bytes(const obca_batch *bt, long long *bytes);
+/* A-posteriori check of the LAST SOLUTION of a resident batch, on the device (obca_validate.h; the numpy statement of the same classes is obca_amd/validate.py).
+ * viol (14 x B, may be NULL): per instance the 13 classes of validate.parking_constraints_full in the conventions of validate.validate_parking, in the order
+ *   u_bounds, x_bounds, ts_bounds, ts_chain, dual_pos, start, end, dyn, steer_rate, norm, rot, sep, penetration
+ * (signed-distance formulation: rows with the instance's slack, norm = max | |A'lam|^2 - 1 |; dist formulation: rows without slack, norm = max(|A'lam|^2 - 1); fixTime: t = 1),
+ * then ref_worst: the largest "should be <= 0" quantity of the reference's own acceptance test ParkingConstraints.jl:29-149 with its quirks (only the last obstacle, no slack,
+ * only the speed row of the dynamics in variable-time mode, the steering rate over timeScale[1]).  All values in the caller's units (those of obca_batch_download).
+ * ok[i] = every class except penetration <= tol (tol <= 0: 5e-5); ref_ok[i] (may be NULL) = ref_worst <= 5e-5, the reference's fixed tolerance.  A non-finite entry anywhere in
+ * the solution gives ok = ref_ok = 0 and non-finite classes.  Only these outputs are downloaded (16 doubles per instance).  Returns -1 if nothing has been solved since the
+ * last upload or shift.  Synchronises the batch's stream. */
+int obca_batch_validate(obca_batch *bt, double tol, int *ok /* B */, int *ref_ok /* B, may be NULL */, double *viol /* 14 x B, may be NULL */);
+int obca_batch_validate_ms(obca_batch *bt, float *ms);   /* HIP-event duration of the last validate kernel of this batch */
+/* ParkingConstraints(x0,xF,N,Ts,L,ego,XYbounds,nOb,vOb,A,b,x,u,l,n,timeScale,fixTime,sd) -- AutonomousParking/ParkingConstraints.jl:29 -- for arbitrary trajectories in host
+ * memory: the same outputs as obca_batch_validate (ref_ok is the reference's verdict with sd = 1 - dist).  Problem arguments and packing as in obca_parking_signed_dist_batch;
+ * x 4 x (N+1) x B, u 2 x N x B, l / n / sl packed like lp / np / slp; timeScale (N+1) x B may vary over the stages (ts_chain and dyn honour that); sl == NULL: zeros. */
+int obca_parking_constraints_batch(obca_ctx *ctx, int B, int N, const double *Ts /* B */, double L, const double ego[4], const double XYbounds[4], int fixTime,
+                                   const double *x0, const double *xF, const int *nOb, const int *vOb, const double *A, const double *b, int dist,
+                                   const double *x, const double *u, const double *timeScale, const double *l, const double *n, const double *sl /* may be NULL */,
+                                   double tol, int *ok, int *ref_ok /* may be NULL */, double *viol /* 14 x B, may be NULL */);
 #ifdef OBCA_PROFILE      /* profiling build only (libobca_hip_prof.so: per-phase shader clocks, tools/phase_profile.py); not an entry point of the product library */
 int obca_batch_debug_phase_cycles(obca_batch *bt, double *out /* B x 16 */);
 #endif
@@ -207,6 +225,15 @@ int obca_quad_batch_kernel_ms(obca_quad_batch *bt, float *ipm_ms);
 int obca_quad_batch_download(obca_quad_batch *bt, double *xp, double *up, double *timeScale, int *exitflag, double *lp, double *slack,
                              double *info);
 int obca_quad_batch_scratch_bytes(const obca_quad_batch *bt, long long *bytes);
+/* constrSatisfaction(x,u,timeScale,x0,xF,Ts,lambda,ob1..ob5,R) -- QuadcopterNavigation/constrSatisfaction.jl:25-204 -- on the device.  viol (9 x B, may be NULL): the classes
+ * start, end, u_bounds, x_bounds, dyn, ts_chain, dual_pos, norm, sep of validate.validate_quadcopter, quirks kept (bounds, norm and separation on stages 1..N only, the
+ * gyroscopic terms at stage 1's rates).  ok[i]: bounds not above 0, the other classes not above tol (tol <= 0: 1e-3), every entry finite.
+ * obca_quad_batch_validate checks the last solution of a resident batch (-1 if nothing has been solved since the last upload), the _batch entry arbitrary trajectories in
+ * host memory (x 12 x (N+1) x B, u 4 x N x B, timeScale (N+1) x B, lambda 30 x (N+1) x B, ob 6 x 5 x B). */
+int obca_quad_batch_validate(obca_quad_batch *bt, double tol, int *ok /* B */, double *viol /* 9 x B, may be NULL */);
+int obca_quad_batch_validate_ms(obca_quad_batch *bt, float *ms);
+int obca_quadcopter_constr_satisfaction_batch(obca_ctx *ctx, int B, int N, const double *Ts /* B */, double R, const double *x0, const double *xF, const double *ob,
+                                              const double *x, const double *u, const double *timeScale, const double *lambda, double tol, int *ok, double *viol);
 #ifdef OBCA_PROFILE
 int obca_quad_batch_debug_phase_cycles(obca_quad_batch *bt, double *out /* B x 16 */);
 #endif

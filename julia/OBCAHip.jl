@@ -6,6 +6,8 @@
 #   ParkingDist(...)                                                                       (AutonomousParking/ParkingDist.jl:29)
 #   QuadcopterSignedDist(x0,xF,N,Ts,R,ob1,ob2,ob3,ob4,ob5,xWS,uWS,timeWS)                  (QuadcopterNavigation/QuadcopterSignedDist.jl:25)
 #   QuadcopterDist(...)                                                                    (QuadcopterNavigation/QuadcopterDist.jl:25)
+#   ParkingConstraints(x0,xF,N,Ts,L,ego,XYbounds,nOb,vOb,A,b,x,u,l,n,timeScale,fixTime,sd) (AutonomousParking/ParkingConstraints.jl:29)
+#   constrSatisfaction(x,u,timeScale,x0,xF,Ts,lambda,ob1,ob2,ob3,ob4,ob5,R)                (QuadcopterNavigation/constrSatisfaction.jl:25)
 # plus batched variants and multi-GPU contexts.  Julia arrays are column-major, which is exactly the "stage-contiguous" layout of the C ABI
 # (include/obca_hip.h), so every array is passed with zero copies.
 #
@@ -138,6 +140,39 @@ function ParkingDist(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, rx, ry, ry
     return xp, up, timeScalep, Int(ef[1]), time() - t0, lp, np          # ParkingDist.jl:313
 end
 
+"""
+    ParkingConstraints_batch(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, u, l, n, timeScale, fixTime, sd; sl=nothing, tol=5e-5)
+
+Batched a-posteriori check on the GPU (obca_parking_constraints_batch): x0, xF 4xB; Ts a vector of length B; x 4x(N+1)xB; u 2xNxB; l Mx(N+1)xB; n 4nObx(N+1)xB;
+timeScale (N+1)xB (it may vary over the stages); sl nObx(N+1)xB or nothing (zeros); the obstacle set is shared by the batch.  Returns (ok B, ref_ok B, viol 14xB):
+ok = every class of the full checker except the penetration <= tol, ref_ok = the reference's own test (ParkingConstraints.jl:29-149, quirks included) at 5e-5,
+viol = u_bounds, x_bounds, ts_bounds, ts_chain, dual_pos, start, end, dyn, steer_rate, norm, rot, sep, penetration, ref_worst.
+"""
+function ParkingConstraints_batch(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, u, l, n, timeScale, fixTime, sd; sl=nothing, tol=5e-5)
+    B = size(x0, 2)
+    nObs = fill(Cint(nOb), B); vflat = repeat(Cint.(vec(vOb)), B)
+    At = repeat(vec(permutedims(f64(A))), B); bt = repeat(vec(f64(b)), B)
+    ok = zeros(Cint, B); rok = zeros(Cint, B); viol = zeros(14, B)
+    rc = ccall((:obca_parking_constraints_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Cdouble, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}),
+               ctx().h, B, N, f64(vec(Ts)), L, f64(vec(ego)), f64(vec(XYbounds)), fixTime, f64(x0), f64(xF), nObs, vflat, At, bt, sd == 1 ? 0 : 1,
+               f64(x), f64(u), f64(timeScale), f64(l), f64(n), sl === nothing ? C_NULL : f64(sl), tol, ok, rok, viol)
+    rc == 0 || error("obca_parking_constraints_batch failed: " * lasterr(ctx()))
+    return ok, rok, viol
+end
+
+"Drop-in for ParkingConstraints.jl:29 (one instance): same arguments (x 4x(N+1), u 2xN, l Mx(N+1), n 4nObx(N+1), timeScale of length N+1), returns 1 or 0 like :141-148."
+function ParkingConstraints(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, u, l, n, timeScale, fixTime, sd)
+    M = sum(vOb)
+    ts = length(timeScale) == 1 ? fill(Float64(timeScale[1]), N + 1) : f64(vec(timeScale))[1:N+1]
+    ok, rok, viol = ParkingConstraints_batch(reshape(f64(vec(x0)), 4, 1), reshape(f64(vec(xF)), 4, 1), N, [Float64(Ts)], L, ego, XYbounds, nOb, vOb, A, b,
+        reshape(f64(x)[:, 1:N+1], 4, N + 1, 1), reshape(f64(u)[:, 1:N], 2, N, 1), reshape(f64(l)[:, 1:N+1], M, N + 1, 1), reshape(f64(n)[:, 1:N+1], 4nOb, N + 1, 1),
+        reshape(ts, N + 1, 1), fixTime, sd)
+    return Int(rok[1])
+end
+
 "Drop-in for DualMultWS.jl:29; `ego` defaults to the global the reference reads (DualMultWS.jl:39-45). Returns (lp (N+1)xM, np (N+1)x4nOb)."
 function DualMultWS(N, nOb, vOb, A, b, rx, ry, ryaw; ego=Main.ego)
     M = sum(vOb)
@@ -179,6 +214,33 @@ function QuadcopterSignedDist_batch(x0, xF, N, Ts, R, ob, xWS, timeWS; dual_ws::
     end
     rc == 0 || error("obca_quadcopter_(signed_)dist_batch failed: " * lasterr(ctx()))
     return xp, up, ts, ef, time() - t0, lp, info[1, :]
+end
+
+"""
+    constrSatisfaction_batch(x, u, timeScale, x0, xF, Ts, lambda, ob, R; tol=1e-3)
+
+Batched constrSatisfaction on the GPU (obca_quadcopter_constr_satisfaction_batch): x 12x(N+1)xB; u 4xNxB; timeScale (N+1)xB; x0, xF 12xB; Ts a vector of length B;
+lambda 30x(N+1)xB; ob 6x5xB.  Returns (ok B, viol 9xB): viol = start, end, u_bounds, x_bounds, dyn, ts_chain, dual_pos, norm, sep (constrSatisfaction.jl:25-204).
+"""
+function constrSatisfaction_batch(x, u, timeScale, x0, xF, Ts, lambda, ob, R; tol=1e-3)
+    B = size(x, 3); N = size(x, 2) - 1
+    ok = zeros(Cint, B); viol = zeros(9, B)
+    rc = ccall((:obca_quadcopter_constr_satisfaction_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Cdouble, Ptr{Cint}, Ptr{Cdouble}),
+               ctx().h, B, N, f64(vec(Ts)), Float64(R), f64(x0), f64(xF), f64(ob), f64(x), f64(u), f64(timeScale), f64(lambda), tol, ok, viol)
+    rc == 0 || error("obca_quadcopter_constr_satisfaction_batch failed: " * lasterr(ctx()))
+    return ok, viol
+end
+
+"Drop-in for constrSatisfaction.jl:25 (call sites mainQuadcopter.jl:147,154): same arguments (x 12x(N+1), u 4xN, lambda 30x(N+1)), returns true / false."
+function constrSatisfaction(x, u, timeScale, x0, xF, Ts, lambda, ob1, ob2, ob3, ob4, ob5, R)
+    N = size(x, 2) - 1
+    ob = reshape(f64(vcat(map(vec, (ob1, ob2, ob3, ob4, ob5))...)), 6, 5, 1)
+    ts = length(timeScale) == 1 ? fill(Float64(timeScale[1]), N + 1) : f64(vec(timeScale))[1:N+1]
+    ok, viol = constrSatisfaction_batch(reshape(f64(x), 12, N + 1, 1), reshape(f64(u), 4, N, 1), reshape(ts, N + 1, 1), reshape(f64(vec(x0)), 12, 1), reshape(f64(vec(xF)), 12, 1),
+        [Float64(Ts)], reshape(f64(lambda), 30, N + 1, 1), ob, R)
+    return ok[1] == 1
 end
 
 _quad_status(c) = c == 0 ? "Optimal" : (c == 1 ? "UserLimit" : "Error")

@@ -1,5 +1,5 @@
 # main_quadcopter.jl -- the flow of QuadcopterNavigation/mainQuadcopter.jl (scenario :29-54, 3-D A* :116-129, Ts_as :131, warm start :134-138,
-# QuadcopterDist :145, QuadcopterSignedDist :152) on top of the HIP drop-in (julia/OBCAHip.jl).  Julia >= 1.6; no plots, no constrSatisfaction.
+# QuadcopterDist :145, QuadcopterSignedDist :152, constrSatisfaction :147,154) on top of the HIP drop-ins (julia/OBCAHip.jl).  Julia >= 1.6; no plots.
 # NOT executed in this repository's build environment (no Julia there); tests/test_gpu_quad_parity.py::test_reference_main_call_runs_as_is runs the
 # same sequence through the same C entry points from Python.
 #
@@ -40,11 +40,13 @@ function main()
     uWS_as = 0.5 * ones(4, N_as); timeWS_as = 1                                     # :137-138
     println("Trajectory using Distance Approach (Collision Avoidance, A star)")    # :144-145
     xp1, up1, scaleTime1, exitflag1, time1, l1, status1 = OBCAHip.QuadcopterDist(x0, xF, N_as, Ts_as, egoR, ob12, ob22, ob32, ob42, ob52, xWS_as, uWS_as, timeWS_as; dual_ws=false)
+    trajFeas1 = OBCAHip.constrSatisfaction(xp1, up1, scaleTime1, x0, xF, Ts_as, l1, ob12, ob22, ob32, ob42, ob52, egoR)   # :147
     println("Trajectory using Signed Distance Approach (Minimum Penetration, A star)")   # :151-152
     xp2, up2, scaleTime2, exitflag2, time2, l2, status2 = OBCAHip.QuadcopterSignedDist(x0, xF, N_as, Ts_as, egoR, ob12, ob22, ob32, ob42, ob52, xWS_as, uWS_as, timeWS_as; dual_ws=false)
+    trajFeas2 = OBCAHip.constrSatisfaction(xp2, up2, scaleTime2, x0, xF, Ts_as, l2, ob12, ob22, ob32, ob42, ob52, egoR)   # :154
     @printf("  A*: %d way-points, %.3f s;  N = %d, Ts = %.2f\n", N_as + 1, timeAstar, N_as, Ts_as)
-    @printf("  Distance:        exitflag %d (%s)  %.4f s  timeScale %.4f\n", exitflag1, status1, time1, scaleTime1[1])
-    @printf("  Signed distance: exitflag %d (%s)  %.4f s  timeScale %.4f  final position error %.2e\n", exitflag2, status2, time2, scaleTime2[1], maximum(abs.(xp2[1:3, end] .- vec(xF)[1:3])))
+    @printf("  Distance:        exitflag %d (%s)  %.4f s  timeScale %.4f  feasible %s\n", exitflag1, status1, time1, scaleTime1[1], trajFeas1)
+    @printf("  Signed distance: exitflag %d (%s)  %.4f s  timeScale %.4f  final position error %.2e  feasible %s\n", exitflag2, status2, time2, scaleTime2[1], maximum(abs.(xp2[1:3, end] .- vec(xF)[1:3])), trajFeas2)
     println("---- Done ----")
     return xp2, up2, scaleTime2, exitflag2
 end

@@ -20,6 +20,7 @@ import os
 import subprocess
 import time
 import numpy as np
+from .validate import VIOL_NAMES, QUAD_VIOL_NAMES
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
@@ -47,7 +48,7 @@ def library_path():
 
 def build_library(force=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("obca_hip.hip", "obca_solver.h", "obca_solver_lanes.h", "obca_solver_assemble.h", "obca_solver_riccati.h", "obca_solver_direction.h", "obca_solver_ipm.h", "obca_model.h", "obca_quad_solver.h", "obca_quad_model.h")] + \
+    srcs = [os.path.join(_CSRC, f) for f in ("obca_hip.hip", "obca_solver.h", "obca_solver_lanes.h", "obca_solver_assemble.h", "obca_solver_riccati.h", "obca_solver_direction.h", "obca_solver_ipm.h", "obca_model.h", "obca_quad_solver.h", "obca_quad_model.h", "obca_validate.h")] + \
            [os.path.join(_HERE, "..", "include", "obca_hip.h"), os.path.join(_HERE, "buildflags.py")]      # (that file holds the compile flags)
     if not force and os.path.exists(_LIBPATH) and all(os.path.getmtime(_LIBPATH) >= os.path.getmtime(s) for s in srcs):
         return _LIBPATH
@@ -79,7 +80,8 @@ EXPORTS = ["obca_create", "obca_create_multi", "obca_device_count", "obca_visibl
            "obca_dualmult_ws_batch", "obca_parking_signed_dist_batch", "obca_parking_dist_batch", "obca_batch_create", "obca_batch_destroy",
            "obca_batch_set_formulation", "obca_batch_shift_warm_start",
            "obca_batch_upload", "obca_batch_solve", "obca_batch_sync", "obca_batch_kernel_ms", "obca_batch_last_schedule", "obca_batch_download",
-           "obca_batch_scratch_bytes",
+           "obca_batch_scratch_bytes", "obca_batch_validate", "obca_batch_validate_ms", "obca_parking_constraints_batch",
+           "obca_quad_batch_validate", "obca_quad_batch_validate_ms", "obca_quadcopter_constr_satisfaction_batch",
            "obca_quadcopter_default_opts", "obca_quadcopter_reference_opts", "obca_quadcopter_signed_dist_batch", "obca_quadcopter_dist_batch", "obca_quad_batch_create", "obca_quad_batch_destroy",
            "obca_quad_batch_upload", "obca_quad_batch_solve", "obca_quad_batch_sync", "obca_quad_batch_kernel_ms",
            "obca_quad_batch_download", "obca_quad_batch_scratch_bytes"]
@@ -331,6 +333,22 @@ class Batch:
         self.ctx._check(rc, "obca_batch_download")
         return _unpack_parking(B, N, self.nObs, self.Ms, xp, up, ts, ef, lp, npp, sl, info)
 
+    def validate(self, tol=5e-5):
+        """A-posteriori check of the last solution ON THE DEVICE (obca_batch_validate; the numpy statement is obca_amd.validate.validate_parking /
+        parking_constraints_ref_worst): dict(ok (B,) bool -- every class except penetration <= tol --, ref_ok (B,) bool -- the reference's own test at 5e-5 --,
+        viol (B, 14) in the order of `names` = VIOL_NAMES).  Only these 16 numbers per instance are downloaded."""
+        B = self.B
+        ok = np.zeros(B, np.int32); rok = np.zeros(B, np.int32); viol = np.zeros((B, len(VIOL_NAMES)))
+        rc = _load().obca_batch_validate(self._h, C.c_double(float(tol)), ok.ctypes.data_as(_I), rok.ctypes.data_as(_I), viol.ctypes.data_as(_D))
+        self.ctx._check(rc, "obca_batch_validate")
+        return dict(ok=ok.astype(bool), ref_ok=rok.astype(bool), viol=viol, names=VIOL_NAMES)
+
+    def validate_ms(self):
+        """HIP-event duration of the last validate kernel"""
+        a = C.c_float(0)
+        self.ctx._check(_load().obca_batch_validate_ms(self._h, C.byref(a)), "obca_batch_validate_ms")
+        return a.value
+
     def close(self):
         if self._h:
             _load().obca_batch_destroy(self._h)
@@ -435,6 +453,48 @@ def ParkingDist(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, rx, ry, ryaw, f
     return r["xp"][0], r["up"][0], ts, int(r["exitflag"][0]), r["time"], r["lp"][0], r["np"][0]
 
 
+def _pack_cols(a, B, rows, N1, what):
+    """per-instance (rows_i, N+1) arrays (a list, or one (B, rows, N+1) array) -> the C ABI's packed stage-contiguous blocks"""
+    out = np.concatenate([np.ascontiguousarray(np.asarray(a[i], float).T).ravel() for i in range(B)])
+    if out.size != int(np.sum(rows)) * N1:
+        raise ObcaError(f"{what} has the wrong size: {out.size} (need {int(np.sum(rows)) * N1})")
+    return out
+
+
+def parking_constraints_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, x, u, timeScale, l, n, sl=None, fixTime=0, dist=False, tol=5e-5, device=0):
+    """Batched ParkingConstraints on the device for arbitrary trajectories (obca_parking_constraints_batch): x (B,4,N+1), u (B,2,N), l / n / sl per instance
+    (M_i,N+1) / (4nOb_i,N+1) / (nOb_i,N+1) -- the shapes the solve calls return --, timeScale scalar, (B,) or (B,N+1) (it may vary over the stages).
+    Obstacles and `device` as in parking_signed_dist_batch.  Returns dict(ok, ref_ok, viol (B,14), names) like Batch.validate; sl=None: zeros."""
+    x0 = np.ascontiguousarray(np.reshape(x0, (-1, 4)), float); B = x0.shape[0]; N = int(N)
+    ctx = _ctx(device)
+    nObs, vflat, Aflat, bflat = _norm_obstacles(B, vOb, A, b)
+    Ms = _row_counts(nObs, vflat)
+    Tsv = np.ascontiguousarray(np.broadcast_to(np.asarray(Ts, float), (B,)))
+    x = np.asarray(x, float); u = np.asarray(u, float)
+    if x.shape != (B, 4, N + 1) or u.shape != (B, 2, N):
+        raise ObcaError(f"x must be (B,4,N+1) and u (B,2,N); got {x.shape}, {u.shape}")
+    ts = np.asarray(timeScale, float)
+    ts = np.broadcast_to(ts.reshape(B, 1) if ts.ndim == 1 and ts.size == B else ts, (B, N + 1))
+    keep = [_d(Tsv), _d(ego), _d(XYbounds), _d(x0), _d(np.reshape(xF, (B, 4))), _i(nObs), _i(vflat), _d(Aflat), _d(bflat),
+            _d(np.transpose(x, (0, 2, 1))), _d(np.transpose(u, (0, 2, 1))), _d(ts), _d(_pack_cols(l, B, Ms, N + 1, "l")), _d(_pack_cols(n, B, 4 * nObs, N + 1, "n")),
+            _d(_pack_cols(sl, B, nObs, N + 1, "sl") if sl is not None else None)]
+    p = [k[1] for k in keep]
+    ok = np.zeros(B, np.int32); rok = np.zeros(B, np.int32); viol = np.zeros((B, len(VIOL_NAMES)))
+    rc = _load().obca_parking_constraints_batch(ctx._h, C.c_int(B), C.c_int(N), p[0], C.c_double(float(L)), p[1], p[2], C.c_int(int(fixTime)), p[3], p[4], p[5], p[6], p[7], p[8],
+                                                C.c_int(int(bool(dist))), p[9], p[10], p[11], p[12], p[13], p[14], C.c_double(float(tol)),
+                                                ok.ctypes.data_as(_I), rok.ctypes.data_as(_I), viol.ctypes.data_as(_D))
+    ctx._check(rc, "obca_parking_constraints_batch")
+    return dict(ok=ok.astype(bool), ref_ok=rok.astype(bool), viol=viol, names=VIOL_NAMES)
+
+
+def ParkingConstraints(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, u, l, n, timeScale, fixTime, sd, device=0):
+    """Drop-in for ParkingConstraints.jl:29 (one instance): 1 if the reference's own acceptance test passes at 5e-5, else 0 (sd = 1: signed-distance formulation)."""
+    assert int(nOb) == len(np.ravel(vOb))
+    r = parking_constraints_batch(np.reshape(x0, (1, 4)), np.reshape(xF, (1, 4)), N, Ts, L, ego, XYbounds, vOb, A, b, np.asarray(x, float)[None], np.asarray(u, float)[None],
+                                  np.reshape(np.broadcast_to(np.ravel(np.asarray(timeScale, float)), (N + 1,)), (1, N + 1)), [l], [n], None, fixTime, dist=not int(sd), device=device)
+    return int(r["ref_ok"][0])
+
+
 def dualmult_ws_batch(N, vOb, A, b, rx, ry, ryaw, ego, device=0):
     """Batched DualMultWS: rx,ry,ryaw (B,N+1) -> lWS list of (N+1,M), nWS list of (N+1,4nOb), d list of (N+1,nOb)."""
     rx = np.atleast_2d(np.asarray(rx, float)); B = rx.shape[0]
@@ -535,6 +595,19 @@ class QuadBatch:
         return dict(xp=T(xp), up=T(up), timeScale=ts, exitflag=ef, lp=T(lp), slack=T(sl), info=info, iters=info[:, 1].astype(int),
                     obj=info[:, 2], status=info[:, 0].astype(int))
 
+    def validate(self, tol=1e-3):
+        """constrSatisfaction on the last solution, on the device (obca_quad_batch_validate): dict(ok (B,) bool, viol (B, 9) in the order of `names` = QUAD_VIOL_NAMES)"""
+        B = self.B
+        ok = np.zeros(B, np.int32); viol = np.zeros((B, len(QUAD_VIOL_NAMES)))
+        rc = _load().obca_quad_batch_validate(self._h, C.c_double(float(tol)), ok.ctypes.data_as(_I), viol.ctypes.data_as(_D))
+        self.ctx._check(rc, "obca_quad_batch_validate")
+        return dict(ok=ok.astype(bool), viol=viol, names=QUAD_VIOL_NAMES)
+
+    def validate_ms(self):
+        a = C.c_float(0)
+        self.ctx._check(_load().obca_quad_batch_validate_ms(self._h, C.byref(a)), "obca_quad_batch_validate_ms")
+        return a.value
+
     def close(self):
         if self._h:
             _load().obca_quad_batch_destroy(self._h)
@@ -574,6 +647,37 @@ def quadcopter_signed_dist_batch(x0, xF, N, Ts, R, ob, xWS, timeWS, dual_ws=True
     T = lambda a: np.transpose(a, (0, 2, 1))
     return dict(xp=T(xp), up=T(up), timeScale=ts, exitflag=ef, lp=T(lp), slack=T(sl), info=info, iters=info[:, 1].astype(int),
                 obj=info[:, 2], status=info[:, 0].astype(int), time=dt)
+
+
+def quadcopter_constr_satisfaction_batch(x, u, timeScale, x0, xF, Ts, lam, ob, R, tol=1e-3, device=0):
+    """Batched constrSatisfaction on the device for arbitrary trajectories (obca_quadcopter_constr_satisfaction_batch): x (B,12,N+1), u (B,4,N), lam (B,30,N+1) -- the
+    shapes quadcopter_signed_dist_batch returns --, timeScale scalar, (B,) or (B,N+1); x0, xF (B,12) or (12,); ob (5,6) shared or (B,5,6).  Returns dict(ok, viol (B,9), names)."""
+    x = np.asarray(x, float); B, _, N1 = x.shape; N = N1 - 1
+    u = np.asarray(u, float); lam = np.asarray(lam, float)
+    if x.shape != (B, 12, N1) or u.shape != (B, 4, N) or lam.shape != (B, 30, N1):
+        raise ObcaError(f"x must be (B,12,N+1), u (B,4,N), lam (B,30,N+1); got {x.shape}, {u.shape}, {lam.shape}")
+    ctx = _ctx(device)
+    Tsv = np.broadcast_to(np.asarray(Ts, float), (B,)).copy()
+    obv = np.broadcast_to(np.asarray(ob, float).reshape(-1, 30) if np.size(ob) != 30 else np.asarray(ob, float).reshape(1, 30), (B, 30)).copy()
+    ts = np.asarray(timeScale, float)
+    ts = np.broadcast_to(ts.reshape(B, 1) if ts.ndim == 1 and ts.size == B else ts, (B, N1))
+    keep = [_d(Tsv), _d(np.broadcast_to(np.reshape(x0, (-1, 12)), (B, 12))), _d(np.broadcast_to(np.reshape(xF, (-1, 12)), (B, 12))), _d(obv),
+            _d(np.transpose(x, (0, 2, 1))), _d(np.transpose(u, (0, 2, 1))), _d(ts), _d(np.transpose(lam, (0, 2, 1)))]
+    p = [k[1] for k in keep]
+    ok = np.zeros(B, np.int32); viol = np.zeros((B, len(QUAD_VIOL_NAMES)))
+    rc = _load().obca_quadcopter_constr_satisfaction_batch(ctx._h, C.c_int(B), C.c_int(N), p[0], C.c_double(float(R)), p[1], p[2], p[3], p[4], p[5], p[6], p[7],
+                                                           C.c_double(float(tol)), ok.ctypes.data_as(_I), viol.ctypes.data_as(_D))
+    ctx._check(rc, "obca_quadcopter_constr_satisfaction_batch")
+    return dict(ok=ok.astype(bool), viol=viol, names=QUAD_VIOL_NAMES)
+
+
+def constrSatisfaction(x, u, timeScale, x0, xF, Ts, lam, ob1, ob2, ob3, ob4, ob5, R, device=0):
+    """Drop-in for constrSatisfaction.jl:25 (one instance): True / False at the reference's tolerance 1e-3."""
+    ob = np.stack([np.ravel(o)[:6] for o in (ob1, ob2, ob3, ob4, ob5)])
+    x = np.asarray(x, float)
+    r = quadcopter_constr_satisfaction_batch(x[None], np.asarray(u, float)[None], np.reshape(np.broadcast_to(np.ravel(np.asarray(timeScale, float)), (x.shape[1],)), (1, -1)),
+                                             x0, xF, Ts, np.asarray(lam, float)[None], ob, R, device=device)
+    return bool(r["ok"][0])
 
 
 _QUAD_STATUS = {0: "Optimal", 1: "UserLimit", 2: "Error"}

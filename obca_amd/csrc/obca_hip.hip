@@ -5,6 +5,7 @@
 //                             interior-point solve (obca_solver.h).  grid = B, block = 64; four instances per CU.
 //   obca_quad_ipm_kernel    : the same for the quadcopter NLP (obca_quad_solver.h).
 //   obca_dualws_kernel      : one lane per (instance, stage, obstacle) convex sub-problem of DualMultWS (obca_model.h).
+//   obca_validate_*_kernel  : one wavefront per instance, the a-posteriori feasibility classes of a solution or of a caller's trajectory (obca_validate.h).
 // Memory (per instance, fp64, all in HBM; sizes for N=80, 3 obstacles / 5 rows in brackets):
 //   prob  header+rx,ry,ryaw   [495]      z, zn  primal-dual iterate and the line search's
 //   trial point (they swap) [6797 each]      d  stage part of the search direction [~650 used]
@@ -21,6 +22,7 @@
 #include <algorithm>
 #include "obca_solver.h"
 #include "obca_quad_solver.h"
+#include "obca_validate.h"
 #include "../../include/obca_hip.h"
 
 using namespace obca;
@@ -254,6 +256,23 @@ __global__ __launch_bounds__(QNT, OBCA_QUAD_WAVES_PER_EU) void obca_quad_ipm_ker
 #endif
 }
 
+// a-posteriori checks (obca_validate.h): one wavefront per instance; the point is read in the solver's layout (resident: the last solution; host-pointer
+// entries: the packed trajectory), `aux` holds per instance [ |a_r| of the MMax rows | timeScale (N + 1) | slack nObMax x (N + 1) ] (the last two for host-pointer calls only)
+__global__ __launch_bounds__(OB_NT) void obca_validate_parking_kernel(int B, int N, const double *prob, size_t s_prob, const double *z, size_t s_z, const double *aux, size_t s_aux,
+                                                                      int MMax, int use_ts, int use_sl, double tol, double *out) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    const double *a = aux + (size_t)inst * s_aux;
+    val::validate_parking_instance(N, prob + (size_t)inst * s_prob, z + (size_t)inst * s_z, a, use_ts ? a + MMax : nullptr, use_sl ? a + MMax + N + 1 : nullptr, tol, out + (size_t)inst * PV_OUT);
+}
+__global__ __launch_bounds__(QNT) void obca_validate_quad_kernel(int B, int N, const double *prob, size_t s_prob, const double *base, size_t s_base, int ox, int ou, int ot, int tstride, int olam,
+                                                                 double tol, double *out) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    const double *v = base + (size_t)inst * s_base;
+    val::validate_quad_instance(N, prob + (size_t)inst * s_prob, v + ox, v + ou, v + ot, tstride, v + olam, tol, out + (size_t)inst * QV_OUT);
+}
+
 // rows of a strided device array <-> a dense staging array (one contiguous PCIe transfer per direction instead of a 2-D copy):
 //   scatter: dst[i * ds + j] = j < W ? src[i * W + j] : 0   for j < zero_to   (upload: primal prefix of the iterate, rest of the row cleared)
 //   gather : dst[i * W + j] = src[i * ss + j]                                   (download: the output prefix of the iterate)
@@ -286,6 +305,8 @@ struct obca_ctx {
 };
 static std::string g_create_err;
 
+// buffers of the validate calls of a batch: device input (row lengths; a host-pointer call's trajectory extras) and output, their pinned mirrors, the events around the kernel
+struct ValBufs { double *d_in, *d_out, *h_in, *h_out; size_t dcap_in, dcap_out, hcap_in, hcap_out; hipEvent_t e0, e1; int have_ev, timed; };
 struct obca_batch {
     obca_ctx *ctx; int device; hipStream_t stream; std::string err;
     int B, cap, N, nObMax, MMax, zlen, have_duals, uploaded, dist, vmax;   // vmax: most rows of one obstacle in the uploaded instances
@@ -298,6 +319,9 @@ struct obca_batch {
     hipEvent_t e0, e1, e2;
     long long bytes;
     int sliced;          // slice length (passes) of the last solve if it used the two-launch schedule, else 0
+    int solved;          // a solve has been queued since the last upload / shift: d.z holds a solution obca_batch_validate may check
+    int val_rl;          // the row lengths of the uploaded instances are in val.d_in (resident validate)
+    ValBufs val;
 };
 
 #define HIPCHK(bt, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (bt)->err = std::string(#call) + ": " + hipGetErrorString(e_); return -2; } } while (0)
@@ -425,7 +449,7 @@ static int batch_create_on(obca_ctx *ctx, int device, hipStream_t stream, int B,
     obca_batch *bt = new obca_batch();
     bt->ctx = ctx; bt->device = device; bt->stream = stream;
     bt->B = B; bt->cap = B; bt->N = N; bt->uploaded = 0; bt->have_duals = 0; bt->nObMax = 0; bt->MMax = 0; bt->bytes = 0; bt->dist = 0; bt->sliced = 0;
-    bt->zlen = 0; bt->fixTime = 0; bt->vmax = 0;
+    bt->zlen = 0; bt->fixTime = 0; bt->vmax = 0; bt->solved = 0; bt->val_rl = 0; memset(&bt->val, 0, sizeof bt->val);
     memset(&bt->d, 0, sizeof bt->d); bt->stage = nullptr; bt->dcap_stage = 0;
     bt->h_prob = bt->h_zin = bt->h_zout = bt->h_info = nullptr; bt->hcap_prob = bt->hcap_zin = bt->hcap_zout = bt->hcap_info = 0;
     use_device(device);
@@ -465,7 +489,7 @@ static int park_prefix(std::string &err, int B, const int *nOb, const int *vOb, 
 static int batch_upload_range(obca_batch *bt, const ParkIn &in, int lo, int n) {
     const int N = bt->N, N1 = N + 1;
     if (n < 1 || n > bt->cap) { bt->err = "obca_batch_upload: more instances than the batch was created for"; return -1; }
-    bt->B = n;
+    bt->B = n; bt->solved = 0; bt->val_rl = 0;
     bt->nOb.assign(n, 0); bt->M.assign(n, 0); bt->obOff.assign(n + 1, 0); bt->rowOff.assign(n + 1, 0);
     int nObMax = 0, MMax = 0; bt->vmax = 0;
     for (int i = 0; i < n; i++) {
@@ -638,6 +662,7 @@ static int batch_solve(obca_batch *bt, const obca_opts *opts, int dualws_only) {
         }
     }
     HIPCHK(bt, hipEventRecord(bt->e2, bt->stream));
+    bt->solved = 1;
     return 0;
 }
 
@@ -680,6 +705,82 @@ static int batch_download_range(obca_batch *bt, const ParkOut &o, int lo) {
         HIPCHK(bt, hipStreamSynchronize(bt->stream));
         for (int i = 0; i < B; i++) for (int k = 0; k < N1; k++) for (int j = 0; j < bt->nOb[i]; j++)
             o.dd[(size_t)bt->obOff[i] * N1 + (size_t)k * bt->nOb[i] + j] = bt->h_zout[(size_t)i * N1 * bt->nObMax + (size_t)k * bt->nObMax + j];
+    }
+    return 0;
+}
+
+// ---- a-posteriori validation (obca_validate.h)
+static void val_release(ValBufs &v) {
+    if (v.d_in) (void)hipFree(v.d_in);
+    if (v.d_out) (void)hipFree(v.d_out);
+    if (v.h_in) (void)hipHostFree(v.h_in);
+    if (v.h_out) (void)hipHostFree(v.h_out);
+    if (v.have_ev) { (void)hipEventDestroy(v.e0); (void)hipEventDestroy(v.e1); }
+    memset(&v, 0, sizeof v);
+}
+static int val_reserve(std::string &err, ValBufs &v, size_t in_doubles, size_t out_doubles, hipStream_t stream) {
+    if (!v.have_ev) {
+        if (hipEventCreate(&v.e0) != hipSuccess) { err = "hipEventCreate failed"; return -2; }
+        if (hipEventCreate(&v.e1) != hipSuccess) { (void)hipEventDestroy(v.e0); err = "hipEventCreate failed"; return -2; }
+        v.have_ev = 1;
+    }
+    if (v.dcap_in < in_doubles) {
+        if (v.d_in) (void)hipFree(v.d_in);
+        v.dcap_in = 0;
+        if (dev_alloc((void **)&v.d_in, in_doubles * sizeof(double), stream) != hipSuccess) { err = "hipMalloc(validate input) failed"; return -2; }
+        v.dcap_in = in_doubles;
+    }
+    if (v.dcap_out < out_doubles) {
+        if (v.d_out) (void)hipFree(v.d_out);
+        v.dcap_out = 0;
+        if (dev_alloc((void **)&v.d_out, out_doubles * sizeof(double), stream) != hipSuccess) { err = "hipMalloc(validate output) failed"; return -2; }
+        v.dcap_out = out_doubles;
+    }
+    if (pinned_reserve(err, &v.h_in, &v.hcap_in, in_doubles) || pinned_reserve(err, &v.h_out, &v.hcap_out, out_doubles)) return -2;
+    return 0;
+}
+static int val_ms(const ValBufs &v, float *ms) {
+    if (!v.timed || hipEventElapsedTime(ms, v.e0, v.e1) != hipSuccess) return -2;
+    return 0;
+}
+
+// Checks the batch's instances: resident (ts == nullptr: the last solution in d.z, only the row lengths travel up) or a caller's trajectory that
+// batch_upload_range has just packed into d.z0 (ts: (N + 1) per instance of the call, sl: the caller's packed slack or nullptr = the zeros of the upload).
+// Instance i of the batch is instance lo + i of the call.  Only PV_OUT doubles per instance come back.  Synchronises the batch's stream.
+static int batch_validate_range(obca_batch *bt, const double *ts, const double *sl, double tol, int lo, int *ok, int *ref_ok, double *viol) {
+    const int B = bt->B, N = bt->N, N1 = N + 1, MMax = bt->MMax;
+    const bool host = ts != nullptr;
+    const size_t s_aux = (size_t)MMax + (host ? (size_t)N1 + (size_t)bt->nObMax * N1 : 0);
+    use_device(bt->device);
+    if (int rc = val_reserve(bt->err, bt->val, std::max<size_t>(1, (size_t)bt->cap * s_aux), (size_t)bt->cap * PV_OUT, bt->stream)) return rc;
+    ValBufs &v = bt->val;
+    if (host || !bt->val_rl) {
+        for (int i = 0; i < B; i++) {
+            double *a = v.h_in + (size_t)i * s_aux;
+            const double *rl = bt->rowLen.data() + (bt->rowOff[i] - bt->rowOff[0]);
+            for (int r = 0; r < MMax; r++) a[r] = r < bt->M[i] ? rl[r] : 1.0;
+            if (host) {
+                memcpy(a + MMax, ts + ((size_t)lo + i) * N1, sizeof(double) * N1);
+                double *as = a + MMax + N1; const size_t ns = (size_t)bt->nOb[i] * N1;
+                if (sl) memcpy(as, sl + (size_t)bt->obOff[i] * N1, sizeof(double) * ns); else memset(as, 0, sizeof(double) * ns);
+            }
+        }
+        HIPCHK(bt, hipMemcpyAsync(v.d_in, v.h_in, (size_t)B * s_aux * sizeof(double), hipMemcpyHostToDevice, bt->stream));
+        bt->val_rl = host ? 0 : 1;
+    }
+    HIPCHK(bt, hipEventRecord(v.e0, bt->stream));
+    hipLaunchKernelGGL(obca_validate_parking_kernel, dim3(B), dim3(OB_NT), 0, bt->stream, B, N, (const double *)bt->d.prob, bt->d.s_prob, (const double *)(host ? bt->d.z0 : bt->d.z), bt->d.s_z,
+                       (const double *)v.d_in, s_aux, MMax, host ? 1 : 0, (host && sl) ? 1 : 0, tol, v.d_out);
+    HIPCHK(bt, hipGetLastError());
+    HIPCHK(bt, hipEventRecord(v.e1, bt->stream));
+    v.timed = 1;
+    HIPCHK(bt, hipMemcpyAsync(v.h_out, v.d_out, (size_t)B * PV_OUT * sizeof(double), hipMemcpyDeviceToHost, bt->stream));
+    HIPCHK(bt, hipStreamSynchronize(bt->stream));
+    for (int i = 0; i < B; i++) {
+        const double *o = v.h_out + (size_t)i * PV_OUT; const size_t g = (size_t)lo + i;
+        if (viol) memcpy(viol + g * PV_NCLS, o, sizeof(double) * PV_NCLS);
+        if (ok) ok[g] = o[PV_NCLS] != 0.0;
+        if (ref_ok) ref_ok[g] = o[PV_NCLS + 1] != 0.0;
     }
     return 0;
 }
@@ -768,7 +869,7 @@ int obca_batch_create(obca_ctx *ctx, int B, int N, obca_batch **out) {
 int obca_batch_destroy(obca_batch *bt) {
     if (!bt) return -1;
     use_device(bt->device);
-    free_dev(bt); (void)hipEventDestroy(bt->e0); (void)hipEventDestroy(bt->e1); (void)hipEventDestroy(bt->e2);
+    free_dev(bt); val_release(bt->val); (void)hipEventDestroy(bt->e0); (void)hipEventDestroy(bt->e1); (void)hipEventDestroy(bt->e2);
     double **hs[] = {&bt->h_prob, &bt->h_zin, &bt->h_zout, &bt->h_info};
     for (auto p : hs) if (*p) (void)hipHostFree(*p);
     delete bt; return 0;
@@ -814,6 +915,7 @@ int obca_batch_shift_warm_start(obca_batch *bt, int shift, const double *x0_new)
     }
     hipLaunchKernelGGL(obca_shift_kernel, dim3(bt->B), dim3(128), 0, bt->stream, bt->B, bt->N, shift, bt->d, (const double *)dx0);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(bt->stream) != hipSuccess) { ctx->err = "obca_batch_shift_warm_start: kernel failed"; return -2; }
+    bt->solved = 0;                                     // d.z still holds the previous solution, but the problem (x0, reference) has moved on
     bt->have_duals = 1;                                 // the shifted multipliers are the dual warm start: DualMultWS is skipped
     return 0;
 }
@@ -841,6 +943,41 @@ int obca_batch_download(obca_batch *bt, double *xp, double *up, double *ts, int 
     if (!bt->uploaded) { bt->ctx->err = "obca_batch_download: nothing uploaded"; return -1; }
     ParkOut o = {xp, up, ts, exitflag, lp, np, slp, info, nullptr, nullptr, nullptr};
     return fin(bt, batch_download_range(bt, o, 0));
+}
+
+int obca_batch_validate(obca_batch *bt, double tol, int *ok, int *ref_ok, double *viol) {
+    if (!bt) return -1;
+    if (!ok) { bt->ctx->err = "obca_batch_validate: NULL argument"; return -1; }
+    if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_batch_validate: nothing has been solved since the last upload or shift"; return -1; }
+    if (bt->N < 1) { bt->ctx->err = "obca_batch_validate: needs a horizon N>=1"; return -1; }
+    return fin(bt, batch_validate_range(bt, nullptr, nullptr, tol > 0 ? tol : PV_REF_TOL, 0, ok, ref_ok, viol));
+}
+int obca_batch_validate_ms(obca_batch *bt, float *ms) {
+    if (!bt || !ms) return -1;
+    if (val_ms(bt->val, ms)) { bt->ctx->err = "obca_batch_validate_ms: no validate call has run on this batch"; return -2; }
+    return 0;
+}
+int obca_parking_constraints_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const double XYb[4], int fixTime,
+                                   const double *x0, const double *xF, const int *nOb, const int *vOb, const double *A, const double *b, int dist,
+                                   const double *x, const double *u, const double *timeScale, const double *l, const double *n, const double *sl,
+                                   double tol, int *ok, int *ref_ok, double *viol) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 1 || N > OBCA_NMAX) { ctx->err = "obca_parking_constraints_batch: need B>=1, 1<=N<=OBCA_NMAX"; return -1; }
+    if (!Ts || !ego || !XYb || !x0 || !xF || !nOb || !vOb || !A || !b || !x || !u || !timeScale || !l || !n || !ok) { ctx->err = "obca_parking_constraints_batch: NULL argument"; return -1; }
+    const std::vector<double> zero((size_t)B * (N + 1), 0.0);      // the tracking reference of a solve: no check reads it
+    ParkIn in = {Ts, L, ego, XYb, fixTime, x0, xF, nOb, vOb, A, b, zero.data(), zero.data(), zero.data(), x, u, l, n, {}, {}};
+    if (int rc = park_prefix(ctx->err, B, nOb, vOb, in)) return rc;
+    const double tl = tol > 0 ? tol : PV_REF_TOL;
+    const int chunk = pick_chunk(ctx, B, 4);
+    return run_chunks(ctx, B, chunk, [&](Slot &s, int lo, int cnt, std::string &err) -> int {
+        int rc = slot_parking_batch(ctx, s, std::min(chunk, B), N, dist, err);
+        if (rc) return rc;
+        obca_batch *bt = s.pb;
+        rc = batch_upload_range(bt, in, lo, cnt);
+        if (!rc) rc = batch_validate_range(bt, timeScale, sl, tl, lo, ok, ref_ok, viol);
+        if (rc) err = bt->err;
+        return rc;
+    });
 }
 
 int obca_parking_signed_dist_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const double XYb[4],
@@ -885,6 +1022,8 @@ struct obca_quad_batch {
     int B, cap, N, uploaded;
     QDevBufs d; double *stage; hipEvent_t e0, e1; long long bytes;
     double *h_prob, *h_z, *h_info; size_t hcap_prob, hcap_z, hcap_info;       // pinned host staging
+    int solved;          // a solve has been queued since the last upload
+    ValBufs val;
 };
 #define QCHK(bt, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (bt)->err = std::string(#call) + ": " + hipGetErrorString(e_); return -2; } } while (0)
 static inline int qfin(obca_quad_batch *bt, int rc) { if (rc) bt->ctx->err = bt->err; return rc; }
@@ -899,6 +1038,7 @@ static int quad_batch_create_on(obca_ctx *ctx, int device, hipStream_t stream, i
     bt->ctx = ctx; bt->device = device; bt->stream = stream; bt->B = B; bt->cap = B; bt->N = N; bt->uploaded = 0; bt->bytes = 0;
     memset(&bt->d, 0, sizeof bt->d); bt->stage = nullptr;
     bt->h_prob = bt->h_z = bt->h_info = nullptr; bt->hcap_prob = bt->hcap_z = bt->hcap_info = 0;
+    bt->solved = 0; memset(&bt->val, 0, sizeof bt->val);
     use_device(device);
     quad::QLay l; quad::q_make_layout(N, l);
     QDevBufs &d = bt->d; const size_t N1 = N + 1;
@@ -918,7 +1058,7 @@ struct QuadIn { const double *Ts; double R; const double *x0, *xF, *ob, *xWS, *t
 struct QuadOut { double *xp, *up, *ts; int *exitflag; double *lp, *slp, *info; };
 static int quad_upload_range(obca_quad_batch *bt, const QuadIn &in, int lo, int n) {
     if (n < 1 || n > bt->cap) { bt->err = "obca_quad_batch_upload: more instances than the batch was created for"; return -1; }
-    bt->B = n;
+    bt->B = n; bt->solved = 0;
     const int N1 = bt->N + 1; const QDevBufs &d = bt->d;
     if (pinned_reserve(bt->err, &bt->h_prob, &bt->hcap_prob, (size_t)bt->cap * d.s_prob)) return -2;
     for (int i = 0; i < n; i++) {
@@ -981,7 +1121,7 @@ int obca_quad_batch_create(obca_ctx *ctx, int B, int N, obca_quad_batch **out) {
 }
 int obca_quad_batch_destroy(obca_quad_batch *bt) {
     if (!bt) return -1;
-    use_device(bt->device); qfree_dev(bt); (void)hipEventDestroy(bt->e0); (void)hipEventDestroy(bt->e1);
+    use_device(bt->device); qfree_dev(bt); val_release(bt->val); (void)hipEventDestroy(bt->e0); (void)hipEventDestroy(bt->e1);
     double **hs[] = {&bt->h_prob, &bt->h_z, &bt->h_info};
     for (auto p : hs) if (*p) (void)hipHostFree(*p);
     delete bt; return 0;
@@ -1019,6 +1159,40 @@ static int quad_solve(obca_quad_batch *bt, const obca_opts *opts) {
     hipLaunchKernelGGL(obca_quad_ipm_kernel, dim3(bt->B), dim3(QNT), (size_t)(bt->N + 2) * (QS + QU) * sizeof(double), bt->stream, bt->B, bt->N, bt->d, ko, o.max_soc, o.lsq_init != 0, o.obj_scaling != 0);
     QCHK(bt, hipGetLastError());
     QCHK(bt, hipEventRecord(bt->e1, bt->stream));
+    bt->solved = 1;
+    return 0;
+}
+// the quadcopter check of the batch's instances: resident (x == nullptr: the last solution in d.z) or a caller's trajectory (host arrays of the whole call, instance lo + i),
+// which travels up densely packed as [ x | u | timeScale (N + 1) | lambda ] per instance.  Only QV_OUT doubles per instance come back.  Synchronises the batch's stream.
+static int quad_validate_range(obca_quad_batch *bt, const double *x, const double *u, const double *ts, const double *lam, double tol, int lo, int *ok, double *viol) {
+    const int B = bt->B, N = bt->N, N1 = N + 1; const QDevBufs &d = bt->d;
+    const bool host = x != nullptr;
+    const size_t nx = (size_t)QX * N1, nu = (size_t)QU * N, nl = (size_t)QL * QOB * N1, W = nx + nu + N1 + nl;
+    use_device(bt->device);
+    if (int rc = val_reserve(bt->err, bt->val, host ? (size_t)bt->cap * W : 1, (size_t)bt->cap * QV_OUT, bt->stream)) return rc;
+    ValBufs &v = bt->val;
+    if (host) {
+        for (int i = 0; i < B; i++) {
+            double *a = v.h_in + (size_t)i * W; const size_t g = (size_t)lo + i;
+            memcpy(a, x + g * nx, sizeof(double) * nx); memcpy(a + nx, u + g * nu, sizeof(double) * nu);
+            memcpy(a + nx + nu, ts + g * N1, sizeof(double) * N1); memcpy(a + nx + nu + N1, lam + g * nl, sizeof(double) * nl);
+        }
+        QCHK(bt, hipMemcpyAsync(v.d_in, v.h_in, (size_t)B * W * sizeof(double), hipMemcpyHostToDevice, bt->stream));
+    }
+    quad::QLay l; quad::q_make_layout(N, l);
+    QCHK(bt, hipEventRecord(v.e0, bt->stream));
+    if (host) hipLaunchKernelGGL(obca_validate_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)v.d_in, W, 0, (int)nx, (int)(nx + nu), 1, (int)(nx + nu + N1), tol, v.d_out);
+    else hipLaunchKernelGGL(obca_validate_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)d.z, d.s_z, l.x, l.u, l.t, 0, l.lam, tol, v.d_out);
+    QCHK(bt, hipGetLastError());
+    QCHK(bt, hipEventRecord(v.e1, bt->stream));
+    v.timed = 1;
+    QCHK(bt, hipMemcpyAsync(v.h_out, v.d_out, (size_t)B * QV_OUT * sizeof(double), hipMemcpyDeviceToHost, bt->stream));
+    QCHK(bt, hipStreamSynchronize(bt->stream));
+    for (int i = 0; i < B; i++) {
+        const double *o = v.h_out + (size_t)i * QV_OUT; const size_t g = (size_t)lo + i;
+        if (viol) memcpy(viol + g * QV_NCLS, o, sizeof(double) * QV_NCLS);
+        if (ok) ok[g] = o[QV_NCLS] != 0.0;
+    }
     return 0;
 }
 static int quadcopter_call(obca_ctx *ctx, int B, int N, const QuadIn &in, const obca_opts *opts, const QuadOut &out) {
@@ -1049,6 +1223,36 @@ int obca_quad_batch_kernel_ms(obca_quad_batch *bt, float *ipm_ms) {
     if (!bt || !ipm_ms) return -1;
     if (hipEventElapsedTime(ipm_ms, bt->e0, bt->e1) != hipSuccess) { bt->ctx->err = "obca_quad_batch_kernel_ms: events not ready"; return -2; }
     return 0;
+}
+int obca_quad_batch_validate(obca_quad_batch *bt, double tol, int *ok, double *viol) {
+    if (!bt) return -1;
+    if (!ok) { bt->ctx->err = "obca_quad_batch_validate: NULL argument"; return -1; }
+    if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_quad_batch_validate: nothing has been solved since the last upload"; return -1; }
+    return qfin(bt, quad_validate_range(bt, nullptr, nullptr, nullptr, nullptr, tol > 0 ? tol : 1e-3, 0, ok, viol));
+}
+int obca_quad_batch_validate_ms(obca_quad_batch *bt, float *ms) {
+    if (!bt || !ms) return -1;
+    if (val_ms(bt->val, ms)) { bt->ctx->err = "obca_quad_batch_validate_ms: no validate call has run on this batch"; return -2; }
+    return 0;
+}
+int obca_quadcopter_constr_satisfaction_batch(obca_ctx *ctx, int B, int N, const double *Ts, double R, const double *x0, const double *xF, const double *ob,
+                                              const double *x, const double *u, const double *timeScale, const double *lambda, double tol, int *ok, double *viol) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 2 || N > OBCA_QUAD_NMAX) { ctx->err = "obca_quadcopter_constr_satisfaction_batch: need B>=1, 2<=N<=OBCA_QUAD_NMAX"; return -1; }
+    if (!Ts || !x0 || !xF || !ob || !x || !u || !timeScale || !lambda || !ok) { ctx->err = "obca_quadcopter_constr_satisfaction_batch: NULL argument"; return -1; }
+    const std::vector<double> one((size_t)B, 1.0);                 // timeWS of a solve: no check reads it
+    const QuadIn in = {Ts, R, x0, xF, ob, x, one.data(), 0, 0};
+    const double tl = tol > 0 ? tol : 1e-3;
+    const int chunk = pick_chunk(ctx, B, (QNT == 64 ? 4 : 2) * OBCA_QUAD_WAVES_PER_EU);
+    return run_chunks(ctx, B, chunk, [&](Slot &s, int lo, int cnt, std::string &err) -> int {
+        if (s.qb && (s.qb->cap < cnt || s.qb->N != N)) { obca_quad_batch_destroy(s.qb); s.qb = nullptr; }
+        if (!s.qb) { int rc = quad_batch_create_on(ctx, s.device, s.stream, std::min(chunk, B), N, &s.qb, err); if (rc) return rc; }
+        obca_quad_batch *bt = s.qb;
+        int rc = quad_upload_range(bt, in, lo, cnt);
+        if (!rc) rc = quad_validate_range(bt, x, u, timeScale, lambda, tl, lo, ok, viol);
+        if (rc) err = bt->err;
+        return rc;
+    });
 }
 int obca_quad_batch_download(obca_quad_batch *bt, double *xp, double *up, double *ts, int *exitflag, double *lp, double *slp, double *info) {
     if (!bt) return -1;

@@ -7,6 +7,7 @@ parking_constraints_ref : restatement of /root/reference/AutonomousParking/Parki
     row, survives, :76-79); c6 is overwritten per obstacle so only the LAST obstacle is checked (:108-130); the c6[3] row
     ignores the slack (:127-128); the steering-rate check divides by timeScale[0] only (:88).  It is the reference's own
     acceptance test (tolerance 5e-5, :133-139) and decides exitflag after failed attempts (ParkingSignedDist.jl:278-283, ParkingDist.jl).
+parking_constraints_ref_worst : the maximum that parking_constraints_ref thresholds (the device-side check reports it as `ref_worst`).
 parking_constraints_full : a correct checker of every constraint class of ParkingSignedDist.jl:100-207 (with the slack),
     returning the individual maxima.
 validate_parking : (ok, violations) of one returned parking solution; validate_quadcopter: restatement of
@@ -31,7 +32,8 @@ def _dyn(x, u, ts, Ts, L):
     return np.array([x[0] + q * s * np.cos(phi), x[1] + q * s * np.sin(phi), x[2] + q * s * np.tan(u[0]) / L, x[3] + q * u[1]])
 
 
-def parking_constraints_ref(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, u, l, n, timeScale, fixTime, sd):
+def _parking_ref_classes(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, u, l, n, timeScale, fixTime, sd):
+    """the seven quantities ParkingConstraints.jl:133-139 compares with 5e-5"""
     x0 = np.ravel(x0); xF = np.ravel(xF); vOb = [int(v) for v in np.ravel(vOb)]
     A = np.asarray(A, float).reshape(-1, 2); b = np.ravel(b)
     timeScale = np.ravel(timeScale)
@@ -72,9 +74,21 @@ def parking_constraints_ref(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, 
             c6[1, i] = abs(nj[0] - nj[2] + cs * p[0] + sn * p[1])
             c6[2, i] = abs(nj[1] - nj[3] - sn * p[0] + cs * p[1])
             c6[3, i] = -(-g @ nj + (x[0, i] + cs * off) * p[0] + (x[1, i] + sn * off) * p[1] - bj @ lj) + DMIN
-    e = [np.max(c0) <= 5e-5, np.max(c1) <= 5e-5, np.max(c2) <= 5e-5, np.max(np.abs(c3)) <= 5e-5, c4 <= 5e-5, c5 <= 5e-5,
-         np.max(c6) <= 5e-5]
+    return [np.max(c0), np.max(c1), np.max(c2), np.max(np.abs(c3)), c4, c5, np.max(c6)]
+
+
+def parking_constraints_ref(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, u, l, n, timeScale, fixTime, sd):
+    e = [c <= 5e-5 for c in _parking_ref_classes(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, u, l, n, timeScale, fixTime, sd)]
     return 1 if sum(e) == 7 else 0
+
+
+def parking_constraints_ref_worst(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, u, l, n, timeScale, fixTime, sd):
+    """the largest of the quantities parking_constraints_ref compares with 5e-5 (NaN if any of them is): what the device-side check reports as `ref_worst`"""
+    return float(np.max(np.array(_parking_ref_classes(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, u, l, n, timeScale, fixTime, sd), float)))
+
+
+VIOL_NAMES = ("u_bounds", "x_bounds", "ts_bounds", "ts_chain", "dual_pos", "start", "end", "dyn", "steer_rate", "norm", "rot", "sep", "penetration", "ref_worst")
+QUAD_VIOL_NAMES = ("start", "end", "u_bounds", "x_bounds", "dyn", "ts_chain", "dual_pos", "norm", "sep")
 
 
 def parking_constraints_full(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, u, l, n, timeScale, fixTime, sl=None):
