@@ -330,3 +330,105 @@ def quad_warm_start(x0, xF, N, boxes=None, clear=0.4, res=0.25):
     if wp is None:
         return None
     return S.quad_warm_start(x0, xF, N, via=[tuple(p) for p in wp[1:-1]])
+
+
+# ---------------------------------------------------------------- the same search on the GPU, a batch per call (include/obca_plan3d.h, obca_amd/csrc/obca_plan3d.h)
+_SRC3D = [os.path.join(_HERE, "csrc", f) for f in ("obca_plan3d.hip", "obca_plan3d.h")] + [os.path.join(_HERE, "..", "include", "obca_plan3d.h")]
+_LIB3D = os.path.join(_HERE, "csrc", "libobca_plan3d.so")
+_lib3d = None
+_ctx3d = {}
+PLAN3D_EXPORTS = ["obca_plan3d_create", "obca_plan3d_destroy", "obca_plan3d_last_error", "obca_plan3d_paths_batch", "obca_plan3d_warm_start_batch", "obca_plan3d_kernel_ms"]
+PLAN3D_MAXCELLS, PLAN3D_MAXBOX, PLAN3D_NMAX, PLAN3D_WS_CAP = 40000, 8, 128, 1024      # the limits of include/obca_plan3d.h
+
+
+class Plan3DError(RuntimeError):
+    pass
+
+
+def build_plan3d_library(force=False):
+    """compile the device planner for gfx950 in-tree (hipcc cross-compiles without a GPU)"""
+    if force or not os.path.exists(_LIB3D) or os.path.getmtime(_LIB3D) < max(os.path.getmtime(s) for s in _SRC3D):
+        from .buildflags import HIPCC
+        subprocess.check_call(HIPCC + ["-o", _LIB3D, _SRC3D[0]])
+    return _LIB3D
+
+
+def _load3d():
+    global _lib3d
+    if _lib3d is None:
+        if not os.path.exists(_LIB3D):
+            raise Plan3DError(f"{_LIB3D} is missing: build it with obca_amd.planner.build_plan3d_library() / __graft_entry__.build(); there is no CPU fallback")
+        lib = C.CDLL(_LIB3D)
+        lib.obca_plan3d_last_error.restype = C.c_char_p; lib.obca_plan3d_last_error.argtypes = [C.c_void_p]
+        lib.obca_plan3d_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]; lib.obca_plan3d_destroy.argtypes = [C.c_void_p]
+        lib.obca_plan3d_paths_batch.argtypes = [C.c_void_p, C.c_int, _D, _D, C.c_int, _D, C.c_double, _D, C.c_double, _D, C.c_int, _I, _I]
+        lib.obca_plan3d_warm_start_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, _D, _D, C.c_int, _D, C.c_double, _D, C.c_double, _D, _I]
+        lib.obca_plan3d_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        _lib3d = lib
+    return _lib3d
+
+
+def plan3d_context(device=0):
+    """the planner context of a device (created once per process and device; no device, no context: there is no CPU fallback of the device call)"""
+    device = int(device)
+    if device not in _ctx3d:
+        h = C.c_void_p()
+        if _load3d().obca_plan3d_create(device, C.byref(h)) != 0:
+            raise Plan3DError(_load3d().obca_plan3d_last_error(None).decode())
+        _ctx3d[device] = h
+    return _ctx3d[device]
+
+
+def _boxes3d(boxes, B):
+    """one shared box set (nBox, 6) or one per instance (B, nBox, 6) -> (B, nBox, 6)"""
+    bx = np.asarray(S.QUAD_OB if boxes is None else boxes, float)
+    bx = bx.reshape(-1, 6) if bx.ndim < 3 else bx
+    return np.ascontiguousarray(np.broadcast_to(bx, (B,) + bx.shape[-2:]))
+
+
+def _dp(a):
+    return a.ctypes.data_as(_D)
+
+
+def plan3d_paths(starts, goals, boxes=None, clear=0.4, room=QUAD_ROOM, res=0.25, device=0, cap=256):
+    """the C call as it is: (paths (B, cap, 3), counts (B,), sweeps (B,), kernel ms).  counts as obca_plan_astar3d returns them per instance; -1: more than cap way-points."""
+    s = np.ascontiguousarray(np.asarray(starts, float).reshape(-1, np.shape(starts)[-1])[:, :3]); g = np.ascontiguousarray(np.asarray(goals, float).reshape(-1, np.shape(goals)[-1])[:, :3]); B = len(s)
+    bx = _boxes3d(boxes, B); rm = np.ascontiguousarray(room, float)
+    paths = np.zeros((B, max(int(cap), 0), 3)); cnt = np.zeros(B, np.int32); sw = np.zeros(B, np.int32); ms = C.c_float(0)
+    h = plan3d_context(device); lib = _load3d()
+    if lib.obca_plan3d_paths_batch(h, B, _dp(s), _dp(g), bx.shape[1], _dp(bx), float(clear), _dp(rm), float(res), _dp(paths), int(cap), cnt.ctypes.data_as(_I), sw.ctypes.data_as(_I)) != 0:
+        raise Plan3DError(lib.obca_plan3d_last_error(h).decode())
+    lib.obca_plan3d_kernel_ms(h, C.byref(ms))
+    return paths, cnt, sw, ms.value
+
+
+def astar3d_many(starts, goals, boxes=None, clear=0.4, room=QUAD_ROOM, res=0.25, device=0):
+    """B grid searches in one call on the GPU (one workgroup each): a list of way-point arrays (K, 3) -- start point, grid nodes, goal point -- or None (no path, or the
+    start / goal point is blocked), what `astar3d` answers per instance.  The cost of a path is that of the host search's; among paths of equal cost it may be another.
+    boxes: (nBox, 6) shared or (B, nBox, 6)."""
+    paths, cnt, _, _ = plan3d_paths(starts, goals, boxes, clear, room, res, device)
+    long_ = np.flatnonzero(cnt == -1)
+    out = [paths[i, :cnt[i]].copy() if cnt[i] >= 2 else None for i in range(len(cnt))]
+    if len(long_):      # longer than the first call's 256 way-points: those again with room for a path through every node
+        s = np.asarray(starts, float).reshape(len(cnt), -1)[long_]; g = np.asarray(goals, float).reshape(len(cnt), -1)[long_]
+        p2, c2, _, _ = plan3d_paths(s, g, _boxes3d(boxes, len(cnt))[long_], clear, room, res, device, cap=PLAN3D_MAXCELLS + 2)
+        for j, i in enumerate(long_):
+            out[i] = p2[j, :c2[j]].copy() if c2[j] >= 2 else None
+    if np.any(cnt == -3):
+        raise Plan3DError("the relaxation of instances %s did not settle" % np.flatnonzero(cnt == -3).tolist())
+    return out
+
+
+def quad_warm_start_many(x0, xF, N, boxes=None, clear=0.4, room=QUAD_ROOM, res=0.25, device=0, with_ms=False):
+    """warm starts of B quadcopter instances planned and resampled on the GPU: (xWS (B, N+1, 12), ok (B,) bool); what `quad_warm_start` gives per instance (rows of an instance
+    without a path are zero, ok False).  with_ms=True: the kernel's milliseconds as a third value."""
+    a = np.ascontiguousarray(np.asarray(x0, float).reshape(-1, 12)); b = np.ascontiguousarray(np.asarray(xF, float).reshape(-1, 12)); B = len(a)
+    bx = _boxes3d(boxes, B); rm = np.ascontiguousarray(room, float)
+    xWS = np.zeros((B, int(N) + 1, 12)); cnt = np.zeros(B, np.int32); ms = C.c_float(0)
+    h = plan3d_context(device); lib = _load3d()
+    if lib.obca_plan3d_warm_start_batch(h, B, int(N), _dp(a), _dp(b), bx.shape[1], _dp(bx), float(clear), _dp(rm), float(res), _dp(xWS), cnt.ctypes.data_as(_I)) != 0:
+        raise Plan3DError(lib.obca_plan3d_last_error(h).decode())
+    if np.any((cnt == -1) | (cnt == -3)):
+        raise Plan3DError("instances %s: path longer than %d way-points, or the relaxation did not settle" % (np.flatnonzero((cnt == -1) | (cnt == -3)).tolist(), PLAN3D_WS_CAP))
+    lib.obca_plan3d_kernel_ms(h, C.byref(ms))
+    return (xWS, cnt >= 2, ms.value) if with_ms else (xWS, cnt >= 2)

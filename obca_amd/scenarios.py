@@ -292,10 +292,28 @@ def _draw_quad_endpoints(rng):
     return [rng.uniform(0.5, 1.6), rng.uniform(0.5, 9.5), rng.uniform(0.5, 4.5)], [rng.uniform(8.0, 9.5), rng.uniform(0.5, 9.5), rng.uniform(0.5, 4.5)]
 
 
-def plan_quad_batch(x0, xF, N, rng, first_is_fixed=True):
-    """3-D grid A* warm starts (obca_amd/planner.py, the reference's a_star_3D.jl step) for given end points; an instance without a path gets new end points from `rng`
-    (x0 / xF updated in place).  Returns xWS (B,N+1,12)."""
+def _plan_quad_on_device(x0, xF, N, rng, device, fixed):
+    """the planning of plan_quad_batch / make_quad_batch as batch calls of the device planner (planner.quad_warm_start_many): every instance without a path is re-drawn, in
+    index order, and the re-drawn ones are planned again; `fixed` instances must have a path"""
     from . import planner as PL
+    B = len(x0); xWS = np.zeros((B, N + 1, 12)); todo = np.arange(B)
+    while len(todo):
+        w, ok = PL.quad_warm_start_many(x0[todo], xF[todo], N, device=device)
+        xWS[todo[ok]] = w[ok]; todo = todo[~ok]
+        if len(todo) and todo[0] < fixed:
+            raise RuntimeError("no path for the shipped quadcopter scenario")
+        for i in todo:
+            x0[i, :3], xF[i, :3] = _draw_quad_endpoints(rng)
+    return xWS
+
+
+def plan_quad_batch(x0, xF, N, rng, first_is_fixed=True, device=None):
+    """3-D grid A* warm starts (obca_amd/planner.py, the reference's a_star_3D.jl step) for given end points; an instance without a path gets new end points from `rng`
+    (x0 / xF updated in place).  Returns xWS (B,N+1,12).  device=None: the host search, one instance after the other; a device index: the batch planner on that GPU
+    (paths of the same cost, not always the same paths)."""
+    from . import planner as PL
+    if device is not None:
+        return _plan_quad_on_device(x0, xF, N, rng, device, 1 if first_is_fixed else 0)
     B = len(x0); xWS = np.zeros((B, N + 1, 12))
     for i in range(B):
         while True:
@@ -308,16 +326,21 @@ def plan_quad_batch(x0, xF, N, rng, first_is_fixed=True):
     return xWS
 
 
-def make_quad_batch(B, N=60, seed=20260925, jitter=0.3, random_endpoints=False):
+def make_quad_batch(B, N=60, seed=20260925, jitter=0.3, random_endpoints=False, device=None):
     """B instances of the quadcopter scenario.  Default: the shipped start / goal jittered uniformly by +-jitter (instance 0 exact) with the
     way-point warm start.  random_endpoints=True: start anywhere in front of the first wall, goal anywhere behind the second, warm start from
-    the 3-D grid A* of obca_amd/planner.py (the reference's a_star_3D.jl step); instance 0 stays the shipped one."""
+    the 3-D grid A* of obca_amd/planner.py (the reference's a_star_3D.jl step); instance 0 stays the shipped one.  device (with random_endpoints): plan on that GPU
+    instead of the host loop (planner.quad_warm_start_many)."""
     rng = np.random.default_rng(seed)
     x0 = np.tile(QUAD_X0, (B, 1)); xF = np.tile(QUAD_XF, (B, 1))
     if not random_endpoints:
         if B > 1:
             x0[1:, :3] += rng.uniform(-jitter, jitter, (B - 1, 3)); xF[1:, :3] += rng.uniform(-jitter, jitter, (B - 1, 3))
         xWS = np.stack([quad_warm_start(x0[i], xF[i], N) for i in range(B)])
+    elif device is not None:
+        for i in range(1, B):
+            x0[i, :3], xF[i, :3] = _draw_quad_endpoints(rng)
+        xWS = _plan_quad_on_device(x0, xF, N, rng, device, 1)
     else:
         from . import planner as PL
         xWS = np.zeros((B, N + 1, 12))
