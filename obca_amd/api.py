@@ -15,6 +15,7 @@ ctypes binding of libobca_hip.so and the Python mirror of the reference's entry 
 plus batched variants (leading batch dimension) that keep everything resident on the GPU between upload and download.
 """
 import ctypes as C
+import glob
 import numbers
 import os
 import subprocess
@@ -48,8 +49,8 @@ def library_path():
 
 def build_library(force=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("obca_hip.hip", "obca_solver.h", "obca_solver_lanes.h", "obca_solver_assemble.h", "obca_solver_riccati.h", "obca_solver_direction.h", "obca_solver_ipm.h", "obca_model.h", "obca_quad_solver.h", "obca_quad_model.h", "obca_validate.h")] + \
-           [os.path.join(_HERE, "..", "include", "obca_hip.h"), os.path.join(_HERE, "buildflags.py")]      # (that file holds the compile flags)
+    srcs = glob.glob(os.path.join(_CSRC, "*.h")) + \
+           [os.path.join(_CSRC, "obca_hip.hip"), os.path.join(_HERE, "..", "include", "obca_hip.h"), os.path.join(_HERE, "buildflags.py")]      # (that file holds the compile flags)
     if not force and os.path.exists(_LIBPATH) and all(os.path.getmtime(_LIBPATH) >= os.path.getmtime(s) for s in srcs):
         return _LIBPATH
     from .buildflags import HIPCC      # the flags (warnings are errors) and why: obca_amd/buildflags.py
@@ -256,18 +257,66 @@ def _row_counts(nObs, vflat):
     return csum[ends] - csum[ends - nObs]
 
 
-class Batch:
-    """Device-resident batch: upload once, solve (repeatedly), download."""
+class _DeviceBatch:
+    """What Batch and QuadBatch share: the handle and the calls of the C ABI that differ only in their prefix (`_c`: obca_batch / obca_quad_batch)."""
 
     def __init__(self, ctx, B, N):
         self.ctx, self.B, self.N = ctx, int(B), int(N)
         self._h = C.c_void_p()
-        ctx._check(_load().obca_batch_create(ctx._h, C.c_int(self.B), C.c_int(self.N), C.byref(self._h)), "obca_batch_create")
+        self._call("create", ctx._h, C.c_int(self.B), C.c_int(self.N), C.byref(self._h), handle=False)
+
+    def _call(self, name, *args, handle=True):
+        """obca_[quad_]batch_<name>(handle, *args); a non-zero status raises ObcaError with the library's message"""
+        fn = f"{self._c}_{name}"
+        self.ctx._check(getattr(_load(), fn)(*((self._h,) if handle else ()), *args), fn)
+
+    def solve(self, opts=None, sync=True):
+        self._call("solve", C.byref(opts) if opts is not None else None)
+        if sync:
+            self.sync()
+
+    def sync(self):
+        self._call("sync")
+
+    def phase_cycles(self):
+        """(B,16) per-phase shader-cycle counters of the last solve: exists in the profiling build only (OBCA_HIP_LIBRARY=.../libobca_hip_prof.so, tools/phase_profile.py)."""
+        out = np.zeros((self.B, 16))
+        if not hasattr(_load(), f"{self._c}_debug_phase_cycles"):
+            raise ObcaError("phase_cycles(): the loaded library is not the -DOBCA_PROFILE build")
+        self._call("debug_phase_cycles", out.ctypes.data_as(_D))
+        return out
+
+    def scratch_bytes(self):
+        v = C.c_longlong(0)
+        getattr(_load(), f"{self._c}_scratch_bytes")(self._h, C.byref(v))
+        return v.value
+
+    def validate_ms(self):
+        """HIP-event duration of the last validate kernel"""
+        a = C.c_float(0)
+        self._call("validate_ms", C.byref(a))
+        return a.value
+
+    def close(self):
+        if self._h:
+            getattr(_load(), f"{self._c}_destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Batch(_DeviceBatch):
+    """Device-resident batch: upload once, solve (repeatedly), download."""
+    _c = "obca_batch"
 
     def upload(self, x0, xF, Ts, L, ego, XYbounds, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, lWS=None, nWS=None, dist=False):
-        self.ctx._check(_load().obca_batch_set_formulation(self._h, C.c_int(int(bool(dist)))), "obca_batch_set_formulation")
         """lWS/nWS, when given, are packed per instance as (N+1, M_i) / (N+1, 4 nOb_i) row-major blocks (= the reference's
         column-major l (M x N+1) and n (4nOb x N+1))."""
+        self._call("set_formulation", C.c_int(int(bool(dist))))
         B, N = self.B, self.N
         nObs, vflat, Aflat, bflat = _norm_obstacles(B, vOb, A, b)
         self.nObs, self.vflat = nObs, vflat
@@ -279,58 +328,32 @@ class Batch:
                 *(_d(w) for w in _warm_start(xWS, uWS, B, N)),
                 _d(lWS), _d(nWS)]
         p = [k[1] for k in keep]
-        rc = _load().obca_batch_upload(self._h, p[0], C.c_double(float(L)), p[1], p[2], C.c_int(int(fixTime)), p[3], p[4], p[5], p[6],
-                                       p[7], p[8], p[9], p[10], p[11], p[12], p[13], p[14], p[15])
-        self.ctx._check(rc, "obca_batch_upload")
-
-    def solve(self, opts=None, sync=True):
-        self.ctx._check(_load().obca_batch_solve(self._h, C.byref(opts) if opts is not None else None), "obca_batch_solve")
-        if sync:
-            self.sync()
-
-    def sync(self):
-        self.ctx._check(_load().obca_batch_sync(self._h), "obca_batch_sync")
+        self._call("upload", p[0], C.c_double(float(L)), p[1], p[2], C.c_int(int(fixTime)), p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], p[11], p[12], p[13], p[14], p[15])
 
     def shift_warm_start(self, shift, x0_new=None):
         """receding-horizon restart: the next solve starts from the last solution advanced by `shift` stages (kept on the device)."""
         keep = _d(np.reshape(x0_new, (self.B, 4))) if x0_new is not None else None
-        rc = _load().obca_batch_shift_warm_start(self._h, C.c_int(int(shift)), keep[1] if keep else None)
-        self.ctx._check(rc, "obca_batch_shift_warm_start")
+        self._call("shift_warm_start", C.c_int(int(shift)), keep[1] if keep else None)
 
     def kernel_ms(self):
         """(ipm_ms, dualws_ms) of the last solve, measured with HIP events on the launch stream."""
         a, b = C.c_float(0), C.c_float(0)
-        self.ctx._check(_load().obca_batch_kernel_ms(self._h, C.byref(a), C.byref(b)), "obca_batch_kernel_ms")
+        self._call("kernel_ms", C.byref(a), C.byref(b))
         return a.value, b.value
 
     def last_schedule(self):
         """(ipm launches, slice passes) of the last solve: (1, 0) single launch, (2, q) the two-launch schedule with a q-pass first slice"""
         a, b = C.c_int(0), C.c_int(0)
-        self.ctx._check(_load().obca_batch_last_schedule(self._h, C.byref(a), C.byref(b)), "obca_batch_last_schedule")
+        self._call("last_schedule", C.byref(a), C.byref(b))
         return a.value, b.value
-
-    def phase_cycles(self):
-        """(B,16) per-phase shader-cycle counters of the last solve: exists in the profiling build only (OBCA_HIP_LIBRARY=.../libobca_hip_prof.so, tools/phase_profile.py)."""
-        out = np.zeros((self.B, 16))
-        if not hasattr(_load(), "obca_batch_debug_phase_cycles"):
-            raise ObcaError("phase_cycles(): the loaded library is not the -DOBCA_PROFILE build")
-        self.ctx._check(_load().obca_batch_debug_phase_cycles(self._h, out.ctypes.data_as(_D)), "obca_batch_debug_phase_cycles")
-        return out
-
-    def scratch_bytes(self):
-        v = C.c_longlong(0)
-        _load().obca_batch_scratch_bytes(self._h, C.byref(v))
-        return v.value
 
     def download(self):
         B, N = self.B, self.N
         Mt, nt = int(self.Ms.sum()), int(self.nObs.sum())
         xp = np.zeros((B, N + 1, 4)); up = np.zeros((B, N, 2)); ts = np.zeros((B, N + 1)); ef = np.zeros(B, np.int32)
         lp = np.zeros(Mt * (N + 1)); npp = np.zeros(4 * nt * (N + 1)); sl = np.zeros(nt * (N + 1)); info = np.zeros((B, 8))
-        rc = _load().obca_batch_download(self._h, xp.ctypes.data_as(_D), up.ctypes.data_as(_D), ts.ctypes.data_as(_D),
-                                         ef.ctypes.data_as(_I), lp.ctypes.data_as(_D), npp.ctypes.data_as(_D), sl.ctypes.data_as(_D),
-                                         info.ctypes.data_as(_D))
-        self.ctx._check(rc, "obca_batch_download")
+        self._call("download", xp.ctypes.data_as(_D), up.ctypes.data_as(_D), ts.ctypes.data_as(_D), ef.ctypes.data_as(_I), lp.ctypes.data_as(_D), npp.ctypes.data_as(_D),
+                   sl.ctypes.data_as(_D), info.ctypes.data_as(_D))
         return _unpack_parking(B, N, self.nObs, self.Ms, xp, up, ts, ef, lp, npp, sl, info)
 
     def validate(self, tol=5e-5):
@@ -339,26 +362,8 @@ class Batch:
         viol (B, 14) in the order of `names` = VIOL_NAMES).  Only these 16 numbers per instance are downloaded."""
         B = self.B
         ok = np.zeros(B, np.int32); rok = np.zeros(B, np.int32); viol = np.zeros((B, len(VIOL_NAMES)))
-        rc = _load().obca_batch_validate(self._h, C.c_double(float(tol)), ok.ctypes.data_as(_I), rok.ctypes.data_as(_I), viol.ctypes.data_as(_D))
-        self.ctx._check(rc, "obca_batch_validate")
+        self._call("validate", C.c_double(float(tol)), ok.ctypes.data_as(_I), rok.ctypes.data_as(_I), viol.ctypes.data_as(_D))
         return dict(ok=ok.astype(bool), ref_ok=rok.astype(bool), viol=viol, names=VIOL_NAMES)
-
-    def validate_ms(self):
-        """HIP-event duration of the last validate kernel"""
-        a = C.c_float(0)
-        self.ctx._check(_load().obca_batch_validate_ms(self._h, C.byref(a)), "obca_batch_validate_ms")
-        return a.value
-
-    def close(self):
-        if self._h:
-            _load().obca_batch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def parking_signed_dist_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, lWS=None, nWS=None,
@@ -541,13 +546,9 @@ def quadcopter_ipopt_opts():
     return o
 
 
-class QuadBatch:
+class QuadBatch(_DeviceBatch):
     """Device-resident batch of quadcopter signed-distance NLPs (obca_quad_batch_* in include/obca_hip.h)."""
-
-    def __init__(self, ctx, B, N):
-        self.ctx, self.B, self.N = ctx, int(B), int(N)
-        self._h = C.c_void_p()
-        ctx._check(_load().obca_quad_batch_create(ctx._h, C.c_int(self.B), C.c_int(self.N), C.byref(self._h)), "obca_quad_batch_create")
+    _c = "obca_quad_batch"
 
     def upload(self, x0, xF, Ts, R, ob, xWS, timeWS, dual_ws=True, dist=False):
         B, N = self.B, self.N
@@ -556,41 +557,18 @@ class QuadBatch:
         xw = np.ascontiguousarray(np.asarray(xWS, float)[:, :N + 1]); assert xw.shape == (B, N + 1, 12)
         keep = [_d(Tsv), _d(np.reshape(x0, (B, 12))), _d(np.reshape(xF, (B, 12))), _d(obv), _d(xw), _d(tw)]
         p = [k[1] for k in keep]
-        rc = _load().obca_quad_batch_upload(self._h, p[0], C.c_double(R), p[1], p[2], p[3], p[4], p[5], C.c_int(int(bool(dual_ws))), C.c_int(int(bool(dist))))
-        self.ctx._check(rc, "obca_quad_batch_upload")
-
-    def solve(self, opts=None, sync=True):
-        self.ctx._check(_load().obca_quad_batch_solve(self._h, C.byref(opts) if opts is not None else None), "obca_quad_batch_solve")
-        if sync:
-            self.sync()
-
-    def sync(self):
-        self.ctx._check(_load().obca_quad_batch_sync(self._h), "obca_quad_batch_sync")
+        self._call("upload", p[0], C.c_double(R), p[1], p[2], p[3], p[4], p[5], C.c_int(int(bool(dual_ws))), C.c_int(int(bool(dist))))
 
     def kernel_ms(self):
         a = C.c_float(0)
-        self.ctx._check(_load().obca_quad_batch_kernel_ms(self._h, C.byref(a)), "obca_quad_batch_kernel_ms")
+        self._call("kernel_ms", C.byref(a))
         return a.value
-
-    def scratch_bytes(self):
-        v = C.c_longlong(0)
-        _load().obca_quad_batch_scratch_bytes(self._h, C.byref(v))
-        return v.value
-
-    def phase_cycles(self):
-        out = np.zeros((self.B, 16))
-        if not hasattr(_load(), "obca_quad_batch_debug_phase_cycles"):
-            raise ObcaError("phase_cycles(): the loaded library is not the -DOBCA_PROFILE build")
-        self.ctx._check(_load().obca_quad_batch_debug_phase_cycles(self._h, out.ctypes.data_as(_D)), "obca_quad_batch_debug_phase_cycles")
-        return out
 
     def download(self):
         B, N = self.B, self.N
         xp = np.zeros((B, N + 1, 12)); up = np.zeros((B, N, 4)); ts = np.zeros((B, N + 1)); ef = np.zeros(B, np.int32)
         lp = np.zeros((B, N + 1, 30)); sl = np.zeros((B, N + 1, 5)); info = np.zeros((B, 8))
-        rc = _load().obca_quad_batch_download(self._h, xp.ctypes.data_as(_D), up.ctypes.data_as(_D), ts.ctypes.data_as(_D), ef.ctypes.data_as(_I),
-                                              lp.ctypes.data_as(_D), sl.ctypes.data_as(_D), info.ctypes.data_as(_D))
-        self.ctx._check(rc, "obca_quad_batch_download")
+        self._call("download", xp.ctypes.data_as(_D), up.ctypes.data_as(_D), ts.ctypes.data_as(_D), ef.ctypes.data_as(_I), lp.ctypes.data_as(_D), sl.ctypes.data_as(_D), info.ctypes.data_as(_D))
         T = lambda a: np.transpose(a, (0, 2, 1)).copy()
         return dict(xp=T(xp), up=T(up), timeScale=ts, exitflag=ef, lp=T(lp), slack=T(sl), info=info, iters=info[:, 1].astype(int),
                     obj=info[:, 2], status=info[:, 0].astype(int))
@@ -599,25 +577,8 @@ class QuadBatch:
         """constrSatisfaction on the last solution, on the device (obca_quad_batch_validate): dict(ok (B,) bool, viol (B, 9) in the order of `names` = QUAD_VIOL_NAMES)"""
         B = self.B
         ok = np.zeros(B, np.int32); viol = np.zeros((B, len(QUAD_VIOL_NAMES)))
-        rc = _load().obca_quad_batch_validate(self._h, C.c_double(float(tol)), ok.ctypes.data_as(_I), viol.ctypes.data_as(_D))
-        self.ctx._check(rc, "obca_quad_batch_validate")
+        self._call("validate", C.c_double(float(tol)), ok.ctypes.data_as(_I), viol.ctypes.data_as(_D))
         return dict(ok=ok.astype(bool), viol=viol, names=QUAD_VIOL_NAMES)
-
-    def validate_ms(self):
-        a = C.c_float(0)
-        self.ctx._check(_load().obca_quad_batch_validate_ms(self._h, C.byref(a)), "obca_quad_batch_validate_ms")
-        return a.value
-
-    def close(self):
-        if self._h:
-            _load().obca_quad_batch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def quadcopter_signed_dist_batch(x0, xF, N, Ts, R, ob, xWS, timeWS, dual_ws=True, opts=None, device=0, dist=False):

@@ -305,31 +305,6 @@ struct obca_ctx {
 };
 static std::string g_create_err;
 
-// buffers of the validate calls of a batch: device input (row lengths; a host-pointer call's trajectory extras) and output, their pinned mirrors, the events around the kernel
-struct ValBufs { double *d_in, *d_out, *h_in, *h_out; size_t dcap_in, dcap_out, hcap_in, hcap_out; hipEvent_t e0, e1; int have_ev, timed; };
-struct obca_batch {
-    obca_ctx *ctx; int device; hipStream_t stream; std::string err;
-    int B, cap, N, nObMax, MMax, zlen, have_duals, uploaded, dist, vmax;   // vmax: most rows of one obstacle in the uploaded instances
-    DevBufs d; double *stage;                               // stage: dense device staging of the PCIe transfers
-    double *h_prob, *h_zin, *h_zout, *h_info; size_t hcap_prob, hcap_zin, hcap_zout, hcap_info, dcap_stage;   // pinned host staging
-    std::vector<int> nOb, M, obOff, rowOff;                 // per instance; offsets into the caller's packed obstacle arrays
-    // |a_r| of every half-space row of the uploaded instances (index: row offset - rowOff[0]), see batch_upload_range
-    std::vector<double> rowLen;
-    int fixTime;
-    hipEvent_t e0, e1, e2;
-    long long bytes;
-    int sliced;          // slice length (passes) of the last solve if it used the two-launch schedule, else 0
-    int solved;          // a solve has been queued since the last upload / shift: d.z holds a solution obca_batch_validate may check
-    int val_rl;          // the row lengths of the uploaded instances are in val.d_in (resident validate)
-    ValBufs val;
-};
-
-#define HIPCHK(bt, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (bt)->err = std::string(#call) + ": " + hipGetErrorString(e_); return -2; } } while (0)
-// The device index of a context / batch was validated when the context was created (obca_create: hipSetDevice checked there); later calls only select it again,
-// and whatever they then launch or copy reports its own error.  Release paths ignore the status of hipFree & co. on purpose -- `(void)` says so at each site
-// (the library builds with -Wall -Wextra -Werror: an ignored status is a compile error).
-static inline void use_device(int device) { (void)hipSetDevice(device); }
-static inline int fin(obca_batch *bt, int rc) { if (rc) bt->ctx->err = bt->err; return rc; }
 // Device work buffers never carry what a previous owner of the memory left in them:
 // every allocation is filled once, on the stream of the batch it belongs to (the
 // lanes' streams do not synchronise with the null stream).  The product build clears
@@ -347,13 +322,107 @@ static hipError_t dev_alloc(void **p, size_t bytes, hipStream_t stream) {
     return hipMemsetAsync(*p, OBCA_FILL_BYTE, bytes, stream);
 }
 
-static int pinned_reserve(std::string &err, double **p, size_t *cap, size_t need) {
-    if (*cap >= need) return 0;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr; *cap = 0;
-    if (hipHostMalloc((void **)p, need * sizeof(double), hipHostMallocDefault) != hipSuccess) { err = "hipHostMalloc failed"; return -2; }
-    *cap = need;
+// Staging memory that only grows: `cap` doubles at `p` (read like the plain pointer); reserve() keeps a block that is large enough, else frees it
+// and allocates `need` doubles (the contents are not carried over); release() frees.  PinnedBuf: page-locked host memory; DevBuf: device memory from dev_alloc.
+namespace {      // (their member functions are no symbols of the library)
+struct PinnedBuf {
+    double *p = nullptr; size_t cap = 0;
+    operator double *() const { return p; }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+    int reserve(std::string &err, size_t need) {
+        if (cap >= need) return 0;
+        release();
+        if (hipHostMalloc((void **)&p, need * sizeof(double), hipHostMallocDefault) != hipSuccess) { err = "hipHostMalloc failed"; return -2; }
+        cap = need;
+        return 0;
+    }
+};
+struct DevBuf {
+    double *p = nullptr; size_t cap = 0;
+    operator double *() const { return p; }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    hipError_t reserve(size_t need, hipStream_t stream) {
+        if (cap >= need) return hipSuccess;
+        release();
+        const hipError_t e = dev_alloc((void **)&p, need * sizeof(double), stream);
+        if (e == hipSuccess) cap = need;
+        return e;
+    }
+};
+}  // namespace
+
+// buffers of the validate calls of a batch: device input (row lengths; a host-pointer call's trajectory extras) and output, their pinned mirrors, the events around the kernel
+struct ValBufs { DevBuf d_in, d_out; PinnedBuf h_in, h_out; hipEvent_t e0 = nullptr, e1 = nullptr; int have_ev = 0, timed = 0; };
+// what a parking and a quadcopter batch have in common
+struct BatchCore {
+    obca_ctx *ctx; int device; hipStream_t stream; std::string err;
+    int B, cap, N;
+    int uploaded = 0;
+    int solved = 0;      // a solve has been queued since the last upload / shift: d.z holds a solution the validate entry points may check
+    long long bytes = 0;
+    DevBuf stage;                                           // dense device staging of the PCIe transfers
+    PinnedBuf h_prob, h_info;                               // pinned host staging
+    hipEvent_t e0 = nullptr, e1 = nullptr;                  // around the kernels of the last solve
+    ValBufs val;
+    BatchCore(obca_ctx *c, int dev, hipStream_t s, int B_, int N_) : ctx(c), device(dev), stream(s), B(B_), cap(B_), N(N_) {}
+};
+struct obca_quad_batch : BatchCore {
+    using BatchCore::BatchCore;
+    QDevBufs d = {};
+    PinnedBuf h_z;
+};
+struct obca_batch : BatchCore {
+    using BatchCore::BatchCore;
+    int nObMax = 0, MMax = 0, zlen = 0, have_duals = 0, dist = 0, vmax = 0;   // vmax: most rows of one obstacle in the uploaded instances
+    DevBufs d = {};
+    PinnedBuf h_zin, h_zout;
+    std::vector<int> nOb, M, obOff, rowOff;                 // per instance; offsets into the caller's packed obstacle arrays
+    // |a_r| of every half-space row of the uploaded instances (index: row offset - rowOff[0]), see batch_upload_range
+    std::vector<double> rowLen;
+    int fixTime = 0;
+    hipEvent_t e2 = nullptr;      // e0 .. e1: DualMultWS, e1 .. e2: interior point
+    int sliced = 0;      // slice length (passes) of the last solve if it used the two-launch schedule, else 0
+    int val_rl = 0;      // the row lengths of the uploaded instances are in val.d_in (resident validate)
+};
+
+#define HIPCHK(bt, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (bt)->err = std::string(#call) + ": " + hipGetErrorString(e_); return -2; } } while (0)
+// The device index of a context / batch was validated when the context was created (obca_create: hipSetDevice checked there); later calls only select it again,
+// and whatever they then launch or copy reports its own error.  Release paths ignore the status of hipFree & co. on purpose -- `(void)` says so at each site
+// (the library builds with -Wall -Wextra -Werror: an ignored status is a compile error).
+static inline void use_device(int device) { (void)hipSetDevice(device); }
+static inline int fin(BatchCore *bt, int rc) { if (rc) bt->ctx->err = bt->err; return rc; }
+
+// the bodies of the obca_batch_* / obca_quad_batch_* entry points that differ in nothing but the text of their error (`what`)
+static int core_sync(BatchCore *bt, const char *what) {
+    if (!bt) return -1;
+    use_device(bt->device);
+    if (hipStreamSynchronize(bt->stream) != hipSuccess) { bt->ctx->err = what; return -2; }
     return 0;
+}
+static int core_elapsed_ms(BatchCore *bt, bool recorded, hipEvent_t from, hipEvent_t to, float *ms, const char *what) {
+    if (!recorded || hipEventElapsedTime(ms, from, to) != hipSuccess) { bt->ctx->err = what; return -2; }
+    return 0;
+}
+static int core_validate_ms(BatchCore *bt, float *ms, const char *what) {
+    if (!bt || !ms) return -1;
+    return core_elapsed_ms(bt, bt->val.timed != 0, bt->val.e0, bt->val.e1, ms, what);
+}
+static int core_scratch_bytes(const BatchCore *bt, long long *bytes) { if (!bt || !bytes) return -1; *bytes = bt->bytes; return 0; }
+#ifdef OBCA_PROFILE      /* the per-phase clocks exist in the profiling build only (libobca_hip_prof.so, tools/phase_profile.py): not an entry point of the product */
+static int core_phase_cycles(BatchCore *bt, const double *prof, double *out /* B x 16 */, const char *what) {
+    if (!out) return -1;
+    use_device(bt->device);
+    if (hipStreamSynchronize(bt->stream) != hipSuccess || hipMemcpy(out, prof, (size_t)bt->B * 16 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { bt->ctx->err = what; return -2; }
+    return 0;
+}
+#endif
+// everything of the core that a batch's destroy releases, except `stage` (it goes with the family's device buffers); the batch's device is selected
+static void core_release(BatchCore *bt) {
+    ValBufs &v = bt->val;
+    v.d_in.release(); v.d_out.release(); v.h_in.release(); v.h_out.release();
+    if (v.have_ev) { (void)hipEventDestroy(v.e0); (void)hipEventDestroy(v.e1); }
+    bt->h_prob.release(); bt->h_info.release();
+    (void)hipEventDestroy(bt->e0); (void)hipEventDestroy(bt->e1);
 }
 
 extern "C" {
@@ -446,22 +515,17 @@ int obca_device_name(const obca_ctx *c, char *buf, int n) { if (!c || !buf || n 
 
 static int batch_create_on(obca_ctx *ctx, int device, hipStream_t stream, int B, int N, obca_batch **out, std::string &err) {
     if (B < 1 || N < 0 || N > OBCA_NMAX) { err = "obca_batch_create: need B>=1, 0<=N<=OBCA_NMAX"; return -1; }
-    obca_batch *bt = new obca_batch();
-    bt->ctx = ctx; bt->device = device; bt->stream = stream;
-    bt->B = B; bt->cap = B; bt->N = N; bt->uploaded = 0; bt->have_duals = 0; bt->nObMax = 0; bt->MMax = 0; bt->bytes = 0; bt->dist = 0; bt->sliced = 0;
-    bt->zlen = 0; bt->fixTime = 0; bt->vmax = 0; bt->solved = 0; bt->val_rl = 0; memset(&bt->val, 0, sizeof bt->val);
-    memset(&bt->d, 0, sizeof bt->d); bt->stage = nullptr; bt->dcap_stage = 0;
-    bt->h_prob = bt->h_zin = bt->h_zout = bt->h_info = nullptr; bt->hcap_prob = bt->hcap_zin = bt->hcap_zout = bt->hcap_info = 0;
+    obca_batch *bt = new obca_batch(ctx, device, stream, B, N);
     use_device(device);
     if (hipEventCreate(&bt->e0) != hipSuccess || hipEventCreate(&bt->e1) != hipSuccess || hipEventCreate(&bt->e2) != hipSuccess) { err = "hipEventCreate failed"; delete bt; return -2; }
     *out = bt;
     return 0;
 }
 static void free_dev(obca_batch *bt) {
-    double **ps[] = {&bt->d.prob, &bt->d.z0, &bt->d.z, &bt->d.zn, &bt->d.d, &bt->d.as, &bt->d.rs, &bt->d.oc, &bt->d.info, &bt->d.dws, &bt->d.prof, &bt->d.slice, &bt->d.csoc, &bt->stage};
+    double **ps[] = {&bt->d.prob, &bt->d.z0, &bt->d.z, &bt->d.zn, &bt->d.d, &bt->d.as, &bt->d.rs, &bt->d.oc, &bt->d.info, &bt->d.dws, &bt->d.prof, &bt->d.slice, &bt->d.csoc};
     for (auto p : ps) { if (*p) (void)hipFree(*p); *p = nullptr; }
     if (bt->d.order) (void)hipFree(bt->d.order); bt->d.order = nullptr;
-    bt->dcap_stage = 0;
+    bt->stage.release();
 }
 
 // everything a parking call hands over (host pointers of the whole call; a chunk is instances lo .. lo+n-1 of it)
@@ -521,8 +585,8 @@ static int batch_upload_range(obca_batch *bt, const ParkIn &in, int lo, int n) {
         ALLOC(d.info, B * 8); ALLOC(d.dws, B * N1 * bt->nObMax); ALLOC(d.prof, B * 16);
         ALLOC(d.slice, B * SL_SIZE);
         ALLOC(d.csoc, B * d.s_csoc);      // (rows + direction of a second-order correction: with the other buffers since round 6 -- allocated by the first solve that asked for corrections, it put a 60 MB hipMalloc into that solve: profiles/r06_first_solve_costs.txt)
-        bt->dcap_stage = B * (size_t)lmax.nprimal;                       // nprimal >= the output prefix
-        ALLOC(bt->stage, bt->dcap_stage);
+        if (hipError_t e_ = bt->stage.reserve(B * (size_t)lmax.nprimal, bt->stream)) { bt->err = std::string("hipMalloc(bt->stage): ") + hipGetErrorString(e_); free_dev(bt); return -2; }
+        tot += bt->stage.cap * sizeof(double);                           // nprimal >= the output prefix
         if (dev_alloc((void **)&d.order, (B + 1) * sizeof(int), bt->stream) != hipSuccess) { bt->err = "hipMalloc(order) failed"; free_dev(bt); return -2; }
         tot += (B + 1) * sizeof(int);
 #undef ALLOC
@@ -534,7 +598,7 @@ static int batch_upload_range(obca_batch *bt, const ParkIn &in, int lo, int n) {
     // only what the caller provides travels over PCIe: x, u, t (the same offsets in every instance's layout) and, with a dual warm start, lam and mu;
     // the scatter kernel clears the rest of each row
     const size_t W = duals ? (size_t)lmax.sl : (size_t)lmax.lam;
-    if (pinned_reserve(bt->err, &bt->h_prob, &bt->hcap_prob, B * d.s_prob) || pinned_reserve(bt->err, &bt->h_zin, &bt->hcap_zin, B * W)) return -2;
+    if (bt->h_prob.reserve(bt->err, B * d.s_prob) || bt->h_zin.reserve(bt->err, B * W)) return -2;
     const double *ego = in.ego, *XYb = in.XYb;
     const double W_ev = ego[1] + ego[3], L_ev = ego[0] + ego[2];     /* ParkingSignedDist.jl:182-188 */
     for (int i = 0; i < n; i++) {
@@ -675,8 +739,7 @@ static int batch_download_range(obca_batch *bt, const ParkOut &o, int lo) {
     Lay lmax; make_layout(N, bt->nObMax, bt->MMax, lmax);
     const size_t W = (size_t)lmax.so;                       // outputs are a prefix of the iterate: x, u, t, lam, mu, sl
     const bool want_z = o.xp || o.up || o.ts || o.lp || o.np || o.slp || o.lWS || o.nWS;
-    if (pinned_reserve(bt->err, &bt->h_zout, &bt->hcap_zout, (size_t)bt->cap * std::max(W, (size_t)N1 * bt->nObMax)) ||
-        pinned_reserve(bt->err, &bt->h_info, &bt->hcap_info, (size_t)bt->cap * 8)) return -2;
+    if (bt->h_zout.reserve(bt->err, (size_t)bt->cap * std::max(W, (size_t)N1 * bt->nObMax)) || bt->h_info.reserve(bt->err, (size_t)bt->cap * 8)) return -2;
     if (want_z) {
         hipLaunchKernelGGL(obca_gather_rows_kernel, dim3(B, (unsigned)((W + 1023) / 1024)), dim3(256), 0, bt->stream, bt->stage, W, (const double *)d.z, d.s_z);
         HIPCHK(bt, hipGetLastError());
@@ -710,79 +773,67 @@ static int batch_download_range(obca_batch *bt, const ParkOut &o, int lo) {
 }
 
 // ---- a-posteriori validation (obca_validate.h)
-static void val_release(ValBufs &v) {
-    if (v.d_in) (void)hipFree(v.d_in);
-    if (v.d_out) (void)hipFree(v.d_out);
-    if (v.h_in) (void)hipHostFree(v.h_in);
-    if (v.h_out) (void)hipHostFree(v.h_out);
-    if (v.have_ev) { (void)hipEventDestroy(v.e0); (void)hipEventDestroy(v.e1); }
-    memset(&v, 0, sizeof v);
-}
 static int val_reserve(std::string &err, ValBufs &v, size_t in_doubles, size_t out_doubles, hipStream_t stream) {
     if (!v.have_ev) {
         if (hipEventCreate(&v.e0) != hipSuccess) { err = "hipEventCreate failed"; return -2; }
         if (hipEventCreate(&v.e1) != hipSuccess) { (void)hipEventDestroy(v.e0); err = "hipEventCreate failed"; return -2; }
         v.have_ev = 1;
     }
-    if (v.dcap_in < in_doubles) {
-        if (v.d_in) (void)hipFree(v.d_in);
-        v.dcap_in = 0;
-        if (dev_alloc((void **)&v.d_in, in_doubles * sizeof(double), stream) != hipSuccess) { err = "hipMalloc(validate input) failed"; return -2; }
-        v.dcap_in = in_doubles;
-    }
-    if (v.dcap_out < out_doubles) {
-        if (v.d_out) (void)hipFree(v.d_out);
-        v.dcap_out = 0;
-        if (dev_alloc((void **)&v.d_out, out_doubles * sizeof(double), stream) != hipSuccess) { err = "hipMalloc(validate output) failed"; return -2; }
-        v.dcap_out = out_doubles;
-    }
-    if (pinned_reserve(err, &v.h_in, &v.hcap_in, in_doubles) || pinned_reserve(err, &v.h_out, &v.hcap_out, out_doubles)) return -2;
+    if (v.d_in.reserve(in_doubles, stream) != hipSuccess) { err = "hipMalloc(validate input) failed"; return -2; }
+    if (v.d_out.reserve(out_doubles, stream) != hipSuccess) { err = "hipMalloc(validate output) failed"; return -2; }
+    if (v.h_in.reserve(err, in_doubles) || v.h_out.reserve(err, out_doubles)) return -2;
     return 0;
 }
-static int val_ms(const ValBufs &v, float *ms) {
-    if (!v.timed || hipEventElapsedTime(ms, v.e0, v.e1) != hipSuccess) return -2;
+// One validate call over the batch's instances, on its stream: reserve the buffers -> if `upload`, pack(i, row) fills instance i's `s_in` doubles of val.h_in
+// and they travel up to val.d_in (else val.d_in is left as it is) -> launch() between the two events -> the `s_out` result doubles per instance come down -> unpack(i, row) reads instance i's.
+// Synchronises the batch's stream.
+template <typename Pack, typename Launch, typename Unpack>
+static int run_validate(BatchCore *bt, size_t s_in, bool upload, size_t s_out, Pack &&pack, Launch &&launch, Unpack &&unpack) {
+    const int B = bt->B;
+    use_device(bt->device);
+    if (int rc = val_reserve(bt->err, bt->val, std::max<size_t>(1, (size_t)bt->cap * s_in), (size_t)bt->cap * s_out, bt->stream)) return rc;
+    ValBufs &v = bt->val;
+    if (upload) {
+        for (int i = 0; i < B; i++) pack(i, v.h_in + (size_t)i * s_in);
+        HIPCHK(bt, hipMemcpyAsync(v.d_in, v.h_in, (size_t)B * s_in * sizeof(double), hipMemcpyHostToDevice, bt->stream));
+    }
+    HIPCHK(bt, hipEventRecord(v.e0, bt->stream));
+    launch();
+    HIPCHK(bt, hipGetLastError());
+    HIPCHK(bt, hipEventRecord(v.e1, bt->stream));
+    v.timed = 1;
+    HIPCHK(bt, hipMemcpyAsync(v.h_out, v.d_out, (size_t)B * s_out * sizeof(double), hipMemcpyDeviceToHost, bt->stream));
+    HIPCHK(bt, hipStreamSynchronize(bt->stream));
+    for (int i = 0; i < B; i++) unpack(i, (const double *)v.h_out + (size_t)i * s_out);
     return 0;
 }
 
 // Checks the batch's instances: resident (ts == nullptr: the last solution in d.z, only the row lengths travel up) or a caller's trajectory that
 // batch_upload_range has just packed into d.z0 (ts: (N + 1) per instance of the call, sl: the caller's packed slack or nullptr = the zeros of the upload).
-// Instance i of the batch is instance lo + i of the call.  Only PV_OUT doubles per instance come back.  Synchronises the batch's stream.
+// Instance i of the batch is instance lo + i of the call.  Only PV_OUT doubles per instance come back.
 static int batch_validate_range(obca_batch *bt, const double *ts, const double *sl, double tol, int lo, int *ok, int *ref_ok, double *viol) {
     const int B = bt->B, N = bt->N, N1 = N + 1, MMax = bt->MMax;
     const bool host = ts != nullptr;
     const size_t s_aux = (size_t)MMax + (host ? (size_t)N1 + (size_t)bt->nObMax * N1 : 0);
-    use_device(bt->device);
-    if (int rc = val_reserve(bt->err, bt->val, std::max<size_t>(1, (size_t)bt->cap * s_aux), (size_t)bt->cap * PV_OUT, bt->stream)) return rc;
-    ValBufs &v = bt->val;
-    if (host || !bt->val_rl) {
-        for (int i = 0; i < B; i++) {
-            double *a = v.h_in + (size_t)i * s_aux;
-            const double *rl = bt->rowLen.data() + (bt->rowOff[i] - bt->rowOff[0]);
-            for (int r = 0; r < MMax; r++) a[r] = r < bt->M[i] ? rl[r] : 1.0;
-            if (host) {
-                memcpy(a + MMax, ts + ((size_t)lo + i) * N1, sizeof(double) * N1);
-                double *as = a + MMax + N1; const size_t ns = (size_t)bt->nOb[i] * N1;
-                if (sl) memcpy(as, sl + (size_t)bt->obOff[i] * N1, sizeof(double) * ns); else memset(as, 0, sizeof(double) * ns);
-            }
+    const int rc = run_validate(bt, s_aux, host || !bt->val_rl, PV_OUT, [&](int i, double *a) {
+        const double *rl = bt->rowLen.data() + (bt->rowOff[i] - bt->rowOff[0]);
+        for (int r = 0; r < MMax; r++) a[r] = r < bt->M[i] ? rl[r] : 1.0;
+        if (host) {
+            memcpy(a + MMax, ts + ((size_t)lo + i) * N1, sizeof(double) * N1);
+            double *as = a + MMax + N1; const size_t ns = (size_t)bt->nOb[i] * N1;
+            if (sl) memcpy(as, sl + (size_t)bt->obOff[i] * N1, sizeof(double) * ns); else memset(as, 0, sizeof(double) * ns);
         }
-        HIPCHK(bt, hipMemcpyAsync(v.d_in, v.h_in, (size_t)B * s_aux * sizeof(double), hipMemcpyHostToDevice, bt->stream));
-        bt->val_rl = host ? 0 : 1;
-    }
-    HIPCHK(bt, hipEventRecord(v.e0, bt->stream));
-    hipLaunchKernelGGL(obca_validate_parking_kernel, dim3(B), dim3(OB_NT), 0, bt->stream, B, N, (const double *)bt->d.prob, bt->d.s_prob, (const double *)(host ? bt->d.z0 : bt->d.z), bt->d.s_z,
-                       (const double *)v.d_in, s_aux, MMax, host ? 1 : 0, (host && sl) ? 1 : 0, tol, v.d_out);
-    HIPCHK(bt, hipGetLastError());
-    HIPCHK(bt, hipEventRecord(v.e1, bt->stream));
-    v.timed = 1;
-    HIPCHK(bt, hipMemcpyAsync(v.h_out, v.d_out, (size_t)B * PV_OUT * sizeof(double), hipMemcpyDeviceToHost, bt->stream));
-    HIPCHK(bt, hipStreamSynchronize(bt->stream));
-    for (int i = 0; i < B; i++) {
-        const double *o = v.h_out + (size_t)i * PV_OUT; const size_t g = (size_t)lo + i;
+    }, [&] {
+        hipLaunchKernelGGL(obca_validate_parking_kernel, dim3(B), dim3(OB_NT), 0, bt->stream, B, N, (const double *)bt->d.prob, bt->d.s_prob, (const double *)(host ? bt->d.z0 : bt->d.z), bt->d.s_z,
+                           (const double *)bt->val.d_in, s_aux, MMax, host ? 1 : 0, (host && sl) ? 1 : 0, tol, bt->val.d_out);
+    }, [&](int i, const double *o) {
+        const size_t g = (size_t)lo + i;
         if (viol) memcpy(viol + g * PV_NCLS, o, sizeof(double) * PV_NCLS);
         if (ok) ok[g] = o[PV_NCLS] != 0.0;
         if (ref_ok) ref_ok[g] = o[PV_NCLS + 1] != 0.0;
-    }
-    return 0;
+    });
+    if (!rc && !host) bt->val_rl = 1;      // the row lengths stay in val.d_in until the next upload: the next resident validate skips its H2D
+    return rc;
 }
 
 // ---- chunked execution of a host-pointer call over the slots of the context (work queue)
@@ -834,11 +885,12 @@ static int pick_chunk(const obca_ctx *ctx, int B, int resident_per_cu) {
     if (B < chunk * ns && B >= 64 * ns) chunk = (B + ns - 1) / ns;
     return std::max(1, std::min(chunk, B));
 }
-static int slot_parking_batch(obca_ctx *ctx, Slot &s, int n, int N, int dist, std::string &err) {
-    if (s.pb && (s.pb->cap < n || s.pb->N != N)) { obca_batch_destroy(s.pb); s.pb = nullptr; }
-    if (!s.pb) { int rc = batch_create_on(ctx, s.device, s.stream, n, N, &s.pb, err); if (rc) return rc; }
-    if (s.pb->dist != (dist ? 1 : 0)) { s.pb->dist = dist ? 1 : 0; }
-    return 0;
+static int batch_create_on(obca_ctx *ctx, int device, hipStream_t stream, int B, int N, obca_quad_batch **out, std::string &err);
+// the slot's cached batch (`cached` is s.pb or s.qb) if it holds `need` instances of horizon N, else a new one of capacity `cap` in its place
+template <typename BT>
+static int slot_batch(obca_ctx *ctx, Slot &s, BT *&cached, int (*destroy)(BT *), int need, int cap, int N, std::string &err) {
+    if (cached && (cached->cap < need || cached->N != N)) { destroy(cached); cached = nullptr; }
+    return cached ? 0 : batch_create_on(ctx, s.device, s.stream, cap, N, &cached, err);
 }
 
 static int parking_call(obca_ctx *ctx, int dist, int dualws_only, int B, int N, ParkIn &in, const obca_opts *opts, const ParkOut &out) {
@@ -849,9 +901,9 @@ static int parking_call(obca_ctx *ctx, int dist, int dualws_only, int B, int N, 
     if (int rc = park_prefix(ctx->err, B, in.nOb, in.vOb, in)) return rc;
     const int chunk = pick_chunk(ctx, B, 4);
     return run_chunks(ctx, B, chunk, [&](Slot &s, int lo, int n, std::string &err) -> int {
-        int rc = slot_parking_batch(ctx, s, std::min(chunk, B), N, dist, err);
+        int rc = slot_batch(ctx, s, s.pb, obca_batch_destroy, std::min(chunk, B), std::min(chunk, B), N, err);
         if (rc) return rc;
-        obca_batch *bt = s.pb;
+        obca_batch *bt = s.pb; bt->dist = dist ? 1 : 0;
         rc = batch_upload_range(bt, in, lo, n);
         if (!rc) rc = batch_solve(bt, opts, dualws_only);
         if (!rc) rc = batch_download_range(bt, out, lo);
@@ -869,23 +921,14 @@ int obca_batch_create(obca_ctx *ctx, int B, int N, obca_batch **out) {
 int obca_batch_destroy(obca_batch *bt) {
     if (!bt) return -1;
     use_device(bt->device);
-    free_dev(bt); val_release(bt->val); (void)hipEventDestroy(bt->e0); (void)hipEventDestroy(bt->e1); (void)hipEventDestroy(bt->e2);
-    double **hs[] = {&bt->h_prob, &bt->h_zin, &bt->h_zout, &bt->h_info};
-    for (auto p : hs) if (*p) (void)hipHostFree(*p);
+    free_dev(bt); core_release(bt); (void)hipEventDestroy(bt->e2); bt->h_zin.release(); bt->h_zout.release();
     delete bt; return 0;
 }
-#ifdef OBCA_PROFILE      /* the per-phase clocks exist in the profiling build only (libobca_hip_prof.so, tools/phase_profile.py): not an entry point of the product */
-int obca_batch_debug_phase_cycles(obca_batch *bt, double *out /* B x 16 */) {   
-    if (!bt || !out) return -1;
-    use_device(bt->device);
-    if (hipStreamSynchronize(bt->stream) != hipSuccess ||
-        hipMemcpy(out, bt->d.prof, (size_t)bt->B * 16 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { bt->ctx->err = "obca_batch_debug_phase_cycles: copy failed";
-        return -2; }
-    return 0;
-}
+#ifdef OBCA_PROFILE
+int obca_batch_debug_phase_cycles(obca_batch *bt, double *out) { return bt ? core_phase_cycles(bt, bt->d.prof, out, "obca_batch_debug_phase_cycles: copy failed") : -1; }
 #endif
 int obca_batch_set_formulation(obca_batch *bt, int dist) { if (!bt) return -1; bt->dist = dist ? 1 : 0; return 0; }   /* before obca_batch_upload */
-int obca_batch_scratch_bytes(const obca_batch *bt, long long *bytes) { if (!bt || !bytes) return -1; *bytes = bt->bytes; return 0; }
+int obca_batch_scratch_bytes(const obca_batch *bt, long long *bytes) { return core_scratch_bytes(bt, bytes); }
 
 int obca_batch_upload(obca_batch *bt, const double *Ts, double L, const double ego[4], const double XYb[4], int fixTime,
                       const double *x0, const double *xF, const int *nOb, const int *vOb, const double *A, const double *b,
@@ -908,7 +951,7 @@ int obca_batch_shift_warm_start(obca_batch *bt, int shift, const double *x0_new)
     use_device(bt->device);
     double *dx0 = nullptr;
     if (x0_new) {   // staged through the (idle) device staging buffer of the batch: nothing to free on the error paths
-        if (pinned_reserve(bt->err, &bt->h_info, &bt->hcap_info, (size_t)bt->cap * 8)) return fin(bt, -2);
+        if (bt->h_info.reserve(bt->err, (size_t)bt->cap * 8)) return fin(bt, -2);
         memcpy(bt->h_info, x0_new, (size_t)bt->B * 4 * sizeof(double));
         dx0 = bt->stage;
         if (hipMemcpyAsync(dx0, bt->h_info, (size_t)bt->B * 4 * sizeof(double), hipMemcpyHostToDevice, bt->stream) != hipSuccess) { ctx->err = "obca_batch_shift_warm_start: H2D failed"; return -2; }
@@ -919,12 +962,7 @@ int obca_batch_shift_warm_start(obca_batch *bt, int shift, const double *x0_new)
     bt->have_duals = 1;                                 // the shifted multipliers are the dual warm start: DualMultWS is skipped
     return 0;
 }
-int obca_batch_sync(obca_batch *bt) {
-    if (!bt) return -1;
-    use_device(bt->device);
-    if (hipStreamSynchronize(bt->stream) != hipSuccess) { bt->ctx->err = "obca_batch_sync: hipStreamSynchronize failed"; return -2; }
-    return 0;
-}
+int obca_batch_sync(obca_batch *bt) { return core_sync(bt, "obca_batch_sync: hipStreamSynchronize failed"); }
 int obca_batch_last_schedule(const obca_batch *bt, int *ipm_launches, int *slice_passes) {
     if (!bt) return -1;
     if (ipm_launches) *ipm_launches = bt->sliced ? 2 : 1;
@@ -933,8 +971,8 @@ int obca_batch_last_schedule(const obca_batch *bt, int *ipm_launches, int *slice
 }
 int obca_batch_kernel_ms(obca_batch *bt, float *ipm_ms, float *dualws_ms) {
     if (!bt) return -1;
-    float a = 0, b = 0;
-    if (hipEventElapsedTime(&a, bt->e0, bt->e1) != hipSuccess || hipEventElapsedTime(&b, bt->e1, bt->e2) != hipSuccess) { bt->ctx->err = "obca_batch_kernel_ms: events not ready"; return -2; }
+    float a = 0, b = 0; const char *what = "obca_batch_kernel_ms: events not ready";
+    if (core_elapsed_ms(bt, true, bt->e0, bt->e1, &a, what) || core_elapsed_ms(bt, true, bt->e1, bt->e2, &b, what)) return -2;
     if (dualws_ms) *dualws_ms = a; if (ipm_ms) *ipm_ms = b;
     return 0;
 }
@@ -952,11 +990,7 @@ int obca_batch_validate(obca_batch *bt, double tol, int *ok, int *ref_ok, double
     if (bt->N < 1) { bt->ctx->err = "obca_batch_validate: needs a horizon N>=1"; return -1; }
     return fin(bt, batch_validate_range(bt, nullptr, nullptr, tol > 0 ? tol : PV_REF_TOL, 0, ok, ref_ok, viol));
 }
-int obca_batch_validate_ms(obca_batch *bt, float *ms) {
-    if (!bt || !ms) return -1;
-    if (val_ms(bt->val, ms)) { bt->ctx->err = "obca_batch_validate_ms: no validate call has run on this batch"; return -2; }
-    return 0;
-}
+int obca_batch_validate_ms(obca_batch *bt, float *ms) { return core_validate_ms(bt, ms, "obca_batch_validate_ms: no validate call has run on this batch"); }
 int obca_parking_constraints_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const double XYb[4], int fixTime,
                                    const double *x0, const double *xF, const int *nOb, const int *vOb, const double *A, const double *b, int dist,
                                    const double *x, const double *u, const double *timeScale, const double *l, const double *n, const double *sl,
@@ -970,9 +1004,9 @@ int obca_parking_constraints_batch(obca_ctx *ctx, int B, int N, const double *Ts
     const double tl = tol > 0 ? tol : PV_REF_TOL;
     const int chunk = pick_chunk(ctx, B, 4);
     return run_chunks(ctx, B, chunk, [&](Slot &s, int lo, int cnt, std::string &err) -> int {
-        int rc = slot_parking_batch(ctx, s, std::min(chunk, B), N, dist, err);
+        int rc = slot_batch(ctx, s, s.pb, obca_batch_destroy, std::min(chunk, B), std::min(chunk, B), N, err);
         if (rc) return rc;
-        obca_batch *bt = s.pb;
+        obca_batch *bt = s.pb; bt->dist = dist ? 1 : 0;
         rc = batch_upload_range(bt, in, lo, cnt);
         if (!rc) rc = batch_validate_range(bt, timeScale, sl, tl, lo, ok, ref_ok, viol);
         if (rc) err = bt->err;
@@ -1017,40 +1051,27 @@ int obca_dualmult_ws_batch(obca_ctx *ctx, int B, int N, const double ego[4], con
 }  // extern "C"
 
 /* ---------------------------------------------------------------- quadcopter path */
-struct obca_quad_batch {
-    obca_ctx *ctx; int device; hipStream_t stream; std::string err;
-    int B, cap, N, uploaded;
-    QDevBufs d; double *stage; hipEvent_t e0, e1; long long bytes;
-    double *h_prob, *h_z, *h_info; size_t hcap_prob, hcap_z, hcap_info;       // pinned host staging
-    int solved;          // a solve has been queued since the last upload
-    ValBufs val;
-};
-#define QCHK(bt, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (bt)->err = std::string(#call) + ": " + hipGetErrorString(e_); return -2; } } while (0)
-static inline int qfin(obca_quad_batch *bt, int rc) { if (rc) bt->ctx->err = bt->err; return rc; }
-static void qfree_dev(obca_quad_batch *bt) {
+static void free_dev(obca_quad_batch *bt) {
     double **ps[] = {&bt->d.prob, &bt->d.z, &bt->d.d, &bt->d.as, &bt->d.rs, &bt->d.oc, &bt->d.info, &bt->d.prof};
     for (auto p : ps) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    if (bt->stage) (void)hipFree(bt->stage); bt->stage = nullptr;
+    bt->stage.release();
 }
-static int quad_batch_create_on(obca_ctx *ctx, int device, hipStream_t stream, int B, int N, obca_quad_batch **out, std::string &err) {
+static int batch_create_on(obca_ctx *ctx, int device, hipStream_t stream, int B, int N, obca_quad_batch **out, std::string &err) {
     if (B < 1 || N < 2 || N > OBCA_QUAD_NMAX) { err = "obca_quad_batch_create: need B>=1, 2<=N<=OBCA_QUAD_NMAX"; return -1; }
-    obca_quad_batch *bt = new obca_quad_batch();
-    bt->ctx = ctx; bt->device = device; bt->stream = stream; bt->B = B; bt->cap = B; bt->N = N; bt->uploaded = 0; bt->bytes = 0;
-    memset(&bt->d, 0, sizeof bt->d); bt->stage = nullptr;
-    bt->h_prob = bt->h_z = bt->h_info = nullptr; bt->hcap_prob = bt->hcap_z = bt->hcap_info = 0;
-    bt->solved = 0; memset(&bt->val, 0, sizeof bt->val);
+    obca_quad_batch *bt = new obca_quad_batch(ctx, device, stream, B, N);
     use_device(device);
     quad::QLay l; quad::q_make_layout(N, l);
     QDevBufs &d = bt->d; const size_t N1 = N + 1;
     d.s_prob = QPH_SIZE + QX * N1; d.s_z = l.len; d.s_d = QDIR_DOUBLES(l);
          /* two direction buffers (dv | dy) + the rows of a second-order correction, see QCS */ d.s_as = N1 * QSP; d.s_rs = N1 * QRR; d.s_oc = N1 * QOB * OB_OC;
     size_t tot = 0;
-#define ALLOC(ptr, cnt) do { size_t by_ = (size_t)(cnt) * sizeof(double); if (dev_alloc((void **)&(ptr), by_, stream) != hipSuccess) { err = "obca_quad_batch_create: hipMalloc failed"; qfree_dev(bt); delete bt; return -2; } tot += by_; } while (0)
+#define ALLOC(ptr, cnt) do { size_t by_ = (size_t)(cnt) * sizeof(double); if (dev_alloc((void **)&(ptr), by_, stream) != hipSuccess) { err = "obca_quad_batch_create: hipMalloc failed"; free_dev(bt); delete bt; return -2; } tot += by_; } while (0)
     ALLOC(d.prob, B * d.s_prob); ALLOC(d.z, B * d.s_z); ALLOC(d.d, B * d.s_d); ALLOC(d.as, B * d.s_as); ALLOC(d.rs, B * d.s_rs);
-    ALLOC(d.oc, B * d.s_oc); ALLOC(d.info, (size_t)B * 8); ALLOC(d.prof, (size_t)B * 16); ALLOC(bt->stage, (size_t)B * l.so);
+    ALLOC(d.oc, B * d.s_oc); ALLOC(d.info, (size_t)B * 8); ALLOC(d.prof, (size_t)B * 16);
 #undef ALLOC
-    bt->bytes = (long long)tot;
-    if (hipEventCreate(&bt->e0) != hipSuccess || hipEventCreate(&bt->e1) != hipSuccess) { err = "hipEventCreate failed"; qfree_dev(bt); delete bt; return -2; }
+    if (bt->stage.reserve((size_t)B * l.so, stream) != hipSuccess) { err = "obca_quad_batch_create: hipMalloc failed"; free_dev(bt); delete bt; return -2; }
+    bt->bytes = (long long)(tot + bt->stage.cap * sizeof(double));
+    if (hipEventCreate(&bt->e0) != hipSuccess || hipEventCreate(&bt->e1) != hipSuccess) { err = "hipEventCreate failed"; free_dev(bt); delete bt; return -2; }
     *out = bt;
     return 0;
 }
@@ -1060,7 +1081,7 @@ static int quad_upload_range(obca_quad_batch *bt, const QuadIn &in, int lo, int 
     if (n < 1 || n > bt->cap) { bt->err = "obca_quad_batch_upload: more instances than the batch was created for"; return -1; }
     bt->B = n; bt->solved = 0;
     const int N1 = bt->N + 1; const QDevBufs &d = bt->d;
-    if (pinned_reserve(bt->err, &bt->h_prob, &bt->hcap_prob, (size_t)bt->cap * d.s_prob)) return -2;
+    if (bt->h_prob.reserve(bt->err, (size_t)bt->cap * d.s_prob)) return -2;
     for (int i = 0; i < n; i++) {
         const size_t g = (size_t)lo + i;
         double *p = bt->h_prob + (size_t)i * d.s_prob;
@@ -1071,7 +1092,7 @@ static int quad_upload_range(obca_quad_batch *bt, const QuadIn &in, int lo, int 
         memcpy(p + QPH_SIZE, in.xWS + (size_t)QX * N1 * g, sizeof(double) * QX * N1);
     }
     use_device(bt->device);
-    QCHK(bt, hipMemcpyAsync(d.prob, bt->h_prob, (size_t)n * d.s_prob * sizeof(double), hipMemcpyHostToDevice, bt->stream));
+    HIPCHK(bt, hipMemcpyAsync(d.prob, bt->h_prob, (size_t)n * d.s_prob * sizeof(double), hipMemcpyHostToDevice, bt->stream));
     bt->uploaded = 1;
     return 0;
 }
@@ -1081,12 +1102,12 @@ static int quad_download_range(obca_quad_batch *bt, const QuadOut &o, int lo) {
     quad::QLay l; quad::q_make_layout(N, l);
     use_device(bt->device);
     const size_t W = (size_t)l.so;                          // outputs are a prefix of the iterate: x, u, t, lam, s
-    if (pinned_reserve(bt->err, &bt->h_z, &bt->hcap_z, (size_t)bt->cap * W) || pinned_reserve(bt->err, &bt->h_info, &bt->hcap_info, (size_t)bt->cap * 8)) return -2;
+    if (bt->h_z.reserve(bt->err, (size_t)bt->cap * W) || bt->h_info.reserve(bt->err, (size_t)bt->cap * 8)) return -2;
     hipLaunchKernelGGL(obca_gather_rows_kernel, dim3(B, (unsigned)((W + 1023) / 1024)), dim3(256), 0, bt->stream, bt->stage, W, (const double *)d.z, d.s_z);
-    QCHK(bt, hipGetLastError());
-    QCHK(bt, hipMemcpyAsync(bt->h_z, bt->stage, (size_t)B * W * sizeof(double), hipMemcpyDeviceToHost, bt->stream));
-    QCHK(bt, hipMemcpyAsync(bt->h_info, d.info, (size_t)B * 8 * sizeof(double), hipMemcpyDeviceToHost, bt->stream));
-    QCHK(bt, hipStreamSynchronize(bt->stream));
+    HIPCHK(bt, hipGetLastError());
+    HIPCHK(bt, hipMemcpyAsync(bt->h_z, bt->stage, (size_t)B * W * sizeof(double), hipMemcpyDeviceToHost, bt->stream));
+    HIPCHK(bt, hipMemcpyAsync(bt->h_info, d.info, (size_t)B * 8 * sizeof(double), hipMemcpyDeviceToHost, bt->stream));
+    HIPCHK(bt, hipStreamSynchronize(bt->stream));
     for (int i = 0; i < B; i++) {
         const size_t g = (size_t)lo + i;
         const double *z = bt->h_z + (size_t)i * W;
@@ -1117,26 +1138,18 @@ int obca_quadcopter_reference_opts(obca_opts *o) {
 }
 int obca_quad_batch_create(obca_ctx *ctx, int B, int N, obca_quad_batch **out) {
     if (!ctx || !out) return -1;
-    return quad_batch_create_on(ctx, ctx->device, ctx->stream, B, N, out, ctx->err);
+    return batch_create_on(ctx, ctx->device, ctx->stream, B, N, out, ctx->err);
 }
 int obca_quad_batch_destroy(obca_quad_batch *bt) {
     if (!bt) return -1;
-    use_device(bt->device); qfree_dev(bt); val_release(bt->val); (void)hipEventDestroy(bt->e0); (void)hipEventDestroy(bt->e1);
-    double **hs[] = {&bt->h_prob, &bt->h_z, &bt->h_info};
-    for (auto p : hs) if (*p) (void)hipHostFree(*p);
+    use_device(bt->device);
+    free_dev(bt); core_release(bt); bt->h_z.release();
     delete bt; return 0;
 }
 #ifdef OBCA_PROFILE
-int obca_quad_batch_debug_phase_cycles(obca_quad_batch *bt, double *out /* B x 16 */) {   
-    if (!bt || !out) return -1;
-    use_device(bt->device);
-    if (hipStreamSynchronize(bt->stream) != hipSuccess ||
-        hipMemcpy(out, bt->d.prof, (size_t)bt->B * 16 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { bt->ctx->err = "obca_quad_batch_debug_phase_cycles: copy failed";
-        return -2; }
-    return 0;
-}
+int obca_quad_batch_debug_phase_cycles(obca_quad_batch *bt, double *out) { return bt ? core_phase_cycles(bt, bt->d.prof, out, "obca_quad_batch_debug_phase_cycles: copy failed") : -1; }
 #endif
-int obca_quad_batch_scratch_bytes(const obca_quad_batch *bt, long long *bytes) { if (!bt || !bytes) return -1; *bytes = bt->bytes; return 0; }
+int obca_quad_batch_scratch_bytes(const obca_quad_batch *bt, long long *bytes) { return core_scratch_bytes(bt, bytes); }
 int obca_quad_batch_upload(obca_quad_batch *bt, const double *Ts, double R, const double *x0, const double *xF, const double *ob,
                            const double *xWS, const double *timeWS, int dual_ws, int dist) {
     if (!bt) return -1;
@@ -1144,7 +1157,7 @@ int obca_quad_batch_upload(obca_quad_batch *bt, const double *Ts, double R, cons
     QuadIn in = {Ts, R, x0, xF, ob, xWS, timeWS, dual_ws, dist};
     int rc = quad_upload_range(bt, in, 0, bt->cap);
     if (!rc && hipStreamSynchronize(bt->stream) != hipSuccess) { bt->err = "obca_quad_batch_upload: stream sync failed"; rc = -2; }
-    return qfin(bt, rc);
+    return fin(bt, rc);
 }
 }  // extern "C"
 static int quad_solve(obca_quad_batch *bt, const obca_opts *opts) {
@@ -1155,56 +1168,45 @@ static int quad_solve(obca_quad_batch *bt, const obca_opts *opts) {
     if (o.recalc_y != 0) { bt->err = "quadcopter solve: recalc_y is a switch of the parking kernels only (the reference's quadcopter call sets recalc_y = \"no\", QuadcopterSignedDist.jl:29); the quadcopter kernel would ignore it -- refusing instead"; return -1; }
     Opts ko; memcpy(&ko, &o, sizeof ko);
     use_device(bt->device);
-    QCHK(bt, hipEventRecord(bt->e0, bt->stream));
+    HIPCHK(bt, hipEventRecord(bt->e0, bt->stream));
     hipLaunchKernelGGL(obca_quad_ipm_kernel, dim3(bt->B), dim3(QNT), (size_t)(bt->N + 2) * (QS + QU) * sizeof(double), bt->stream, bt->B, bt->N, bt->d, ko, o.max_soc, o.lsq_init != 0, o.obj_scaling != 0);
-    QCHK(bt, hipGetLastError());
-    QCHK(bt, hipEventRecord(bt->e1, bt->stream));
+    HIPCHK(bt, hipGetLastError());
+    HIPCHK(bt, hipEventRecord(bt->e1, bt->stream));
     bt->solved = 1;
     return 0;
 }
 // the quadcopter check of the batch's instances: resident (x == nullptr: the last solution in d.z) or a caller's trajectory (host arrays of the whole call, instance lo + i),
-// which travels up densely packed as [ x | u | timeScale (N + 1) | lambda ] per instance.  Only QV_OUT doubles per instance come back.  Synchronises the batch's stream.
+// which travels up densely packed as [ x | u | timeScale (N + 1) | lambda ] per instance.  Only QV_OUT doubles per instance come back.
 static int quad_validate_range(obca_quad_batch *bt, const double *x, const double *u, const double *ts, const double *lam, double tol, int lo, int *ok, double *viol) {
     const int B = bt->B, N = bt->N, N1 = N + 1; const QDevBufs &d = bt->d;
     const bool host = x != nullptr;
     const size_t nx = (size_t)QX * N1, nu = (size_t)QU * N, nl = (size_t)QL * QOB * N1, W = nx + nu + N1 + nl;
-    use_device(bt->device);
-    if (int rc = val_reserve(bt->err, bt->val, host ? (size_t)bt->cap * W : 1, (size_t)bt->cap * QV_OUT, bt->stream)) return rc;
-    ValBufs &v = bt->val;
-    if (host) {
-        for (int i = 0; i < B; i++) {
-            double *a = v.h_in + (size_t)i * W; const size_t g = (size_t)lo + i;
-            memcpy(a, x + g * nx, sizeof(double) * nx); memcpy(a + nx, u + g * nu, sizeof(double) * nu);
-            memcpy(a + nx + nu, ts + g * N1, sizeof(double) * N1); memcpy(a + nx + nu + N1, lam + g * nl, sizeof(double) * nl);
-        }
-        QCHK(bt, hipMemcpyAsync(v.d_in, v.h_in, (size_t)B * W * sizeof(double), hipMemcpyHostToDevice, bt->stream));
-    }
     quad::QLay l; quad::q_make_layout(N, l);
-    QCHK(bt, hipEventRecord(v.e0, bt->stream));
-    if (host) hipLaunchKernelGGL(obca_validate_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)v.d_in, W, 0, (int)nx, (int)(nx + nu), 1, (int)(nx + nu + N1), tol, v.d_out);
-    else hipLaunchKernelGGL(obca_validate_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)d.z, d.s_z, l.x, l.u, l.t, 0, l.lam, tol, v.d_out);
-    QCHK(bt, hipGetLastError());
-    QCHK(bt, hipEventRecord(v.e1, bt->stream));
-    v.timed = 1;
-    QCHK(bt, hipMemcpyAsync(v.h_out, v.d_out, (size_t)B * QV_OUT * sizeof(double), hipMemcpyDeviceToHost, bt->stream));
-    QCHK(bt, hipStreamSynchronize(bt->stream));
-    for (int i = 0; i < B; i++) {
-        const double *o = v.h_out + (size_t)i * QV_OUT; const size_t g = (size_t)lo + i;
+    return run_validate(bt, host ? W : 0, host, QV_OUT, [&](int i, double *a) {
+        const size_t g = (size_t)lo + i;
+        memcpy(a, x + g * nx, sizeof(double) * nx); memcpy(a + nx, u + g * nu, sizeof(double) * nu);
+        memcpy(a + nx + nu, ts + g * N1, sizeof(double) * N1); memcpy(a + nx + nu + N1, lam + g * nl, sizeof(double) * nl);
+    }, [&] {
+        if (host) hipLaunchKernelGGL(obca_validate_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)bt->val.d_in, W, 0, (int)nx, (int)(nx + nu), 1, (int)(nx + nu + N1), tol, bt->val.d_out);
+        else hipLaunchKernelGGL(obca_validate_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)d.z, d.s_z, l.x, l.u, l.t, 0, l.lam, tol, bt->val.d_out);
+    }, [&](int i, const double *o) {
+        const size_t g = (size_t)lo + i;
         if (viol) memcpy(viol + g * QV_NCLS, o, sizeof(double) * QV_NCLS);
         if (ok) ok[g] = o[QV_NCLS] != 0.0;
-    }
-    return 0;
+    });
 }
+// instances (one wavefront each) resident per CU, as OBCA_RESIDENT_PER_CU for the parking kernel: what pick_chunk sizes a quadcopter chunk by
+static const int QUAD_RESIDENT_PER_CU = (QNT == 64 ? 4 : 2) * OBCA_QUAD_WAVES_PER_EU;
 static int quadcopter_call(obca_ctx *ctx, int B, int N, const QuadIn &in, const obca_opts *opts, const QuadOut &out) {
     if (!ctx) return -1;
     if (B < 1 || N < 2 || N > OBCA_QUAD_NMAX) { ctx->err = "need B>=1, 2<=N<=OBCA_QUAD_NMAX"; return -1; }
     if (!in.Ts || !in.x0 || !in.xF || !in.ob || !in.xWS || !in.timeWS) { ctx->err = "NULL argument"; return -1; }
-    const int chunk = pick_chunk(ctx, B, (QNT == 64 ? 4 : 2) * OBCA_QUAD_WAVES_PER_EU);
+    const int chunk = pick_chunk(ctx, B, QUAD_RESIDENT_PER_CU);
     return run_chunks(ctx, B, chunk, [&](Slot &s, int lo, int n, std::string &err) -> int {
-        if (s.qb && (s.qb->cap < n || s.qb->N != N)) { obca_quad_batch_destroy(s.qb); s.qb = nullptr; }
-        if (!s.qb) { int rc = quad_batch_create_on(ctx, s.device, s.stream, std::min(chunk, B), N, &s.qb, err); if (rc) return rc; }
+        int rc = slot_batch(ctx, s, s.qb, obca_quad_batch_destroy, n, std::min(chunk, B), N, err);
+        if (rc) return rc;
         obca_quad_batch *bt = s.qb;
-        int rc = quad_upload_range(bt, in, lo, n);
+        rc = quad_upload_range(bt, in, lo, n);
         if (!rc) rc = quad_solve(bt, opts);
         if (!rc) rc = quad_download_range(bt, out, lo);
         if (rc) err = bt->err;
@@ -1212,29 +1214,19 @@ static int quadcopter_call(obca_ctx *ctx, int B, int N, const QuadIn &in, const 
     });
 }
 extern "C" {
-int obca_quad_batch_solve(obca_quad_batch *bt, const obca_opts *opts) { if (!bt) return -1; return qfin(bt, quad_solve(bt, opts)); }
-int obca_quad_batch_sync(obca_quad_batch *bt) {
-    if (!bt) return -1;
-    use_device(bt->device);
-    if (hipStreamSynchronize(bt->stream) != hipSuccess) { bt->ctx->err = "obca_quad_batch_sync: hipStreamSynchronize failed"; return -2; }
-    return 0;
-}
+int obca_quad_batch_solve(obca_quad_batch *bt, const obca_opts *opts) { if (!bt) return -1; return fin(bt, quad_solve(bt, opts)); }
+int obca_quad_batch_sync(obca_quad_batch *bt) { return core_sync(bt, "obca_quad_batch_sync: hipStreamSynchronize failed"); }
 int obca_quad_batch_kernel_ms(obca_quad_batch *bt, float *ipm_ms) {
     if (!bt || !ipm_ms) return -1;
-    if (hipEventElapsedTime(ipm_ms, bt->e0, bt->e1) != hipSuccess) { bt->ctx->err = "obca_quad_batch_kernel_ms: events not ready"; return -2; }
-    return 0;
+    return core_elapsed_ms(bt, true, bt->e0, bt->e1, ipm_ms, "obca_quad_batch_kernel_ms: events not ready");
 }
 int obca_quad_batch_validate(obca_quad_batch *bt, double tol, int *ok, double *viol) {
     if (!bt) return -1;
     if (!ok) { bt->ctx->err = "obca_quad_batch_validate: NULL argument"; return -1; }
     if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_quad_batch_validate: nothing has been solved since the last upload"; return -1; }
-    return qfin(bt, quad_validate_range(bt, nullptr, nullptr, nullptr, nullptr, tol > 0 ? tol : 1e-3, 0, ok, viol));
+    return fin(bt, quad_validate_range(bt, nullptr, nullptr, nullptr, nullptr, tol > 0 ? tol : 1e-3, 0, ok, viol));
 }
-int obca_quad_batch_validate_ms(obca_quad_batch *bt, float *ms) {
-    if (!bt || !ms) return -1;
-    if (val_ms(bt->val, ms)) { bt->ctx->err = "obca_quad_batch_validate_ms: no validate call has run on this batch"; return -2; }
-    return 0;
-}
+int obca_quad_batch_validate_ms(obca_quad_batch *bt, float *ms) { return core_validate_ms(bt, ms, "obca_quad_batch_validate_ms: no validate call has run on this batch"); }
 int obca_quadcopter_constr_satisfaction_batch(obca_ctx *ctx, int B, int N, const double *Ts, double R, const double *x0, const double *xF, const double *ob,
                                               const double *x, const double *u, const double *timeScale, const double *lambda, double tol, int *ok, double *viol) {
     if (!ctx) return -1;
@@ -1243,12 +1235,12 @@ int obca_quadcopter_constr_satisfaction_batch(obca_ctx *ctx, int B, int N, const
     const std::vector<double> one((size_t)B, 1.0);                 // timeWS of a solve: no check reads it
     const QuadIn in = {Ts, R, x0, xF, ob, x, one.data(), 0, 0};
     const double tl = tol > 0 ? tol : 1e-3;
-    const int chunk = pick_chunk(ctx, B, (QNT == 64 ? 4 : 2) * OBCA_QUAD_WAVES_PER_EU);
+    const int chunk = pick_chunk(ctx, B, QUAD_RESIDENT_PER_CU);
     return run_chunks(ctx, B, chunk, [&](Slot &s, int lo, int cnt, std::string &err) -> int {
-        if (s.qb && (s.qb->cap < cnt || s.qb->N != N)) { obca_quad_batch_destroy(s.qb); s.qb = nullptr; }
-        if (!s.qb) { int rc = quad_batch_create_on(ctx, s.device, s.stream, std::min(chunk, B), N, &s.qb, err); if (rc) return rc; }
+        int rc = slot_batch(ctx, s, s.qb, obca_quad_batch_destroy, cnt, std::min(chunk, B), N, err);
+        if (rc) return rc;
         obca_quad_batch *bt = s.qb;
-        int rc = quad_upload_range(bt, in, lo, cnt);
+        rc = quad_upload_range(bt, in, lo, cnt);
         if (!rc) rc = quad_validate_range(bt, x, u, timeScale, lambda, tl, lo, ok, viol);
         if (rc) err = bt->err;
         return rc;
@@ -1257,7 +1249,7 @@ int obca_quadcopter_constr_satisfaction_batch(obca_ctx *ctx, int B, int N, const
 int obca_quad_batch_download(obca_quad_batch *bt, double *xp, double *up, double *ts, int *exitflag, double *lp, double *slp, double *info) {
     if (!bt) return -1;
     QuadOut o = {xp, up, ts, exitflag, lp, slp, info};
-    return qfin(bt, quad_download_range(bt, o, 0));
+    return fin(bt, quad_download_range(bt, o, 0));
 }
 int obca_quadcopter_signed_dist_batch(obca_ctx *ctx, int B, int N, const double *Ts, double R, const double *x0, const double *xF,
                                       const double *ob, const double *xWS, const double *uWS, const double *timeWS, int dual_ws,
