@@ -221,6 +221,23 @@ int obca_quad_batch_upload(obca_quad_batch *bt, const double *Ts, double R, cons
                            const double *xWS, const double *timeWS, int dual_ws, int dist /* 1: QuadcopterDist formulation */);
 int obca_quad_batch_solve(obca_quad_batch *bt, const obca_opts *opts);   /* asynchronous on the context's stream */
 int obca_quad_batch_sync(obca_quad_batch *bt);
+/* receding-horizon restart of a resident quadcopter batch (not in the reference; the text is obca_amd/csrc/obca_quad_shift.h): the problem of the NEXT
+ * obca_quad_batch_solve is written from the LAST solution, entirely on the device -- nothing but the two optional arrays crosses the bus.  Per instance:
+ *   last exit flag 1 or 2: stage k = 0..N of the warm start becomes stage min(k + shift, N) of the solution (all 12 states, not only the positions; the tail repeats the
+ *                          terminal stage), timeWS becomes the solution's t, and dual_ws becomes 1: the next solve starts lambda at the closed-form point-to-box duals of the
+ *                          shifted positions, the inputs at the hover speed and the slacks at 1 like every quadcopter solve (u, lambda and the slack of the last solution are
+ *                          NOT carried: that would need another starting point inside the kernel);
+ *   last exit flag 0:      warm start, timeWS and dual_ws stay what was uploaded (or shifted last); nothing is read from the failed iterate, which may be non-finite;
+ *   every instance:        x0 becomes x0_new (12 x B host, the measured state) or, if NULL, stage `shift` of the solution (exit flag 0 and NULL: x0 stays);
+ *                          xF becomes xF_new (12 x B host, a moving goal) if not NULL, and the tail stages k + shift > N of a shifted warm start then hold xF_new.
+ * Ts, R, the boxes and the formulation stay.  Returns -1 if nothing is uploaded, if shift is outside 0..N, if nothing has been solved since the last upload or shift, or if
+ * x0_new / xF_new hold a non-finite entry; -2 on a device error.  Synchronises the batch's stream; afterwards obca_quad_batch_validate refuses until the next solve.
+ * A restart pays with small barrier and push values (mu_init = bound_push = bound_frac = 1e-4 on top of either option set): measured on the CPU checker at N = 60, shift 4,
+ * 108 / 108 / 107 / 70 -> 43 / 46 / 44 / 25 iterations (throughput options) and 72 / 73 / 75 / 77 -> 60 / 50 / 57 / 60 (obca_quadcopter_reference_opts); with the cold values
+ * of the three options it is often slower than a cold solve, and at N = 20 one instance went from 61 to 77 iterations.  On one MI355X (tools/quad_mpc_rate.py,
+ * profiles/quad_mpc_restart.json; N = 60, B = 256, shift 4): interior-point kernel 36.4 -> 22.0 ms (throughput options), 36.6 -> 25.2 ms (reference switches); this call 0.02-0.06 ms
+ * against 1.0 ms for download + host shift + upload.  In a disturbed closed loop the reference switches kept every instance solvable, the throughput options lost 1-6 % per step. */
+int obca_quad_batch_shift_warm_start(obca_quad_batch *bt, int shift, const double *x0_new /* 12 x B or NULL */, const double *xF_new /* 12 x B or NULL */);
 int obca_quad_batch_kernel_ms(obca_quad_batch *bt, float *ipm_ms);
 int obca_quad_batch_download(obca_quad_batch *bt, double *xp, double *up, double *timeScale, int *exitflag, double *lp, double *slack,
                              double *info);

@@ -262,4 +262,94 @@ QuadcopterSignedDist(x0, xF, N, Ts, R, ob1, ob2, ob3, ob4, ob5, xWS, uWS, timeWS
 QuadcopterDist(x0, xF, N, Ts, R, ob1, ob2, ob3, ob4, ob5, xWS, uWS, timeWS; dual_ws::Bool=true, opts=quadcopter_ipopt_opts()) =
     _quad_one(x0, xF, N, Ts, R, (ob1, ob2, ob3, ob4, ob5), xWS, timeWS, dual_ws, true, opts)
 
+# ---------------------------------------------------------------- device-resident quadcopter batch: upload once, solve / shift / solve ... (receding horizon)
+"options for a solve that starts from `shift_warm_start!`: the quadcopter defaults (reference=true: `quadcopter_ipopt_opts()`) with mu_init = bound_push = bound_frac = 1e-4"
+function quad_warm_restart_opts(; reference::Bool=false)
+    o = Opts()
+    sym_ok = reference ? ccall((:obca_quadcopter_reference_opts, LIB), Cint, (Ref{Opts},), o) : ccall((:obca_quadcopter_default_opts, LIB), Cint, (Ref{Opts},), o)
+    sym_ok == 0 || error("obca_quadcopter_*_opts failed")
+    o.mu_init = 1e-4; o.bound_push = 1e-4; o.bound_frac = 1e-4
+    return o
+end
+
+"""
+    QuadBatch(B, N)
+
+B quadcopter instances of horizon N resident on the GPU (obca_quad_batch_* of include/obca_hip.h): `upload!`, `solve!`, `sync!`, `shift_warm_start!`, `download`, `validate`,
+`destroy!`.  The iterate stays on the device between solves: a receding-horizon loop moves 12 numbers per instance up (the measured state) and whatever it downloads.
+"""
+mutable struct QuadBatch
+    h::Ptr{Cvoid}
+    B::Int
+    N::Int
+    c::Context
+end
+function QuadBatch(B::Integer, N::Integer; context::Context=ctx())
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = ccall((:obca_quad_batch_create, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Ref{Ptr{Cvoid}}), context.h, B, N, r)
+    rc == 0 || error("obca_quad_batch_create failed: " * lasterr(context))
+    b = QuadBatch(r[], B, N, context)
+    finalizer(destroy!, b)
+    return b
+end
+function destroy!(b::QuadBatch)
+    b.h == C_NULL || ccall((:obca_quad_batch_destroy, LIB), Cint, (Ptr{Cvoid},), b.h)
+    b.h = C_NULL
+    return nothing
+end
+_qcheck(b::QuadBatch, rc, what) = rc == 0 || error(what * " failed: " * lasterr(b.c))
+
+"x0, xF 12xB; Ts, timeWS vectors of length B; ob 6x5xB; xWS 12x(N+1)xB (the layouts of `QuadcopterSignedDist_batch`)"
+function upload!(b::QuadBatch, x0, xF, Ts, R, ob, xWS, timeWS; dual_ws::Bool=true, dist::Bool=false)
+    size(xWS) == (12, b.N + 1, b.B) || error("xWS must be 12 x (N+1) x B")
+    _qcheck(b, ccall((:obca_quad_batch_upload, LIB), Cint,
+                     (Ptr{Cvoid}, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint),
+                     b.h, f64(vec(Ts)), Float64(R), f64(x0), f64(xF), f64(ob), f64(xWS), f64(vec(timeWS)), dual_ws ? 1 : 0, dist ? 1 : 0), "obca_quad_batch_upload")
+    return b
+end
+"queue a solve on the context's stream (asynchronous; `sync!` waits).  opts=nothing: the throughput defaults; after `shift_warm_start!`: `quad_warm_restart_opts()`"
+function solve!(b::QuadBatch; opts=nothing)
+    _qcheck(b, GC.@preserve(opts, ccall((:obca_quad_batch_solve, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), b.h, optsptr(opts))), "obca_quad_batch_solve")
+    return b
+end
+sync!(b::QuadBatch) = (_qcheck(b, ccall((:obca_quad_batch_sync, LIB), Cint, (Ptr{Cvoid},), b.h), "obca_quad_batch_sync"); b)
+"""
+    shift_warm_start!(b, shift; x0_new=nothing, xF_new=nothing)
+
+Receding-horizon restart on the device (obca_quad_batch_shift_warm_start): the next `solve!` starts from the last solution advanced by `shift` stages, from `x0_new` (12xB, the
+measured state; nothing: stage `shift` of the solution) towards `xF_new` (12xB, a moving goal; nothing: unchanged).  A failed instance keeps its uploaded warm start.
+"""
+function shift_warm_start!(b::QuadBatch, shift::Integer; x0_new=nothing, xF_new=nothing)
+    a0 = x0_new === nothing ? C_NULL : f64(x0_new); aF = xF_new === nothing ? C_NULL : f64(xF_new)
+    (x0_new === nothing || length(a0) == 12 * b.B) && (xF_new === nothing || length(aF) == 12 * b.B) || error("x0_new / xF_new must be 12 x B")
+    _qcheck(b, ccall((:obca_quad_batch_shift_warm_start, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}), b.h, shift, a0, aF), "obca_quad_batch_shift_warm_start")
+    return b
+end
+"(xp 12x(N+1)xB, up 4xNxB, timeScale (N+1)xB, exitflag B, lp 30x(N+1)xB, slack 5x(N+1)xB, info 8xB) of the last solve; synchronises"
+function download(b::QuadBatch)
+    B, N = b.B, b.N
+    xp = zeros(12, N + 1, B); up = zeros(4, N, B); ts = zeros(N + 1, B); ef = zeros(Cint, B); lp = zeros(30, N + 1, B); sl = zeros(5, N + 1, B); info = zeros(8, B)
+    _qcheck(b, ccall((:obca_quad_batch_download, LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                     b.h, xp, up, ts, ef, lp, sl, info), "obca_quad_batch_download")
+    return xp, up, ts, ef, lp, sl, info
+end
+"constrSatisfaction on the last solution, on the device: (ok B, viol 9xB); refused between `shift_warm_start!` and the next `solve!`"
+function validate(b::QuadBatch; tol=1e-3)
+    ok = zeros(Cint, b.B); viol = zeros(9, b.B)
+    _qcheck(b, ccall((:obca_quad_batch_validate, LIB), Cint, (Ptr{Cvoid}, Cdouble, Ptr{Cint}, Ptr{Cdouble}), b.h, tol, ok, viol), "obca_quad_batch_validate")
+    return ok, viol
+end
+
+"""
+    batch_shift_warm_start!(h, shift; x0_new=nothing)
+
+The parking restart (obca_batch_shift_warm_start) for a caller that holds an `obca_batch` handle `h` (a `Ptr{Cvoid}` from `obca_batch_create`): the uploaded warm start becomes
+the last solution advanced by `shift` stages -- x, u, lambda, mu and the tracking reference --, x0 becomes `x0_new` (4xB) or stage `shift` of the solution.
+"""
+function batch_shift_warm_start!(h::Ptr{Cvoid}, shift::Integer; x0_new=nothing)
+    rc = ccall((:obca_batch_shift_warm_start, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}), h, shift, x0_new === nothing ? C_NULL : f64(x0_new))
+    rc == 0 || error("obca_batch_shift_warm_start failed: " * lasterr(ctx()))
+    return nothing
+end
+
 end # module

@@ -84,7 +84,7 @@ EXPORTS = ["obca_create", "obca_create_multi", "obca_device_count", "obca_visibl
            "obca_batch_scratch_bytes", "obca_batch_validate", "obca_batch_validate_ms", "obca_parking_constraints_batch",
            "obca_quad_batch_validate", "obca_quad_batch_validate_ms", "obca_quadcopter_constr_satisfaction_batch",
            "obca_quadcopter_default_opts", "obca_quadcopter_reference_opts", "obca_quadcopter_signed_dist_batch", "obca_quadcopter_dist_batch", "obca_quad_batch_create", "obca_quad_batch_destroy",
-           "obca_quad_batch_upload", "obca_quad_batch_solve", "obca_quad_batch_sync", "obca_quad_batch_kernel_ms",
+           "obca_quad_batch_upload", "obca_quad_batch_solve", "obca_quad_batch_sync", "obca_quad_batch_shift_warm_start", "obca_quad_batch_kernel_ms",
            "obca_quad_batch_download", "obca_quad_batch_scratch_bytes"]
 
 
@@ -546,6 +546,28 @@ def quadcopter_ipopt_opts():
     return o
 
 
+def quad_warm_restart_opts(reference=False):
+    """options for a quadcopter solve that starts from QuadBatch.shift_warm_start: the quadcopter defaults (reference=True: the reference's IPOPT switches,
+    quadcopter_ipopt_opts()) with a small initial barrier and bound push, mu_init = bound_push = bound_frac = 1e-4, so that the interior point does not first walk
+    away from the previous solution.  What the restart buys, measured on the CPU checker under oracle/ (states advanced by `shift`, tail = the terminal
+    stage, timeWS = the previous t, closed-form duals) on scenarios.make_quad_batch instances (the device: tools/quad_mpc_rate.py, profiles/quad_mpc_restart.json):
+
+        N, shift, formulation           option set        iterations cold -> shifted restart            ratio
+        60, 4, SignedDist (4 inst.)     throughput        108, 108, 107, 70 -> 43, 46, 44, 25           0.40
+        60, 4, SignedDist (4 inst.)     reference         72, 73, 75, 77 -> 60, 50, 57, 60              0.76
+        30, 3, SignedDist (6 inst.)     throughput / ref  sums 490 -> 285 / 713 -> 350                  0.58 / 0.49
+        30, 3, Dist (6 inst.)           throughput / ref  sums 349 -> 301 / 458 -> 275                  0.86 / 0.60
+
+    Every restart ended with exit flag 1 (shift = 0 and shift = N at N = 33 and 60 included); a 12-step closed loop at N = 60 (shift 2, +-0.02 disturbances on position and
+    velocity per step) stayed solvable at 25-66 iterations per step against 97 cold.  The restart is not uniformly cheaper: at N = 20 one instance went from 61 to 77
+    iterations, and with the COLD values of the three options a restart is often slower than a cold solve -- use these options with it.  In a closed loop with disturbed
+    measured states (one MI355X, 20 steps, +-0.02 per step) reference=True kept every instance solvable; the throughput set lost 1-6 % of the instances of a step, and a lost
+    instance runs into max_iter = 3 000: prefer reference=True there and cap max_iter."""
+    o = quadcopter_ipopt_opts() if reference else quadcopter_default_opts()
+    o.mu_init = 1e-4; o.bound_push = 1e-4; o.bound_frac = 1e-4
+    return o
+
+
 class QuadBatch(_DeviceBatch):
     """Device-resident batch of quadcopter signed-distance NLPs (obca_quad_batch_* in include/obca_hip.h)."""
     _c = "obca_quad_batch"
@@ -558,6 +580,14 @@ class QuadBatch(_DeviceBatch):
         keep = [_d(Tsv), _d(np.reshape(x0, (B, 12))), _d(np.reshape(xF, (B, 12))), _d(obv), _d(xw), _d(tw)]
         p = [k[1] for k in keep]
         self._call("upload", p[0], C.c_double(R), p[1], p[2], p[3], p[4], p[5], C.c_int(int(bool(dual_ws))), C.c_int(int(bool(dist))))
+
+    def shift_warm_start(self, shift, x0_new=None, xF_new=None):
+        """receding-horizon restart on the device (obca_quad_batch_shift_warm_start): the next solve starts from the last solution advanced by `shift` stages -- all 12 states,
+        timeWS = the last t, closed-form duals --, from x0_new (B,12; the measured state; None: stage `shift` of the solution) towards xF_new (B,12; a moving goal; None: unchanged).
+        An instance whose last solve failed keeps its uploaded warm start.  Solve with quad_warm_restart_opts()."""
+        k0 = _d(np.reshape(x0_new, (self.B, 12))) if x0_new is not None else (None, None)
+        kF = _d(np.reshape(xF_new, (self.B, 12))) if xF_new is not None else (None, None)
+        self._call("shift_warm_start", C.c_int(int(shift)), k0[1], kF[1])
 
     def kernel_ms(self):
         a = C.c_float(0)

@@ -6,6 +6,8 @@
 //   obca_quad_ipm_kernel    : the same for the quadcopter NLP (obca_quad_solver.h).
 //   obca_dualws_kernel      : one lane per (instance, stage, obstacle) convex sub-problem of DualMultWS (obca_model.h).
 //   obca_validate_*_kernel  : one wavefront per instance, the a-posteriori feasibility classes of a solution or of a caller's trajectory (obca_validate.h).
+//   obca_shift_kernel, obca_quad_shift_kernel : receding-horizon restarts, one workgroup per instance: the warm start of the next solve from the last solution
+//                             (parking: below; quadcopter: obca_quad_shift.h).
 // Memory (per instance, fp64, all in HBM; sizes for N=80, 3 obstacles / 5 rows in brackets):
 //   prob  header+rx,ry,ryaw   [495]      z, zn  primal-dual iterate and the line search's
 //   trial point (they swap) [6797 each]      d  stage part of the search direction [~650 used]
@@ -23,6 +25,7 @@
 #include "obca_solver.h"
 #include "obca_quad_solver.h"
 #include "obca_validate.h"
+#include "obca_quad_shift.h"
 #include "../../include/obca_hip.h"
 
 using namespace obca;
@@ -254,6 +257,15 @@ __global__ __launch_bounds__(QNT, OBCA_QUAD_WAVES_PER_EU) void obca_quad_ipm_ker
     __syncthreads();
     if (threadIdx.x < 16) b.prof[(size_t)inst * 16 + threadIdx.x] = quad::gq_sh.prof[threadIdx.x];
 #endif
+}
+
+// receding-horizon restart of the quadcopter batch (obca_quad_shift.h): one wavefront per instance rewrites the warm start, TWS, DWS, X0 (and XF) words of its problem
+// record from the resident solution; x0_new / xF_new: 12 x B on the device, or NULL
+__global__ __launch_bounds__(QNT) void obca_quad_shift_kernel(int B, int N, int shift, QDevBufs b, const double *x0_new, const double *xF_new) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    quad::quad_shift_instance(N, shift, b.prob + (size_t)inst * b.s_prob, b.z + (size_t)inst * b.s_z, b.info + (size_t)inst * 8,
+                              x0_new ? x0_new + (size_t)inst * QX : nullptr, xF_new ? xF_new + (size_t)inst * QX : nullptr);
 }
 
 // a-posteriori checks (obca_validate.h): one wavefront per instance; the point is read in the solver's layout (resident: the last solution; host-pointer
@@ -1215,6 +1227,30 @@ static int quadcopter_call(obca_ctx *ctx, int B, int N, const QuadIn &in, const 
 }
 extern "C" {
 int obca_quad_batch_solve(obca_quad_batch *bt, const obca_opts *opts) { if (!bt) return -1; return fin(bt, quad_solve(bt, opts)); }
+int obca_quad_batch_shift_warm_start(obca_quad_batch *bt, int shift, const double *x0_new, const double *xF_new) {
+    if (!bt) return -1;
+    obca_ctx *ctx = bt->ctx;
+    if (!bt->uploaded) { ctx->err = "obca_quad_batch_shift_warm_start: nothing uploaded"; return -1; }
+    if (shift < 0 || shift > bt->N) { ctx->err = "obca_quad_batch_shift_warm_start: shift out of range 0..N"; return -1; }
+    if (!bt->solved) { ctx->err = "obca_quad_batch_shift_warm_start: nothing has been solved since the last upload or shift"; return -1; }
+    const size_t n = (size_t)bt->B * QX;
+    for (const double *a : {x0_new, xF_new})
+        for (size_t i = 0; a && i < n; i++)
+            if (!(a[i] - a[i] == 0.0)) { ctx->err = std::string("obca_quad_batch_shift_warm_start: non-finite entry in ") + (a == x0_new ? "x0_new" : "xF_new"); return -1; }
+    use_device(bt->device);
+    const double *dx0 = nullptr, *dxF = nullptr;
+    if (x0_new || xF_new) {   // staged through the pinned problem buffer and the (idle) device staging buffer of the batch: [ x0_new | xF_new ], nothing to free on the error paths
+        if (bt->h_prob.reserve(bt->err, 2 * n)) return fin(bt, -2);
+        if (x0_new) { memcpy(bt->h_prob, x0_new, n * sizeof(double)); dx0 = bt->stage; }
+        if (xF_new) { memcpy(bt->h_prob + n, xF_new, n * sizeof(double)); dxF = bt->stage + n; }
+        const size_t lo = x0_new ? 0 : n, hi = xF_new ? 2 * n : n;      // only the halves that were filled travel
+        if (hipMemcpyAsync(bt->stage + lo, bt->h_prob + lo, (hi - lo) * sizeof(double), hipMemcpyHostToDevice, bt->stream) != hipSuccess) { ctx->err = "obca_quad_batch_shift_warm_start: H2D failed"; return -2; }
+    }
+    hipLaunchKernelGGL(obca_quad_shift_kernel, dim3(bt->B), dim3(QNT), 0, bt->stream, bt->B, bt->N, shift, bt->d, dx0, dxF);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(bt->stream) != hipSuccess) { ctx->err = "obca_quad_batch_shift_warm_start: kernel failed"; return -2; }
+    bt->solved = 0;                                     // d.z still holds the previous solution, but the problem (x0, xF, warm start) has moved on
+    return 0;
+}
 int obca_quad_batch_sync(obca_quad_batch *bt) { return core_sync(bt, "obca_quad_batch_sync: hipStreamSynchronize failed"); }
 int obca_quad_batch_kernel_ms(obca_quad_batch *bt, float *ipm_ms) {
     if (!bt || !ipm_ms) return -1;
