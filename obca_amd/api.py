@@ -15,17 +15,14 @@ ctypes binding of libobca_hip.so and the Python mirror of the reference's entry 
 plus batched variants (leading batch dimension) that keep everything resident on the GPU between upload and download.
 """
 import ctypes as C
-import glob
 import numbers
 import os
-import subprocess
 import time
 import numpy as np
+from . import buildflags
 from .validate import VIOL_NAMES, QUAD_VIOL_NAMES
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "csrc")
-_LIBPATH = os.environ.get("OBCA_HIP_LIBRARY") or os.path.join(_CSRC, "libobca_hip.so")   # override: diagnostic builds
+_LIBPATH = os.environ.get("OBCA_HIP_LIBRARY") or buildflags.PIECES["hip"].out   # override: diagnostic builds
 _D = C.POINTER(C.c_double)
 _I = C.POINTER(C.c_int)
 _lib = None
@@ -49,14 +46,7 @@ def library_path():
 
 def build_library(force=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = glob.glob(os.path.join(_CSRC, "*.h")) + \
-           [os.path.join(_CSRC, "obca_hip.hip"), os.path.join(_HERE, "..", "include", "obca_hip.h"), os.path.join(_HERE, "buildflags.py")]      # (that file holds the compile flags)
-    if not force and os.path.exists(_LIBPATH) and all(os.path.getmtime(_LIBPATH) >= os.path.getmtime(s) for s in srcs):
-        return _LIBPATH
-    from .buildflags import HIPCC      # the flags (warnings are errors) and why: obca_amd/buildflags.py
-    cmd = HIPCC + ["-o", _LIBPATH, os.path.join(_CSRC, "obca_hip.hip")]
-    subprocess.check_call(cmd)
-    return _LIBPATH
+    return buildflags.build("hip", force, out=_LIBPATH)      # the flags (warnings are errors), the dependency rule and why: obca_amd/buildflags.py
 
 
 def _load():

@@ -1,12 +1,19 @@
-"""ONE place for the compile flags of every native piece (product library, its diagnostic variants, planner, host emulation); `python -m obca_amd.buildflags hipcc|gxx`
-prints a flag set for the shell scripts under tools/.
+"""ONE place for how every native piece is built: the compile flags, the table of the pieces (PIECES: product library, its diagnostic variants, device and host planner, the
+host emulations of the tests) and the one rule that compiles them (compile_if_stale: globbed dependencies, compile aside, rename into place).  The build functions of the
+package, the lazy builds of the tests, __graft_entry__.build() and the shell scripts under tools/ all go through build(NAME):
+
+    python -m obca_amd.buildflags build NAME...     builds the named pieces (those that are out of date)
+    python -m obca_amd.buildflags hipcc|gxx|warn    prints a flag set
 
 Warnings are errors everywhere.  Round 4 lost two stores of the stage assembly behind a `//` comment; `hipcc -Wall` prints that as "variable 'sumz' set but not used" -- the
 build scripts of rounds 1-5 never passed -Wall and filtered the compiler's output, and the bug cost two rounds.  tests/test_abi_cpu.py compiles the
 device sources with these flags (-fsyntax-only, seconds) and asserts that the compiler prints nothing.
   -Wno-unused-parameter: phase functions share signatures (dw, dc, ... are passed to every variant, used by some) -- the one warning class that is interface, not accident.
 """
+import collections
+import glob
 import os
+import subprocess
 import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -19,6 +26,71 @@ HIPCC = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-share
 # host C++ (planner; the emulation of the kernels under tests/emu, which sees `#pragma unroll`)
 GXX = ["g++", "-std=c++17", "-fPIC", "-shared"] + WARN + ["-Wno-unknown-pragmas", "-Wno-misleading-indentation"]
 
+_CSRC = os.path.join(_HERE, "csrc")
+_EMU = os.path.join(os.path.dirname(_HERE), "tests", "emu")
+Piece = collections.namedtuple("Piece", "cc flags out sources libs")
+
+
+def _piece(cc, flags, out, *sources, libs=()):
+    return Piece(cc, list(flags), out, list(sources), list(libs))
+
+
+_HIP = os.path.join(_CSRC, "obca_hip.hip")
+PIECES = {
+    "hip": _piece(HIPCC, [], os.path.join(_CSRC, "libobca_hip.so"), _HIP),                                          # the product: both IPM kernels + the C ABI (include/obca_hip.h)
+    "hip_prof": _piece(HIPCC, ["-DOBCA_PROFILE"], os.path.join(_CSRC, "libobca_hip_prof.so"), _HIP),                # per-phase clocks (tools/phase_profile.py); loaded through OBCA_HIP_LIBRARY
+    "hip_poison": _piece(HIPCC, ["-DOBCA_POISON"], os.path.join(_CSRC, "variants", "libobca_hip_poison.so"), _HIP),      # work buffers and LDS filled with NaN at entry ...
+    "hip_poison_1e30": _piece(HIPCC, ["-DOBCA_POISON", "-DOBCA_POISON_VALUE=1e30"], os.path.join(_CSRC, "variants", "libobca_hip_poison_1e30.so"), _HIP),      # ... and with 1e30: NaN hides behind fmax
+    "diag": _piece(HIPCC, [], os.path.join(_CSRC, "libobca_diag.so"), os.path.join(_CSRC, "obca_diag.hip")),        # the pattern kernel of the bit-equality tests (include/obca_diag.h)
+    "plan3d": _piece(HIPCC, [], os.path.join(_CSRC, "libobca_plan3d.so"), os.path.join(_CSRC, "obca_plan3d.hip")),  # the quadcopter's grid planner on the device (include/obca_plan3d.h)
+    "plan": _piece(GXX, ["-O2", "-pthread", "-I" + INCLUDE], os.path.join(_CSRC, "libobca_plan.so"),               # the host planner (Hybrid A*; REFERENCE mode in the second file)
+                   os.path.join(_CSRC, "obca_planner.cpp"), os.path.join(_CSRC, "obca_planner_ref.cpp")),
+}
+# test infrastructure, listed here so that it is built by the same rule (nothing in the package loads it): the kernel text compiled for the host, tests/emu/NAME.cpp -> libobca_NAME.so
+for _name, _src, _flags, _libs in (("emu", "obca_emu.cpp", ["-O1"], ["-ldl"]), ("validate_emu", "validate_emu.cpp", ["-O1"], []),
+                                   ("quad_shift_emu", "quad_shift_emu.cpp", ["-O1"], []), ("plan3d_emu", "plan3d_emu.cpp", ["-O2"], [])):
+    PIECES[_name] = _piece(GXX, _flags, os.path.join(_EMU, "libobca_%s.so" % _name), os.path.join(_EMU, _src), libs=_libs)
+DEFAULT = [n for n in PIECES if n not in ("hip_prof", "hip_poison", "hip_poison_1e30")]      # what __graft_entry__.build() compiles
+
+
+def dependencies(sources):
+    """What a piece is checked against: its sources, EVERY header of the project and this file (it holds the flags).  Globbed, not listed by hand: a header edit may
+    rebuild a piece that does not include it, never the other way round (tests/test_build_cpu.py walks the #include lines of every piece)."""
+    return list(sources) + glob.glob(os.path.join(_CSRC, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h")) + [os.path.abspath(__file__)]
+
+
+def compile_if_stale(out, cmd, sources, force=False, libs=()):
+    """Run `cmd -o out sources libs` if `out` is missing or older than one of dependencies(sources); returns `out`.  The compiler writes to a temporary beside `out` (its
+    name ends in .so: .gitignore covers it) that is renamed into place: a process that has the old library mapped keeps the old file, and several builders at once (xdist
+    workers, the `&` of tools/build.sh) each replace a whole file.  A failed compile removes its temporary and leaves the previous `out` as it was."""
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in dependencies(sources)):
+        return out
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    tmp = "%s.%d.tmp.so" % (out, os.getpid())
+    try:
+        subprocess.check_call(list(cmd) + ["-o", tmp] + list(sources) + list(libs))
+        os.replace(tmp, out)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return out
+
+
+def build(name, force=False, out=None, flags=None):
+    """build a piece of the table; `out` / `flags` replace the entry's output path / extra flags (the OBCA_HIP_LIBRARY override, the checking builds of the emulation,
+    the tuning variants of tools/plan3d_rate.py)"""
+    p = PIECES[name]
+    return compile_if_stale(out or p.out, p.cc + (p.flags if flags is None else list(flags)), p.sources, force, p.libs)
+
+
+def main(argv):
+    which = argv[0] if argv else "hipcc"
+    if which == "build":
+        for n in argv[1:]:
+            print(build(n))
+    else:
+        print(" ".join({"hipcc": HIPCC, "gxx": GXX, "warn": WARN}[which]))
+
+
 if __name__ == "__main__":
-    which = sys.argv[1] if len(sys.argv) > 1 else "hipcc"
-    print(" ".join({"hipcc": HIPCC, "gxx": GXX, "warn": WARN}[which]))
+    main(sys.argv[1:])

@@ -2,19 +2,14 @@
 contains none of it.  Used by tests/test_gpu_history.py, obca_amd.selftest() and the bit-equality line of bench.py."""
 import ctypes as C
 import os
-import subprocess
+from . import buildflags
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "csrc", "obca_diag.hip")
-_LIB = os.path.join(_HERE, "csrc", "libobca_diag.so")
+_LIB = buildflags.PIECES["diag"].out
 _lib = None
 
 
 def build_library(force=False):
-    if force or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(_SRC), os.path.getmtime(os.path.join(_HERE, "..", "include", "obca_diag.h"))):
-        from .buildflags import HIPCC
-        subprocess.check_call(HIPCC + ["-o", _LIB, _SRC])
-    return _LIB
+    return buildflags.build("diag", force)
 
 
 def _load():

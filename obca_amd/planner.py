@@ -7,23 +7,16 @@ velocity profile -> down-sampling to the horizon N); SURVEY.md section 8f "next-
 """
 import ctypes as C
 import os
-import subprocess
 import numpy as np
-from . import scenarios as S
+from . import buildflags, scenarios as S
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "csrc", "obca_planner.cpp")
-_SRC_REF = os.path.join(_HERE, "csrc", "obca_planner_ref.cpp")      # REFERENCE mode: the reference's Hybrid A* restated
-_LIB = os.path.join(_HERE, "csrc", "libobca_plan.so")
+_LIB = buildflags.PIECES["plan"].out      # obca_planner.cpp + obca_planner_ref.cpp (REFERENCE mode: the reference's Hybrid A* restated)
 _D = C.POINTER(C.c_double); _I = C.POINTER(C.c_int)
 _lib = None
 
 
 def build_library(force=False):
-    if force or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(_SRC), os.path.getmtime(_SRC_REF)):
-        from .buildflags import GXX
-        subprocess.check_call(GXX + ["-O2", "-pthread", "-I" + os.path.join(_HERE, "..", "include"), "-o", _LIB, _SRC, _SRC_REF])
-    return _LIB
+    return buildflags.build("plan", force)
 
 
 def _load():
@@ -333,8 +326,7 @@ def quad_warm_start(x0, xF, N, boxes=None, clear=0.4, res=0.25):
 
 
 # ---------------------------------------------------------------- the same search on the GPU, a batch per call (include/obca_plan3d.h, obca_amd/csrc/obca_plan3d.h)
-_SRC3D = [os.path.join(_HERE, "csrc", f) for f in ("obca_plan3d.hip", "obca_plan3d.h")] + [os.path.join(_HERE, "..", "include", "obca_plan3d.h")]
-_LIB3D = os.path.join(_HERE, "csrc", "libobca_plan3d.so")
+_LIB3D = buildflags.PIECES["plan3d"].out
 _lib3d = None
 _ctx3d = {}
 PLAN3D_EXPORTS = ["obca_plan3d_create", "obca_plan3d_destroy", "obca_plan3d_last_error", "obca_plan3d_paths_batch", "obca_plan3d_warm_start_batch", "obca_plan3d_kernel_ms"]
@@ -347,10 +339,7 @@ class Plan3DError(RuntimeError):
 
 def build_plan3d_library(force=False):
     """compile the device planner for gfx950 in-tree (hipcc cross-compiles without a GPU)"""
-    if force or not os.path.exists(_LIB3D) or os.path.getmtime(_LIB3D) < max(os.path.getmtime(s) for s in _SRC3D):
-        from .buildflags import HIPCC
-        subprocess.check_call(HIPCC + ["-o", _LIB3D, _SRC3D[0]])
-    return _LIB3D
+    return buildflags.build("plan3d", force, out=_LIB3D)
 
 
 def _load3d():

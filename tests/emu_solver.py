@@ -3,9 +3,9 @@ obca_amd.parking_signed_dist_batch so that host-side plumbing (sharding over ran
 with the kernels' own logic -- DualMultWS sub-problems + interior point -- rather than the oracle."""
 import ctypes as C
 import os
-import subprocess
 import numpy as np
 import packing as P
+from obca_amd import buildflags
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 D = C.POINTER(C.c_double)
@@ -20,27 +20,18 @@ class EOpts(C.Structure):
         [("max_soc", C.c_int), ("recalc_y", C.c_int), ("lsq_init", C.c_int), ("obj_scaling", C.c_int), ("restoration", C.c_int)]
 
 
-_VARIANTS = {None: ("libobca_emu.so", ["-O1"])}
+_VARIANTS = {None: {}}      # variant -> what it replaces of the table entry "emu" (obca_amd/buildflags.py): output path and flags
 try:      # the checking builds of the emulation (race log, UBSan, ASan: tests/test_emu_sanitize.py) -- CPU only; their flag table lives in its own file, which like that test is
           # listed in .gpurunignore: sanitizer builds have no business on the GPU box
     from emu_sanitize_variants import VARIANTS as _SAN
-    _VARIANTS.update(_SAN)
+    _VARIANTS.update({v: dict(out=os.path.join(ROOT, "tests", "emu", name), flags=flags) for v, (name, flags) in _SAN.items()})
 except ImportError:
     pass
 _loaded = {}
 
 
 def build(variant=None):
-    name, flags = _VARIANTS[variant]
-    src = os.path.join(ROOT, "tests", "emu", "obca_emu.cpp")
-    so = os.path.join(ROOT, "tests", "emu", name)
-    deps = [src] + [os.path.join(ROOT, "obca_amd", "csrc", f) for f in ("obca_solver.h", "obca_solver_lanes.h", "obca_solver_assemble.h", "obca_solver_riccati.h", "obca_solver_direction.h", "obca_solver_ipm.h", "obca_model.h", "obca_quad_solver.h", "obca_quad_model.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(so) < os.path.getmtime(d) for d in deps):
-        tmp = so + ".%d.tmp" % os.getpid()                  # (several xdist workers may build at once: compile aside, rename into place)
-        from obca_amd.buildflags import GXX                  # warnings are errors here too (obca_amd/buildflags.py)
-        subprocess.check_call(GXX + flags + ["-o", tmp, src, "-ldl"])
-        os.replace(tmp, so)
-    return so
+    return buildflags.build("emu", **_VARIANTS[variant])      # (compiled aside and renamed into place: several xdist workers may build at once)
 
 
 def load(variant=None):

@@ -1,11 +1,8 @@
 """Shared by tests/test_plan3d_cpu.py and tests/test_gpu_plan3d.py: the host build of the device planner (tests/emu/plan3d_emu.cpp), the end points of the tests, path
 costs and the tolerance of the cost comparison."""
 import ctypes as C
-import os
-import subprocess
 import numpy as np
-from conftest import ROOT
-from obca_amd import scenarios as S, planner as PL
+from obca_amd import buildflags, scenarios as S, planner as PL
 
 D = C.POINTER(C.c_double); I = C.POINTER(C.c_int); F = C.POINTER(C.c_float)
 ROOM = np.array(PL.QUAD_ROOM, float); RES = 0.25; CLEAR = 0.4
@@ -25,14 +22,7 @@ def emu():
     """tests/emu/libobca_plan3d_emu.so, compiled the way the other host emulations are"""
     global _emu
     if _emu is None:
-        src = os.path.join(ROOT, "tests", "emu", "plan3d_emu.cpp"); so = os.path.join(ROOT, "tests", "emu", "libobca_plan3d_emu.so")
-        deps = [src, os.path.join(ROOT, "obca_amd", "csrc", "obca_plan3d.h"), os.path.join(ROOT, "include", "obca_plan3d.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(so) < os.path.getmtime(d) for d in deps):
-            from obca_amd.buildflags import GXX
-            tmp = so + ".%d.tmp" % os.getpid()
-            subprocess.check_call(GXX + ["-O2", "-o", tmp, src])
-            os.replace(tmp, so)
-        lib = C.CDLL(so)
+        lib = C.CDLL(buildflags.build("plan3d_emu"))
         lib.emu_plan3d_last_error.restype = C.c_char_p
         lib.emu_plan3d_paths_batch.argtypes = [C.c_int, D, D, C.c_int, D, C.c_double, D, C.c_double, D, C.c_int, I, I, C.c_int, F]
         lib.emu_plan3d_warm_start_batch.argtypes = [C.c_int, C.c_int, D, D, C.c_int, D, C.c_double, D, C.c_double, D, I, D]

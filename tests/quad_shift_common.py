@@ -1,11 +1,9 @@
 """TEST INFRASTRUCTURE ONLY: the quadcopter receding-horizon shift (obca_amd/csrc/obca_quad_shift.h) built for the host (tests/emu/quad_shift_emu.cpp), a numpy statement of
 the same rules, and the packing between a QuadBatch download and the records the shift text reads.  Shared by tests/test_quad_shift_cpu.py and tests/test_gpu_quad_restart.py."""
 import ctypes as C
-import os
-import subprocess
 import numpy as np
-from conftest import ROOT
 import packing as P
+from obca_amd import buildflags
 
 D = C.POINTER(C.c_double)
 _LIB = None
@@ -20,14 +18,7 @@ def load():
     global _LIB
     if _LIB is not None:
         return _LIB
-    src = os.path.join(ROOT, "tests", "emu", "quad_shift_emu.cpp"); so = os.path.join(ROOT, "tests", "emu", "libobca_quad_shift_emu.so")
-    deps = [src] + [os.path.join(ROOT, "obca_amd", "csrc", f) for f in ("obca_quad_shift.h", "obca_solver.h", "obca_solver_lanes.h", "obca_model.h", "obca_quad_solver.h", "obca_quad_model.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(so) < os.path.getmtime(d) for d in deps):
-        from obca_amd.buildflags import GXX
-        tmp = so + ".%d.tmp" % os.getpid()
-        subprocess.check_call(GXX + ["-O1", "-o", tmp, src])
-        os.replace(tmp, so)
-    _LIB = C.CDLL(so)
+    _LIB = C.CDLL(buildflags.build("quad_shift_emu"))
     return _LIB
 
 

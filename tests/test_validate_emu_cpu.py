@@ -4,13 +4,12 @@ Comparison rules and the derivation of the bound: tests/validate_compare.py."""
 import ctypes as C
 import os
 import re
-import subprocess
 import numpy as np
 import pytest
 from conftest import ROOT, golden
 import packing as P
 import validate_compare as K
-from obca_amd import scenarios as S, validate as V
+from obca_amd import buildflags, scenarios as S, validate as V
 
 D = C.POINTER(C.c_double)
 
@@ -21,14 +20,7 @@ def dp(a):
 
 @pytest.fixture(scope="module")
 def vemu():
-    src = os.path.join(ROOT, "tests", "emu", "validate_emu.cpp"); so = os.path.join(ROOT, "tests", "emu", "libobca_validate_emu.so")
-    deps = [src] + [os.path.join(ROOT, "obca_amd", "csrc", f) for f in ("obca_validate.h", "obca_solver.h", "obca_solver_lanes.h", "obca_model.h", "obca_quad_solver.h", "obca_quad_model.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(so) < os.path.getmtime(d) for d in deps):
-        from obca_amd.buildflags import GXX
-        tmp = so + ".%d.tmp" % os.getpid()
-        subprocess.check_call(GXX + ["-O1", "-o", tmp, src])
-        os.replace(tmp, so)
-    lib = C.CDLL(so)
+    lib = C.CDLL(buildflags.build("validate_emu"))
     a, b, c, d = (C.c_int(0) for _ in range(4))
     lib.emu_validate_sizes(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
     assert (a.value, b.value, c.value, d.value) == (len(V.VIOL_NAMES), 16, len(V.QUAD_VIOL_NAMES), 10)

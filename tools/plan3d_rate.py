@@ -10,14 +10,13 @@ not there yet (build them where the compiler is cheap: `python tools/plan3d_rate
 import argparse
 import json
 import os
-import subprocess
 import sys
 import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from obca_amd import scenarios as S, planner as PL     # noqa: E402
+from obca_amd import buildflags, scenarios as S, planner as PL     # noqa: E402
 
 VARIANTS = [(nt, mp) for nt in (1024, 512, 256) for mp in (0, 1)]      # (threads per workgroup, map: 0 = node c to thread c mod NT, 1 = a contiguous run of nodes per thread)
 
@@ -27,12 +26,8 @@ def variant_path(nt, mp):
 
 
 def build_variants():
-    from obca_amd.buildflags import HIPCC
-    os.makedirs(os.path.dirname(variant_path(1, 0)), exist_ok=True)
     for nt, mp in VARIANTS:
-        p = variant_path(nt, mp)
-        if not os.path.exists(p) or os.path.getmtime(p) < max(os.path.getmtime(s) for s in PL._SRC3D):
-            subprocess.check_call(HIPCC + ["-DPL3_NT=%d" % nt, "-DPL3_MAP=%d" % mp, "-o", p, PL._SRC3D[0]])
+        buildflags.build("plan3d", out=variant_path(nt, mp), flags=["-DPL3_NT=%d" % nt, "-DPL3_MAP=%d" % mp])
 
 
 def use_library(path):
