@@ -19,25 +19,16 @@ import numbers
 import os
 import time
 import numpy as np
-from . import buildflags
+from . import buildflags, cabi
+from .cabi import Opts      # `typedef struct obca_opts` of include/obca_hip.h, read from the header
 from .validate import VIOL_NAMES, QUAD_VIOL_NAMES
 
 _LIBPATH = os.environ.get("OBCA_HIP_LIBRARY") or buildflags.PIECES["hip"].out   # override: diagnostic builds
-_D = C.POINTER(C.c_double)
-_I = C.POINTER(C.c_int)
 _lib = None
 
 
 class ObcaError(RuntimeError):
     pass
-
-
-class Opts(C.Structure):
-    _fields_ = [("tol", C.c_double), ("max_iter", C.c_int)] + \
-        [(n, C.c_double) for n in ("mu_init kappa_eps kappa_mu theta_mu tau_min bound_push bound_frac dw_min dw0 dw_max "
-                                   "kw_inc0 kw_inc kw_dec dc_bar kappa_c gamma_theta gamma_phi delta s_theta s_phi eta_phi "
-                                   "gamma_alpha s_max kappa_sigma constr_viol_tol dual_inf_tol compl_inf_tol rho_term").split()] + \
-        [("max_soc", C.c_int), ("recalc_y", C.c_int), ("lsq_init", C.c_int), ("obj_scaling", C.c_int), ("restoration", C.c_int)]      # the IPOPT switches (include/obca_hip.h): 0 in default_opts(), 4 / 1 / 1 in ipopt_opts()
 
 
 def library_path():
@@ -60,11 +51,8 @@ def _load():
     # batches in flight the extra streams bought nothing (rounds 3-6: 4 / 8 / 12 streams gave the same rate).  16 queues: +6 % on config 2, +8 % on config 3 with 16
     # batches in flight (profiles/r06_hw_queues.txt).  Read by the runtime at its first call in the process; a value the caller has set stays.
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-    lib = C.CDLL(_LIBPATH)
-    lib.obca_last_error.restype = C.c_char_p
-    lib.obca_last_error.argtypes = [C.c_void_p]
-    _lib = lib
-    return lib
+    _lib = cabi.bind(C.CDLL(_LIBPATH), "obca_hip.h")      # every prototype of the header: the call sites below pass numbers and prepared arrays
+    return _lib
 
 
 EXPORTS = ["obca_create", "obca_create_multi", "obca_device_count", "obca_visible_device_count", "obca_destroy", "obca_last_error", "obca_default_opts", "obca_reference_opts", "obca_device_name",
@@ -118,46 +106,92 @@ def warm_restart_opts():
     return o
 
 
-def default_opts():
+def _opts(fn):
+    """an option record filled by one of the library's four obca_*_opts"""
     o = Opts()
-    _load().obca_default_opts(C.byref(o))
+    getattr(_load(), fn)(C.byref(o))
     return o
+
+
+def default_opts():
+    return _opts("obca_default_opts")
 
 
 def ipopt_opts():
     """the reference's IPOPT configuration as far as the kernels carry it: default options + second-order correction (IPOPT's default max_soc = 4), recalc_y = "yes"
     (ParkingSignedDist.jl:41), IPOPT's least-squares initial multipliers, and the block feasibility restoration that stands in for IPOPT's restoration phase (restoration = 1)"""
-    o = Opts()
-    _load().obca_reference_opts(C.byref(o))
-    return o
+    return _opts("obca_reference_opts")
 
 
-def _d(a):
-    if a is None:
-        return None, None
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    return a, a.ctypes.data_as(_D)
+def _in(a, dtype=np.float64):
+    """an input as the ABI takes it: C-contiguous float64 (or int32); None stays NULL"""
+    return None if a is None else np.ascontiguousarray(a, dtype=dtype)
 
 
-def _i(a):
-    a = np.ascontiguousarray(a, dtype=np.int32)
-    return a, a.ctypes.data_as(_I)
+def _ref(opts):
+    return C.byref(opts) if opts is not None else None
 
 
-class Context:
+def _per_instance(v, B):
+    """a scalar or (B,) values -> (B,)"""
+    return _in(np.broadcast_to(np.asarray(v, float), (B,)))
+
+
+def _time_scale(timeScale, B, N1):
+    """a scalar, (B,) or (B, N+1) values -> (B, N+1)"""
+    ts = np.asarray(timeScale, float)
+    return _in(np.broadcast_to(ts.reshape(B, 1) if ts.ndim == 1 and ts.size == B else ts, (B, N1)))
+
+
+def _boxes(ob, B):
+    """the quadcopter's five boxes, one shared set (5,6) or (B,5,6) -> (B, 30)"""
+    ob = np.asarray(ob, float)
+    return _in(np.broadcast_to(ob.reshape(-1, 30) if ob.size != 30 else ob.reshape(1, 30), (B, 30)))
+
+
+def _blocks(flat, rows, N1):
+    """the ABI's packed per-instance blocks -> a list of (N+1, rows_i) views"""
+    ends = np.cumsum(rows) * N1
+    return [flat[e - r * N1:e].reshape(N1, r) for e, r in zip(ends.tolist(), np.asarray(rows).tolist())]
+
+
+def _verdict(B, names, call, ref_ok=False):
+    """the outputs of a validate entry point, `call(ok, [ref_ok,] viol)`, and the dict they are returned in"""
+    ok = np.zeros(B, np.int32); rok = [np.zeros(B, np.int32)] if ref_ok else []; viol = np.zeros((B, len(names)))
+    call(ok, *rok, viol)
+    return dict(ok=ok.astype(bool), **({"ref_ok": rok[0].astype(bool)} if ref_ok else {}), viol=viol, names=names)
+
+
+class _Handle:
+    """an opaque handle of the library (`_h`) and the call that destroys it (`_destroy`)"""
+
+    def close(self):
+        if self._h:
+            getattr(_load(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Context(_Handle):
     """One device (`device=k`), an explicit list (`devices=[...]`) or every visible device (`devices="all"`): the host-pointer entry points
     of a multi-device context shard their batch over the devices through a work queue (include/obca_hip.h, obca_create_multi)."""
+    _destroy = "obca_destroy"
 
     def __init__(self, device=0, devices=None):
         lib = _load()
         self._h = C.c_void_p()
         if devices is None:
-            rc = lib.obca_create(C.byref(self._h), C.c_int(int(device)))
+            rc = lib.obca_create(C.byref(self._h), int(device))
             self.devices = [int(device)]
         else:
             lst = [] if isinstance(devices, str) else [int(d) for d in devices]
             arr = (C.c_int * max(1, len(lst)))(*lst)
-            rc = lib.obca_create_multi(C.byref(self._h), arr if lst else None, C.c_int(len(lst)))
+            rc = lib.obca_create_multi(C.byref(self._h), arr if lst else None, len(lst))
             self.devices = lst
         if rc != 0:
             raise ObcaError("obca_create failed: " + (lib.obca_last_error(None) or b"").decode())
@@ -176,17 +210,6 @@ class Context:
         buf = C.create_string_buffer(256)
         _load().obca_device_name(self._h, buf, 256)
         return buf.value.decode()
-
-    def close(self):
-        if self._h:
-            _load().obca_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 _default_ctx = {}
@@ -239,6 +262,13 @@ def _dual_start(lWS, nWS, Mt, nt, N):
     return lWS, nWS
 
 
+def _problem(B, Ts, L, ego, XYbounds, fixTime, x0, xF, vOb, A, b):
+    """what the three parking entry points share: (nOb per instance, rows per instance, the arguments Ts .. b in the order of include/obca_hip.h)"""
+    nObs, vflat, Aflat, bflat = _norm_obstacles(B, vOb, A, b)
+    return nObs, _row_counts(nObs, vflat), (_per_instance(Ts, B), L, _in(ego), _in(XYbounds), int(fixTime), _in(np.reshape(x0, (B, 4))), _in(np.reshape(xF, (B, 4))),
+                                            _in(nObs, np.int32), _in(vflat, np.int32), _in(Aflat), _in(bflat))
+
+
 def _row_counts(nObs, vflat):
     """half-space rows per instance: segment sums of vflat (one numpy call -- a Python loop over 16 384 instances cost a third of the wrapper's time)"""
     nObs = np.asarray(nObs, np.int64)
@@ -247,13 +277,14 @@ def _row_counts(nObs, vflat):
     return csum[ends] - csum[ends - nObs]
 
 
-class _DeviceBatch:
+class _DeviceBatch(_Handle):
     """What Batch and QuadBatch share: the handle and the calls of the C ABI that differ only in their prefix (`_c`: obca_batch / obca_quad_batch)."""
+    _destroy = property(lambda self: f"{self._c}_destroy")
 
     def __init__(self, ctx, B, N):
         self.ctx, self.B, self.N = ctx, int(B), int(N)
         self._h = C.c_void_p()
-        self._call("create", ctx._h, C.c_int(self.B), C.c_int(self.N), C.byref(self._h), handle=False)
+        self._call("create", ctx._h, self.B, self.N, C.byref(self._h), handle=False)
 
     def _call(self, name, *args, handle=True):
         """obca_[quad_]batch_<name>(handle, *args); a non-zero status raises ObcaError with the library's message"""
@@ -261,7 +292,7 @@ class _DeviceBatch:
         self.ctx._check(getattr(_load(), fn)(*((self._h,) if handle else ()), *args), fn)
 
     def solve(self, opts=None, sync=True):
-        self._call("solve", C.byref(opts) if opts is not None else None)
+        self._call("solve", _ref(opts))
         if sync:
             self.sync()
 
@@ -273,7 +304,7 @@ class _DeviceBatch:
         out = np.zeros((self.B, 16))
         if not hasattr(_load(), f"{self._c}_debug_phase_cycles"):
             raise ObcaError("phase_cycles(): the loaded library is not the -DOBCA_PROFILE build")
-        self._call("debug_phase_cycles", out.ctypes.data_as(_D))
+        self._call("debug_phase_cycles", out)
         return out
 
     def scratch_bytes(self):
@@ -287,17 +318,6 @@ class _DeviceBatch:
         self._call("validate_ms", C.byref(a))
         return a.value
 
-    def close(self):
-        if self._h:
-            getattr(_load(), f"{self._c}_destroy")(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class Batch(_DeviceBatch):
     """Device-resident batch: upload once, solve (repeatedly), download."""
@@ -306,24 +326,16 @@ class Batch(_DeviceBatch):
     def upload(self, x0, xF, Ts, L, ego, XYbounds, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, lWS=None, nWS=None, dist=False):
         """lWS/nWS, when given, are packed per instance as (N+1, M_i) / (N+1, 4 nOb_i) row-major blocks (= the reference's
         column-major l (M x N+1) and n (4nOb x N+1))."""
-        self._call("set_formulation", C.c_int(int(bool(dist))))
+        self._call("set_formulation", bool(dist))
         B, N = self.B, self.N
-        nObs, vflat, Aflat, bflat = _norm_obstacles(B, vOb, A, b)
-        self.nObs, self.vflat = nObs, vflat
-        self.Ms = _row_counts(nObs, vflat)
-        Ts = np.broadcast_to(np.asarray(Ts, float), (B,))
-        lWS, nWS = _dual_start(lWS, nWS, int(self.Ms.sum()), int(nObs.sum()), N)
-        keep = [_d(Ts), _d(ego), _d(XYbounds), _d(np.reshape(x0, (B, 4))), _d(np.reshape(xF, (B, 4))), _i(nObs), _i(vflat),
-                _d(Aflat), _d(bflat), _d(np.reshape(rx, (B, N + 1))), _d(np.reshape(ry, (B, N + 1))), _d(np.reshape(ryaw, (B, N + 1))),
-                *(_d(w) for w in _warm_start(xWS, uWS, B, N)),
-                _d(lWS), _d(nWS)]
-        p = [k[1] for k in keep]
-        self._call("upload", p[0], C.c_double(float(L)), p[1], p[2], C.c_int(int(fixTime)), p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], p[11], p[12], p[13], p[14], p[15])
+        self.nObs, self.Ms, prob = _problem(B, Ts, L, ego, XYbounds, fixTime, x0, xF, vOb, A, b)
+        self.vflat = prob[8]
+        lWS, nWS = _dual_start(lWS, nWS, int(self.Ms.sum()), int(self.nObs.sum()), N)
+        self._call("upload", *prob, *(_in(np.reshape(r, (B, N + 1))) for r in (rx, ry, ryaw)), *(_in(w) for w in _warm_start(xWS, uWS, B, N)), _in(lWS), _in(nWS))
 
     def shift_warm_start(self, shift, x0_new=None):
         """receding-horizon restart: the next solve starts from the last solution advanced by `shift` stages (kept on the device)."""
-        keep = _d(np.reshape(x0_new, (self.B, 4))) if x0_new is not None else None
-        self._call("shift_warm_start", C.c_int(int(shift)), keep[1] if keep else None)
+        self._call("shift_warm_start", int(shift), _in(np.reshape(x0_new, (self.B, 4))) if x0_new is not None else None)
 
     def kernel_ms(self):
         """(ipm_ms, dualws_ms) of the last solve, measured with HIP events on the launch stream."""
@@ -342,18 +354,14 @@ class Batch(_DeviceBatch):
         Mt, nt = int(self.Ms.sum()), int(self.nObs.sum())
         xp = np.zeros((B, N + 1, 4)); up = np.zeros((B, N, 2)); ts = np.zeros((B, N + 1)); ef = np.zeros(B, np.int32)
         lp = np.zeros(Mt * (N + 1)); npp = np.zeros(4 * nt * (N + 1)); sl = np.zeros(nt * (N + 1)); info = np.zeros((B, 8))
-        self._call("download", xp.ctypes.data_as(_D), up.ctypes.data_as(_D), ts.ctypes.data_as(_D), ef.ctypes.data_as(_I), lp.ctypes.data_as(_D), npp.ctypes.data_as(_D),
-                   sl.ctypes.data_as(_D), info.ctypes.data_as(_D))
+        self._call("download", xp, up, ts, ef, lp, npp, sl, info)
         return _unpack_parking(B, N, self.nObs, self.Ms, xp, up, ts, ef, lp, npp, sl, info)
 
     def validate(self, tol=5e-5):
         """A-posteriori check of the last solution ON THE DEVICE (obca_batch_validate; the numpy statement is obca_amd.validate.validate_parking /
         parking_constraints_ref_worst): dict(ok (B,) bool -- every class except penetration <= tol --, ref_ok (B,) bool -- the reference's own test at 5e-5 --,
         viol (B, 14) in the order of `names` = VIOL_NAMES).  Only these 16 numbers per instance are downloaded."""
-        B = self.B
-        ok = np.zeros(B, np.int32); rok = np.zeros(B, np.int32); viol = np.zeros((B, len(VIOL_NAMES)))
-        self._call("validate", C.c_double(float(tol)), ok.ctypes.data_as(_I), rok.ctypes.data_as(_I), viol.ctypes.data_as(_D))
-        return dict(ok=ok.astype(bool), ref_ok=rok.astype(bool), viol=viol, names=VIOL_NAMES)
+        return _verdict(self.B, VIOL_NAMES, lambda *out: self._call("validate", tol, *out), ref_ok=True)
 
 
 def parking_signed_dist_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, lWS=None, nWS=None,
@@ -364,40 +372,24 @@ def parking_signed_dist_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, rx, ry
     `device`: an index, a list of indices or "all" (the batch is then sharded over the devices, obca_create_multi), or a Context.
     `buffers`: a dict the caller keeps between calls; the output arrays live in it and are written again by the next call of the same shape (a
     16 384-instance call returns 280 MB: fresh arrays cost a page fault per 4 KB inside the C call, tools/pcie_rate.py measures both)."""
-    x0 = np.ascontiguousarray(np.reshape(x0, (-1, 4)), float); B = x0.shape[0]
+    x0 = np.reshape(x0, (-1, 4)); B = x0.shape[0]
     ctx = _ctx(device)
-    nObs, vflat, Aflat, bflat = _norm_obstacles(B, vOb, A, b)
-    Ms = _row_counts(nObs, vflat)
+    nObs, Ms, prob = _problem(B, Ts, L, ego, XYbounds, fixTime, x0, xF, vOb, A, b)
     Mt, nt = int(Ms.sum()), int(nObs.sum())
-    Tsv = np.ascontiguousarray(np.broadcast_to(np.asarray(Ts, float), (B,)))
     lWS, nWS = _dual_start(lWS, nWS, Mt, nt, N)
-    keep = [_d(Tsv), _d(ego), _d(XYbounds), _d(x0), _d(np.reshape(xF, (B, 4))), _i(nObs), _i(vflat), _d(Aflat), _d(bflat),
-            _d(np.reshape(rx, (B, N + 1))), _d(np.reshape(ry, (B, N + 1))), _d(np.reshape(ryaw, (B, N + 1))),
-            *(_d(w) for w in _warm_start(xWS, uWS, B, N)), _d(lWS), _d(nWS)]
-    p = [k[1] for k in keep]
-    shapes = dict(xp=(B, N + 1, 4), up=(B, N, 2), ts=(B, N + 1), lp=(Mt * (N + 1),), npp=(4 * nt * (N + 1),), sl=(nt * (N + 1),), info=(B, 8))
+    ins = (*prob, *(_in(np.reshape(r, (B, N + 1))) for r in (rx, ry, ryaw)), *(_in(w) for w in _warm_start(xWS, uWS, B, N)), _in(lWS), _in(nWS), _ref(opts))
+    shapes = dict(xp=(B, N + 1, 4), up=(B, N, 2), ts=(B, N + 1), ef=(B,), lp=(Mt * (N + 1),), npp=(4 * nt * (N + 1),), sl=(nt * (N + 1),), info=(B, 8))      # in the ABI's order
     bufs = buffers if buffers is not None else {}
     for k, shp in shapes.items():
         if k not in bufs or bufs[k].shape != shp:
-            bufs[k] = np.zeros(shp) if k in ("sl", "info") else np.empty(shp)
-    if "ef" not in bufs or bufs["ef"].shape != (B,):
-        bufs["ef"] = np.zeros(B, np.int32)
-    xp, up, ts, ef, lp, npp, sl, info = (bufs[k] for k in ("xp", "up", "ts", "ef", "lp", "npp", "sl", "info"))
-    lib = _load()
+            bufs[k] = np.zeros(shp, np.int32 if k == "ef" else float) if k in ("ef", "sl", "info") else np.empty(shp)
+    xp, up, ts, ef, lp, npp, sl, info = (bufs[k] for k in shapes)
+    name = "obca_parking_dist_batch" if dist else "obca_parking_signed_dist_batch"      # the same arguments but for `slp`, which the dist entry point does not have
+    fn = getattr(_load(), name)
     t0 = time.perf_counter()
-    if dist:
-        rc = lib.obca_parking_dist_batch(ctx._h, C.c_int(B), C.c_int(int(N)), p[0], C.c_double(float(L)), p[1], p[2], C.c_int(int(fixTime)), p[3], p[4],
-                                         p[5], p[6], p[7], p[8], p[9], p[10], p[11], p[12], p[13], p[14], p[15], C.byref(opts) if opts is not None else None,
-                                         xp.ctypes.data_as(_D), up.ctypes.data_as(_D), ts.ctypes.data_as(_D), ef.ctypes.data_as(_I), lp.ctypes.data_as(_D),
-                                         npp.ctypes.data_as(_D), info.ctypes.data_as(_D))
-    else:
-        rc = lib.obca_parking_signed_dist_batch(ctx._h, C.c_int(B), C.c_int(int(N)), p[0], C.c_double(float(L)), p[1], p[2], C.c_int(int(fixTime)), p[3], p[4],
-                                                p[5], p[6], p[7], p[8], p[9], p[10], p[11], p[12], p[13], p[14], p[15],
-                                                C.byref(opts) if opts is not None else None, xp.ctypes.data_as(_D), up.ctypes.data_as(_D),
-                                                ts.ctypes.data_as(_D), ef.ctypes.data_as(_I), lp.ctypes.data_as(_D), npp.ctypes.data_as(_D),
-                                                sl.ctypes.data_as(_D), info.ctypes.data_as(_D))
+    rc = fn(ctx._h, B, int(N), *ins, xp, up, ts, ef, lp, npp, *(() if dist else (sl,)), info)
     dt = time.perf_counter() - t0
-    ctx._check(rc, "obca_parking_dist_batch" if dist else "obca_parking_signed_dist_batch")
+    ctx._check(rc, name)
     out = _unpack_parking(B, N, nObs, Ms, xp, up, ts, ef, lp, npp, sl, info)
     out["time"] = dt
     return out
@@ -410,42 +402,34 @@ def _unpack_parking(B, N, nObs, Ms, xp, up, ts, ef, lp, npp, sl, info):
         L3 = lp.reshape(B, N + 1, m).transpose(0, 2, 1); N3 = npp.reshape(B, N + 1, 4 * n).transpose(0, 2, 1); S3 = sl.reshape(B, N + 1, n).transpose(0, 2, 1)
         lps, nps, sls = L3, N3, S3                                             # (B, M, N+1) views: lp[i] is instance i's (M, N+1) array, as in the ragged case -- no 3 x B Python objects
     else:
-        lps, nps, sls = [], [], []
-        ro = oo = 0
-        for m, n in zip(Ms, nObs):
-            lps.append(lp[ro * (N + 1):(ro + m) * (N + 1)].reshape(N + 1, m).T)
-            nps.append(npp[4 * oo * (N + 1):4 * (oo + n) * (N + 1)].reshape(N + 1, 4 * n).T)
-            sls.append(sl[oo * (N + 1):(oo + n) * (N + 1)].reshape(N + 1, n).T)
-            ro += m; oo += n
+        lps, nps, sls = ([x.T for x in _blocks(a, rows, N + 1)] for a, rows in ((lp, Ms), (npp, 4 * nObs), (sl, nObs)))
     return dict(xp=np.transpose(xp, (0, 2, 1)), up=np.transpose(up, (0, 2, 1)), timeScale=ts, exitflag=ef,
                 lp=lps, np=nps, sl=sls, info=info, iters=info[:, 1].astype(int), obj=info[:, 2], status=info[:, 0].astype(int))
+
+
+def _parking_one(dist, x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, opts, device):
+    """one instance through the batched call, returned as the reference's 7-tuple"""
+    assert int(nOb) == len(np.ravel(vOb))
+    opts = ipopt_opts() if opts is None else opts
+    r = parking_signed_dist_batch(np.reshape(x0, (1, 4)), np.reshape(xF, (1, 4)), N, Ts, L, ego, XYbounds, vOb, A, b,
+                                  np.reshape(np.ravel(rx)[:N + 1], (1, -1)), np.reshape(np.ravel(ry)[:N + 1], (1, -1)),
+                                  np.reshape(np.ravel(ryaw)[:N + 1], (1, -1)), fixTime, np.asarray(xWS, float)[None, :N + 1],
+                                  np.asarray(uWS, float)[None, :N], opts=opts, device=device, dist=dist)
+    ts = np.ones((1, N + 1)) if fixTime else r["timeScale"][0]          # ParkingSignedDist.jl:304-308
+    return r["xp"][0], r["up"][0], ts, int(r["exitflag"][0]), r["time"], r["lp"][0], r["np"][0]
 
 
 def ParkingSignedDist(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, opts=None, device=0):
     """Drop-in for ParkingSignedDist.jl:29 (one instance).  Returns (xp, up, timeScalep, exitflag, time, lp, np).
     opts=None runs the reference's IPOPT configuration (ipopt_opts(): recalc_y = "yes" as ParkingSignedDist.jl:41 sets it, IPOPT's default second-order correction and
     least-squares initial multipliers); pass default_opts() for the library's throughput defaults (include/obca_hip.h says what the difference costs and changes)."""
-    assert int(nOb) == len(np.ravel(vOb))
-    opts = ipopt_opts() if opts is None else opts
-    r = parking_signed_dist_batch(np.reshape(x0, (1, 4)), np.reshape(xF, (1, 4)), N, Ts, L, ego, XYbounds, vOb, A, b,
-                                  np.reshape(np.ravel(rx)[:N + 1], (1, -1)), np.reshape(np.ravel(ry)[:N + 1], (1, -1)),
-                                  np.reshape(np.ravel(ryaw)[:N + 1], (1, -1)), fixTime, np.asarray(xWS, float)[None, :N + 1],
-                                  np.asarray(uWS, float)[None, :N], opts=opts, device=device)
-    ts = np.ones((1, N + 1)) if fixTime else r["timeScale"][0]          # ParkingSignedDist.jl:304-308
-    return r["xp"][0], r["up"][0], ts, int(r["exitflag"][0]), r["time"], r["lp"][0], r["np"][0]
+    return _parking_one(False, x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, opts, device)
 
 
 def ParkingDist(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, opts=None, device=0):
     """Drop-in for ParkingDist.jl:29 (the collision-free sibling of ParkingSignedDist): same arguments, same 7-tuple.  opts=None: the reference's IPOPT configuration
     (ParkingDist.jl:41 sets recalc_y = "yes" as well), see ParkingSignedDist."""
-    assert int(nOb) == len(np.ravel(vOb))
-    opts = ipopt_opts() if opts is None else opts
-    r = parking_signed_dist_batch(np.reshape(x0, (1, 4)), np.reshape(xF, (1, 4)), N, Ts, L, ego, XYbounds, vOb, A, b,
-                                  np.reshape(np.ravel(rx)[:N + 1], (1, -1)), np.reshape(np.ravel(ry)[:N + 1], (1, -1)),
-                                  np.reshape(np.ravel(ryaw)[:N + 1], (1, -1)), fixTime, np.asarray(xWS, float)[None, :N + 1],
-                                  np.asarray(uWS, float)[None, :N], opts=opts, device=device, dist=True)
-    ts = np.ones((1, N + 1)) if fixTime else r["timeScale"][0]
-    return r["xp"][0], r["up"][0], ts, int(r["exitflag"][0]), r["time"], r["lp"][0], r["np"][0]
+    return _parking_one(True, x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, opts, device)
 
 
 def _pack_cols(a, B, rows, N1, what):
@@ -460,26 +444,15 @@ def parking_constraints_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, x, u, 
     """Batched ParkingConstraints on the device for arbitrary trajectories (obca_parking_constraints_batch): x (B,4,N+1), u (B,2,N), l / n / sl per instance
     (M_i,N+1) / (4nOb_i,N+1) / (nOb_i,N+1) -- the shapes the solve calls return --, timeScale scalar, (B,) or (B,N+1) (it may vary over the stages).
     Obstacles and `device` as in parking_signed_dist_batch.  Returns dict(ok, ref_ok, viol (B,14), names) like Batch.validate; sl=None: zeros."""
-    x0 = np.ascontiguousarray(np.reshape(x0, (-1, 4)), float); B = x0.shape[0]; N = int(N)
+    x0 = np.reshape(x0, (-1, 4)); B = x0.shape[0]; N = int(N)
     ctx = _ctx(device)
-    nObs, vflat, Aflat, bflat = _norm_obstacles(B, vOb, A, b)
-    Ms = _row_counts(nObs, vflat)
-    Tsv = np.ascontiguousarray(np.broadcast_to(np.asarray(Ts, float), (B,)))
+    nObs, Ms, prob = _problem(B, Ts, L, ego, XYbounds, fixTime, x0, xF, vOb, A, b)
     x = np.asarray(x, float); u = np.asarray(u, float)
     if x.shape != (B, 4, N + 1) or u.shape != (B, 2, N):
         raise ObcaError(f"x must be (B,4,N+1) and u (B,2,N); got {x.shape}, {u.shape}")
-    ts = np.asarray(timeScale, float)
-    ts = np.broadcast_to(ts.reshape(B, 1) if ts.ndim == 1 and ts.size == B else ts, (B, N + 1))
-    keep = [_d(Tsv), _d(ego), _d(XYbounds), _d(x0), _d(np.reshape(xF, (B, 4))), _i(nObs), _i(vflat), _d(Aflat), _d(bflat),
-            _d(np.transpose(x, (0, 2, 1))), _d(np.transpose(u, (0, 2, 1))), _d(ts), _d(_pack_cols(l, B, Ms, N + 1, "l")), _d(_pack_cols(n, B, 4 * nObs, N + 1, "n")),
-            _d(_pack_cols(sl, B, nObs, N + 1, "sl") if sl is not None else None)]
-    p = [k[1] for k in keep]
-    ok = np.zeros(B, np.int32); rok = np.zeros(B, np.int32); viol = np.zeros((B, len(VIOL_NAMES)))
-    rc = _load().obca_parking_constraints_batch(ctx._h, C.c_int(B), C.c_int(N), p[0], C.c_double(float(L)), p[1], p[2], C.c_int(int(fixTime)), p[3], p[4], p[5], p[6], p[7], p[8],
-                                                C.c_int(int(bool(dist))), p[9], p[10], p[11], p[12], p[13], p[14], C.c_double(float(tol)),
-                                                ok.ctypes.data_as(_I), rok.ctypes.data_as(_I), viol.ctypes.data_as(_D))
-    ctx._check(rc, "obca_parking_constraints_batch")
-    return dict(ok=ok.astype(bool), ref_ok=rok.astype(bool), viol=viol, names=VIOL_NAMES)
+    ins = (*prob, bool(dist), _in(np.transpose(x, (0, 2, 1))), _in(np.transpose(u, (0, 2, 1))), _time_scale(timeScale, B, N + 1), _pack_cols(l, B, Ms, N + 1, "l"),
+           _pack_cols(n, B, 4 * nObs, N + 1, "n"), _pack_cols(sl, B, nObs, N + 1, "sl") if sl is not None else None, tol)
+    return _verdict(B, VIOL_NAMES, lambda *out: ctx._check(_load().obca_parking_constraints_batch(ctx._h, B, N, *ins, *out), "obca_parking_constraints_batch"), ref_ok=True)
 
 
 def ParkingConstraints(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, u, l, n, timeScale, fixTime, sd, device=0):
@@ -498,19 +471,10 @@ def dualmult_ws_batch(N, vOb, A, b, rx, ry, ryaw, ego, device=0):
     Ms = _row_counts(nObs, vflat)
     Mt, nt = int(Ms.sum()), int(nObs.sum())
     lw = np.zeros(Mt * (N + 1)); nw = np.zeros(4 * nt * (N + 1)); dd = np.zeros(nt * (N + 1))
-    keep = [_d(ego), _i(nObs), _i(vflat), _d(Aflat), _d(bflat), _d(rx), _d(np.atleast_2d(ry)), _d(np.atleast_2d(ryaw))]
-    p = [k[1] for k in keep]
-    rc = _load().obca_dualmult_ws_batch(ctx._h, C.c_int(B), C.c_int(N), p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7],
-                                        lw.ctypes.data_as(_D), nw.ctypes.data_as(_D), dd.ctypes.data_as(_D))
+    rc = _load().obca_dualmult_ws_batch(ctx._h, B, N, _in(ego), _in(nObs, np.int32), _in(vflat, np.int32), _in(Aflat), _in(bflat), _in(rx), _in(np.atleast_2d(ry)),
+                                        _in(np.atleast_2d(ryaw)), lw, nw, dd)
     ctx._check(rc, "obca_dualmult_ws_batch")
-    ls, ns, ds = [], [], []
-    ro = oo = 0
-    for m, n in zip(Ms, nObs):
-        ls.append(lw[ro * (N + 1):(ro + m) * (N + 1)].reshape(N + 1, m).copy())
-        ns.append(nw[4 * oo * (N + 1):4 * (oo + n) * (N + 1)].reshape(N + 1, 4 * n).copy())
-        ds.append(dd[oo * (N + 1):(oo + n) * (N + 1)].reshape(N + 1, n).copy())
-        ro += m; oo += n
-    return ls, ns, ds
+    return tuple([x.copy() for x in _blocks(a, rows, N + 1)] for a, rows in ((lw, Ms), (nw, 4 * nObs), (dd, nObs)))
 
 
 def DualMultWS(N, nOb, vOb, A, b, rx, ry, ryaw, ego, device=0):
@@ -523,17 +487,13 @@ def DualMultWS(N, nOb, vOb, A, b, rx, ry, ryaw, ego, device=0):
 
 # ---------------------------------------------------------------- quadcopter path (QuadcopterSignedDist.jl)
 def quadcopter_default_opts():
-    o = Opts()
-    _load().obca_quadcopter_default_opts(C.byref(o))
-    return o
+    return _opts("obca_quadcopter_default_opts")
 
 
 def quadcopter_ipopt_opts():
     """the reference's IPOPT configuration of the quadcopter call as far as the kernel carries it (obca_quadcopter_reference_opts: max_soc = 4, least-squares
     initial multipliers, gradient-based objective scaling; recalc_y = "no" as QuadcopterSignedDist.jl:29 sets it): the default of the drop-ins QuadcopterSignedDist / QuadcopterDist"""
-    o = Opts()
-    _load().obca_quadcopter_reference_opts(C.byref(o))
-    return o
+    return _opts("obca_quadcopter_reference_opts")
 
 
 def quad_warm_restart_opts(reference=False):
@@ -558,26 +518,25 @@ def quad_warm_restart_opts(reference=False):
     return o
 
 
+def _unpack_quad(T, xp, up, ts, ef, lp, sl, info):
+    """C-ABI output arrays -> the reference's shapes, T = the transposition of the stage-contiguous ones (a copy for the resident batch, a view for the host-pointer call)"""
+    return dict(xp=T(xp), up=T(up), timeScale=ts, exitflag=ef, lp=T(lp), slack=T(sl), info=info, iters=info[:, 1].astype(int), obj=info[:, 2], status=info[:, 0].astype(int))
+
+
 class QuadBatch(_DeviceBatch):
     """Device-resident batch of quadcopter signed-distance NLPs (obca_quad_batch_* in include/obca_hip.h)."""
     _c = "obca_quad_batch"
 
     def upload(self, x0, xF, Ts, R, ob, xWS, timeWS, dual_ws=True, dist=False):
         B, N = self.B, self.N
-        Tsv = np.broadcast_to(np.asarray(Ts, float), (B,)).copy(); tw = np.broadcast_to(np.asarray(timeWS, float), (B,)).copy()
-        obv = np.broadcast_to(np.asarray(ob, float).reshape(-1, 30) if np.size(ob) != 30 else np.asarray(ob, float).reshape(1, 30), (B, 30)).copy()
-        xw = np.ascontiguousarray(np.asarray(xWS, float)[:, :N + 1]); assert xw.shape == (B, N + 1, 12)
-        keep = [_d(Tsv), _d(np.reshape(x0, (B, 12))), _d(np.reshape(xF, (B, 12))), _d(obv), _d(xw), _d(tw)]
-        p = [k[1] for k in keep]
-        self._call("upload", p[0], C.c_double(R), p[1], p[2], p[3], p[4], p[5], C.c_int(int(bool(dual_ws))), C.c_int(int(bool(dist))))
+        xw = _in(np.asarray(xWS, float)[:, :N + 1]); assert xw.shape == (B, N + 1, 12)
+        self._call("upload", _per_instance(Ts, B), R, _in(np.reshape(x0, (B, 12))), _in(np.reshape(xF, (B, 12))), _boxes(ob, B), xw, _per_instance(timeWS, B), bool(dual_ws), bool(dist))
 
     def shift_warm_start(self, shift, x0_new=None, xF_new=None):
         """receding-horizon restart on the device (obca_quad_batch_shift_warm_start): the next solve starts from the last solution advanced by `shift` stages -- all 12 states,
         timeWS = the last t, closed-form duals --, from x0_new (B,12; the measured state; None: stage `shift` of the solution) towards xF_new (B,12; a moving goal; None: unchanged).
         An instance whose last solve failed keeps its uploaded warm start.  Solve with quad_warm_restart_opts()."""
-        k0 = _d(np.reshape(x0_new, (self.B, 12))) if x0_new is not None else (None, None)
-        kF = _d(np.reshape(xF_new, (self.B, 12))) if xF_new is not None else (None, None)
-        self._call("shift_warm_start", C.c_int(int(shift)), k0[1], kF[1])
+        self._call("shift_warm_start", int(shift), *(_in(np.reshape(a, (self.B, 12))) if a is not None else None for a in (x0_new, xF_new)))
 
     def kernel_ms(self):
         a = C.c_float(0)
@@ -588,46 +547,30 @@ class QuadBatch(_DeviceBatch):
         B, N = self.B, self.N
         xp = np.zeros((B, N + 1, 12)); up = np.zeros((B, N, 4)); ts = np.zeros((B, N + 1)); ef = np.zeros(B, np.int32)
         lp = np.zeros((B, N + 1, 30)); sl = np.zeros((B, N + 1, 5)); info = np.zeros((B, 8))
-        self._call("download", xp.ctypes.data_as(_D), up.ctypes.data_as(_D), ts.ctypes.data_as(_D), ef.ctypes.data_as(_I), lp.ctypes.data_as(_D), sl.ctypes.data_as(_D), info.ctypes.data_as(_D))
-        T = lambda a: np.transpose(a, (0, 2, 1)).copy()
-        return dict(xp=T(xp), up=T(up), timeScale=ts, exitflag=ef, lp=T(lp), slack=T(sl), info=info, iters=info[:, 1].astype(int),
-                    obj=info[:, 2], status=info[:, 0].astype(int))
+        self._call("download", xp, up, ts, ef, lp, sl, info)
+        return _unpack_quad(lambda a: np.transpose(a, (0, 2, 1)).copy(), xp, up, ts, ef, lp, sl, info)
 
     def validate(self, tol=1e-3):
         """constrSatisfaction on the last solution, on the device (obca_quad_batch_validate): dict(ok (B,) bool, viol (B, 9) in the order of `names` = QUAD_VIOL_NAMES)"""
-        B = self.B
-        ok = np.zeros(B, np.int32); viol = np.zeros((B, len(QUAD_VIOL_NAMES)))
-        self._call("validate", C.c_double(float(tol)), ok.ctypes.data_as(_I), viol.ctypes.data_as(_D))
-        return dict(ok=ok.astype(bool), viol=viol, names=QUAD_VIOL_NAMES)
+        return _verdict(self.B, QUAD_VIOL_NAMES, lambda *out: self._call("validate", tol, *out))
 
 
 def quadcopter_signed_dist_batch(x0, xF, N, Ts, R, ob, xWS, timeWS, dual_ws=True, opts=None, device=0, dist=False):
     """Batched QuadcopterSignedDist / QuadcopterDist through the host-pointer entry points (what the Julia shim calls):
     x0,xF (B,12); ob (5,6) shared or (B,5,6); xWS (B,N+1,12); Ts, timeWS scalar or (B,).  `device` as in parking_signed_dist_batch."""
-    x0 = np.ascontiguousarray(np.reshape(x0, (-1, 12)), float); B = x0.shape[0]
+    x0 = _in(np.reshape(x0, (-1, 12))); B = x0.shape[0]
     ctx = _ctx(device)
-    Tsv = np.broadcast_to(np.asarray(Ts, float), (B,)).copy(); tw = np.broadcast_to(np.asarray(timeWS, float), (B,)).copy()
-    obv = np.broadcast_to(np.asarray(ob, float).reshape(-1, 30) if np.size(ob) != 30 else np.asarray(ob, float).reshape(1, 30), (B, 30)).copy()
-    xw = np.ascontiguousarray(np.asarray(xWS, float)[:, :N + 1]); assert xw.shape == (B, N + 1, 12)
-    keep = [_d(Tsv), _d(x0), _d(np.reshape(xF, (B, 12))), _d(obv), _d(xw), _d(tw)]
-    p = [k[1] for k in keep]
+    xw = _in(np.asarray(xWS, float)[:, :N + 1]); assert xw.shape == (B, N + 1, 12)
+    ins = (_per_instance(Ts, B), R, x0, _in(np.reshape(xF, (B, 12))), _boxes(ob, B), xw, None, _per_instance(timeWS, B), bool(dual_ws), _ref(opts))      # (uWS: ignored, NULL)
     xp = np.empty((B, N + 1, 12)); up = np.empty((B, N, 4)); ts = np.empty((B, N + 1)); ef = np.zeros(B, np.int32)
     lp = np.empty((B, N + 1, 30)); sl = np.zeros((B, N + 1, 5)); info = np.zeros((B, 8))
-    lib = _load(); o = C.byref(opts) if opts is not None else None
+    name = "obca_quadcopter_dist_batch" if dist else "obca_quadcopter_signed_dist_batch"      # the same arguments but for `slack`, which the dist entry point does not have
+    fn = getattr(_load(), name)
     t0 = time.perf_counter()
-    if dist:
-        rc = lib.obca_quadcopter_dist_batch(ctx._h, C.c_int(B), C.c_int(int(N)), p[0], C.c_double(float(R)), p[1], p[2], p[3], p[4], None, p[5],
-                                            C.c_int(int(bool(dual_ws))), o, xp.ctypes.data_as(_D), up.ctypes.data_as(_D), ts.ctypes.data_as(_D),
-                                            ef.ctypes.data_as(_I), lp.ctypes.data_as(_D), info.ctypes.data_as(_D))
-    else:
-        rc = lib.obca_quadcopter_signed_dist_batch(ctx._h, C.c_int(B), C.c_int(int(N)), p[0], C.c_double(float(R)), p[1], p[2], p[3], p[4], None, p[5],
-                                                   C.c_int(int(bool(dual_ws))), o, xp.ctypes.data_as(_D), up.ctypes.data_as(_D), ts.ctypes.data_as(_D),
-                                                   ef.ctypes.data_as(_I), lp.ctypes.data_as(_D), sl.ctypes.data_as(_D), info.ctypes.data_as(_D))
+    rc = fn(ctx._h, B, int(N), *ins, xp, up, ts, ef, lp, *(() if dist else (sl,)), info)
     dt = time.perf_counter() - t0
-    ctx._check(rc, "obca_quadcopter_dist_batch" if dist else "obca_quadcopter_signed_dist_batch")
-    T = lambda a: np.transpose(a, (0, 2, 1))
-    return dict(xp=T(xp), up=T(up), timeScale=ts, exitflag=ef, lp=T(lp), slack=T(sl), info=info, iters=info[:, 1].astype(int),
-                obj=info[:, 2], status=info[:, 0].astype(int), time=dt)
+    ctx._check(rc, name)
+    return dict(_unpack_quad(lambda a: np.transpose(a, (0, 2, 1)), xp, up, ts, ef, lp, sl, info), time=dt)
 
 
 def quadcopter_constr_satisfaction_batch(x, u, timeScale, x0, xF, Ts, lam, ob, R, tol=1e-3, device=0):
@@ -638,18 +581,10 @@ def quadcopter_constr_satisfaction_batch(x, u, timeScale, x0, xF, Ts, lam, ob, R
     if x.shape != (B, 12, N1) or u.shape != (B, 4, N) or lam.shape != (B, 30, N1):
         raise ObcaError(f"x must be (B,12,N+1), u (B,4,N), lam (B,30,N+1); got {x.shape}, {u.shape}, {lam.shape}")
     ctx = _ctx(device)
-    Tsv = np.broadcast_to(np.asarray(Ts, float), (B,)).copy()
-    obv = np.broadcast_to(np.asarray(ob, float).reshape(-1, 30) if np.size(ob) != 30 else np.asarray(ob, float).reshape(1, 30), (B, 30)).copy()
-    ts = np.asarray(timeScale, float)
-    ts = np.broadcast_to(ts.reshape(B, 1) if ts.ndim == 1 and ts.size == B else ts, (B, N1))
-    keep = [_d(Tsv), _d(np.broadcast_to(np.reshape(x0, (-1, 12)), (B, 12))), _d(np.broadcast_to(np.reshape(xF, (-1, 12)), (B, 12))), _d(obv),
-            _d(np.transpose(x, (0, 2, 1))), _d(np.transpose(u, (0, 2, 1))), _d(ts), _d(np.transpose(lam, (0, 2, 1)))]
-    p = [k[1] for k in keep]
-    ok = np.zeros(B, np.int32); viol = np.zeros((B, len(QUAD_VIOL_NAMES)))
-    rc = _load().obca_quadcopter_constr_satisfaction_batch(ctx._h, C.c_int(B), C.c_int(N), p[0], C.c_double(float(R)), p[1], p[2], p[3], p[4], p[5], p[6], p[7],
-                                                           C.c_double(float(tol)), ok.ctypes.data_as(_I), viol.ctypes.data_as(_D))
-    ctx._check(rc, "obca_quadcopter_constr_satisfaction_batch")
-    return dict(ok=ok.astype(bool), viol=viol, names=QUAD_VIOL_NAMES)
+    ins = (_per_instance(Ts, B), R, *(_in(np.broadcast_to(np.reshape(a, (-1, 12)), (B, 12))) for a in (x0, xF)), _boxes(ob, B),
+           _in(np.transpose(x, (0, 2, 1))), _in(np.transpose(u, (0, 2, 1))), _time_scale(timeScale, B, N1), _in(np.transpose(lam, (0, 2, 1))), tol)
+    return _verdict(B, QUAD_VIOL_NAMES, lambda *out: ctx._check(_load().obca_quadcopter_constr_satisfaction_batch(ctx._h, B, N, *ins, *out),
+                                                                "obca_quadcopter_constr_satisfaction_batch"))
 
 
 def constrSatisfaction(x, u, timeScale, x0, xF, Ts, lam, ob1, ob2, ob3, ob4, ob5, R, device=0):
@@ -664,20 +599,21 @@ def constrSatisfaction(x, u, timeScale, x0, xF, Ts, lam, ob1, ob2, ob3, ob4, ob5
 _QUAD_STATUS = {0: "Optimal", 1: "UserLimit", 2: "Error"}
 
 
+def _quadcopter_one(dist, x0, xF, N, Ts, R, obs, xWS, timeWS, opts, device, dual_ws):
+    """one instance through the batched call, returned as the reference's 7-tuple"""
+    ob = np.stack([np.ravel(o)[:6] for o in obs])
+    opts = quadcopter_ipopt_opts() if opts is None else opts      # the drop-in runs the reference's IPOPT configuration; the batched calls default to the throughput options
+    r = quadcopter_signed_dist_batch(np.reshape(x0, (1, 12)), np.reshape(xF, (1, 12)), N, Ts, R, ob, np.asarray(xWS, float)[None, :N + 1],
+                                     timeWS, dual_ws, opts, device, dist=dist)
+    return r["xp"][0], r["up"][0], r["timeScale"][0], int(r["exitflag"][0]), r["time"], r["lp"][0], _QUAD_STATUS[int(r["status"][0])]
+
+
 def QuadcopterSignedDist(x0, xF, N, Ts, R, ob1, ob2, ob3, ob4, ob5, xWS, uWS, timeWS, opts=None, device=0, dual_ws=True):
     """Drop-in for QuadcopterSignedDist.jl:25 (one instance; xWS is (N+1,12) here, the reference's is 12 x (N+1) column-major,
     i.e. the same memory).  Returns (xp, up, timeScalep, exitflag, time, lp, status) like :298; uWS is ignored like :202."""
-    ob = np.stack([np.ravel(o)[:6] for o in (ob1, ob2, ob3, ob4, ob5)])
-    opts = quadcopter_ipopt_opts() if opts is None else opts      # the drop-in runs the reference's IPOPT configuration; the batched calls default to the throughput options
-    r = quadcopter_signed_dist_batch(np.reshape(x0, (1, 12)), np.reshape(xF, (1, 12)), N, Ts, R, ob, np.asarray(xWS, float)[None, :N + 1],
-                                     timeWS, dual_ws, opts, device)
-    return r["xp"][0], r["up"][0], r["timeScale"][0], int(r["exitflag"][0]), r["time"], r["lp"][0], _QUAD_STATUS[int(r["status"][0])]
+    return _quadcopter_one(False, x0, xF, N, Ts, R, (ob1, ob2, ob3, ob4, ob5), xWS, timeWS, opts, device, dual_ws)
 
 
 def QuadcopterDist(x0, xF, N, Ts, R, ob1, ob2, ob3, ob4, ob5, xWS, uWS, timeWS, opts=None, device=0, dual_ws=True):
     """Drop-in for QuadcopterDist.jl:25 (the collision-free sibling: no slack variable): same arguments and 7-tuple as QuadcopterSignedDist."""
-    ob = np.stack([np.ravel(o)[:6] for o in (ob1, ob2, ob3, ob4, ob5)])
-    opts = quadcopter_ipopt_opts() if opts is None else opts      # the drop-in runs the reference's IPOPT configuration; the batched calls default to the throughput options
-    r = quadcopter_signed_dist_batch(np.reshape(x0, (1, 12)), np.reshape(xF, (1, 12)), N, Ts, R, ob, np.asarray(xWS, float)[None, :N + 1],
-                                     timeWS, dual_ws, opts, device, dist=True)
-    return r["xp"][0], r["up"][0], r["timeScale"][0], int(r["exitflag"][0]), r["time"], r["lp"][0], _QUAD_STATUS[int(r["status"][0])]
+    return _quadcopter_one(True, x0, xF, N, Ts, R, (ob1, ob2, ob3, ob4, ob5), xWS, timeWS, opts, device, dual_ws)

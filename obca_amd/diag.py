@@ -2,7 +2,7 @@
 contains none of it.  Used by tests/test_gpu_history.py, obca_amd.selftest() and the bit-equality line of bench.py."""
 import ctypes as C
 import os
-from . import buildflags
+from . import buildflags, cabi
 
 _LIB = buildflags.PIECES["diag"].out
 _lib = None
@@ -17,8 +17,7 @@ def _load():
     if _lib is None:
         if not os.path.exists(_LIB):
             raise RuntimeError(f"{_LIB} is missing: build it with obca_amd.diag.build_library() / __graft_entry__.build()")
-        _lib = C.CDLL(_LIB)
-        _lib.obca_diag_leave_pattern.argtypes = [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _lib = cabi.bind(C.CDLL(_LIB), "obca_diag.h")
     return _lib
 
 
@@ -33,7 +32,7 @@ def leave_pattern(devices, mask=4, value=1e30):
     out = []
     for d in devices:
         a, b = C.c_int(0), C.c_int(0)
-        rc = _load().obca_diag_leave_pattern(int(d), int(mask), float(value), C.byref(a), C.byref(b))
+        rc = _load().obca_diag_leave_pattern(int(d), int(mask), value, C.byref(a), C.byref(b))
         if rc != 0:
             raise RuntimeError(f"obca_diag_leave_pattern(device {d}) failed ({rc})")
         out.append((a.value, b.value))

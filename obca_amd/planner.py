@@ -8,10 +8,9 @@ velocity profile -> down-sampling to the horizon N); SURVEY.md section 8f "next-
 import ctypes as C
 import os
 import numpy as np
-from . import buildflags, scenarios as S
+from . import buildflags, cabi, scenarios as S
 
 _LIB = buildflags.PIECES["plan"].out      # obca_planner.cpp + obca_planner_ref.cpp (REFERENCE mode: the reference's Hybrid A* restated)
-_D = C.POINTER(C.c_double); _I = C.POINTER(C.c_int)
 _lib = None
 
 
@@ -22,7 +21,7 @@ def build_library(force=False):
 def _load():
     global _lib
     if _lib is None:
-        _lib = C.CDLL(build_library())
+        _lib = cabi.bind(C.CDLL(build_library()), "obca_plan.h")
     return _lib
 
 
@@ -39,17 +38,19 @@ REFERENCE_GRID = dict(xy_res=0.3, yaw_res_deg=5.0, steer_samples=2)      # (too 
 # mean 43.4 / worst 400 iterations at 1.0, 37.4 / 71 at 0.85, 40.6 / 90 without the expansion), hence 0.85.
 
 
-def hybrid_astar(start, goal, vOb, A, b, ego=S.EGO, L=S.L_WHEELBASE, XYbounds=S.XYBOUNDS, **kw):
-    """start, goal: (x, y, yaw); obstacles as H-rep rows (vOb = rows per obstacle).  Returns (path (K,3), dir (K,), expansions) or None."""
+def _search_args(vOb, A, b, ego, L, XYbounds, kw):
+    """the obstacle field and the options of a Hybrid A* call as the ABI orders them: nOb, vOb, A, b, ego, L, XYbounds, opts, nopts"""
     o = dict(DEFAULT_OPTS); o.update(kw)
     opts = np.array([o[k] for k in DEFAULT_OPTS], float)
-    vOb = np.ascontiguousarray(vOb, np.int32); A = np.ascontiguousarray(A, float); b = np.ascontiguousarray(b, float)
+    vOb = np.ascontiguousarray(vOb, np.int32)
+    return (len(vOb), vOb, *(np.ascontiguousarray(a, float) for a in (A, b, ego)), L, np.ascontiguousarray(XYbounds, float), opts, len(opts))
+
+
+def hybrid_astar(start, goal, vOb, A, b, ego=S.EGO, L=S.L_WHEELBASE, XYbounds=S.XYBOUNDS, **kw):
+    """start, goal: (x, y, yaw); obstacles as H-rep rows (vOb = rows per obstacle).  Returns (path (K,3), dir (K,), expansions) or None."""
     cap = 20000; path = np.zeros((cap, 3)); dr = np.zeros(cap, np.int32); nexp = C.c_int(0)
     s = np.ascontiguousarray(start, float)[:3].copy(); g = np.ascontiguousarray(goal, float)[:3].copy()
-    e = np.ascontiguousarray(ego, float); xy = np.ascontiguousarray(XYbounds, float)
-    n = _load().obca_plan_hybrid_astar2(s.ctypes.data_as(_D), g.ctypes.data_as(_D), C.c_int(len(vOb)), vOb.ctypes.data_as(_I), A.ctypes.data_as(_D),
-                                        b.ctypes.data_as(_D), e.ctypes.data_as(_D), C.c_double(L), xy.ctypes.data_as(_D), opts.ctypes.data_as(_D), C.c_int(len(opts)),
-                                        path.ctypes.data_as(_D), dr.ctypes.data_as(_I), C.c_int(cap), C.byref(nexp))
+    n = _load().obca_plan_hybrid_astar2(s, g, *_search_args(vOb, A, b, ego, L, XYbounds, kw), path, dr, cap, C.byref(nexp))
     if n < 0:
         raise ValueError({-1: "bad arguments", -2: "start or goal pose collides"}[n])
     if n == 0:
@@ -69,8 +70,7 @@ def reference_hybrid_astar(start, goal, ox, oy, **kw):
     ox = np.ascontiguousarray(ox, float); oy = np.ascontiguousarray(oy, float)
     s = np.ascontiguousarray(start, float)[:3].copy(); g = np.ascontiguousarray(goal, float)[:3].copy()
     cap = 20000; path = np.zeros((cap, 3)); nexp = C.c_int(0)
-    n = _load().obca_plan_reference_hybrid_astar(s.ctypes.data_as(_D), g.ctypes.data_as(_D), C.c_int(len(ox)), ox.ctypes.data_as(_D), oy.ctypes.data_as(_D),
-                                                 opts.ctypes.data_as(_D), path.ctypes.data_as(_D), C.c_int(cap), C.byref(nexp))
+    n = _load().obca_plan_reference_hybrid_astar(s, g, len(ox), ox, oy, opts, path, cap, C.byref(nexp))
     if n < 0:
         raise ValueError("bad arguments")
     return None if n == 0 else (path[:n].copy(), nexp.value)
@@ -117,8 +117,7 @@ def reference_astar3d(start, goal, ox, oy, oz, room_min=(0.0, 0.0, 0.0), room_ma
     ox = np.ascontiguousarray(ox, float); oy = np.ascontiguousarray(oy, float); oz = np.ascontiguousarray(oz, float)
     lo = np.ascontiguousarray(room_min, float); hi = np.ascontiguousarray(room_max, float)
     cap = 8192; path = np.zeros((cap, 3)); nexp = C.c_int(0); cost = C.c_double(0)
-    n = _load().obca_plan_reference_astar3d(s.ctypes.data_as(_D), g.ctypes.data_as(_D), C.c_int(len(ox)), ox.ctypes.data_as(_D), oy.ctypes.data_as(_D), oz.ctypes.data_as(_D),
-                                            lo.ctypes.data_as(_D), hi.ctypes.data_as(_D), C.c_double(reso), path.ctypes.data_as(_D), C.c_int(cap), C.byref(nexp), C.byref(cost))
+    n = _load().obca_plan_reference_astar3d(s, g, len(ox), ox, oy, oz, lo, hi, reso, path, cap, C.byref(nexp), C.byref(cost))
     if n < 0:
         raise ValueError("bad arguments")
     return None if n == 0 else (path[:n].copy(), nexp.value, cost.value)
@@ -143,8 +142,7 @@ def reeds_shepp(start, goal, R, step=0.2):
     """shortest Reeds-Shepp path between two poses (x, y, yaw) for turning radius R: returns (path (K,3), dir (K,), word, segment lengths, total)"""
     s = np.ascontiguousarray(start, float)[:3].copy(); g = np.ascontiguousarray(goal, float)[:3].copy()
     cap = 20000; path = np.zeros((cap, 3)); dr = np.zeros(cap, np.int32); word = C.create_string_buffer(8); seg = np.zeros(5); tot = C.c_double(0)
-    n = _load().obca_plan_reeds_shepp(s.ctypes.data_as(_D), g.ctypes.data_as(_D), C.c_double(R), C.c_double(step), path.ctypes.data_as(_D),
-                                      dr.ctypes.data_as(_I), C.c_int(cap), word, seg.ctypes.data_as(_D), C.byref(tot))
+    n = _load().obca_plan_reeds_shepp(s, g, R, step, path, dr, cap, word, seg, C.byref(tot))
     if n < 0:
         raise ValueError("bad arguments")
     w = word.value.decode()
@@ -154,8 +152,7 @@ def reeds_shepp(start, goal, R, step=0.2):
 def collides(pose, vOb, A, b, ego=S.EGO, XYbounds=S.XYBOUNDS, margin=0.0):
     vOb = np.ascontiguousarray(vOb, np.int32); A = np.ascontiguousarray(A, float); b = np.ascontiguousarray(b, float)
     e = np.ascontiguousarray(ego, float); xy = np.ascontiguousarray(XYbounds, float)
-    return bool(_load().obca_plan_collides(C.c_double(pose[0]), C.c_double(pose[1]), C.c_double(pose[2]), C.c_int(len(vOb)), vOb.ctypes.data_as(_I),
-                                           A.ctypes.data_as(_D), b.ctypes.data_as(_D), e.ctypes.data_as(_D), xy.ctypes.data_as(_D), C.c_double(margin)))
+    return bool(_load().obca_plan_collides(pose[0], pose[1], pose[2], len(vOb), vOb, A, b, e, xy, margin))
 
 
 def path_to_warm_start(path, dr, N, xF=None, v_nom=0.5, L=S.L_WHEELBASE, smooth=False):
@@ -265,15 +262,9 @@ def effective_cpus():
 def hybrid_astar_many(starts, goals, vOb, A, b, ego=S.EGO, L=S.L_WHEELBASE, XYbounds=S.XYBOUNDS, threads=0, cap=1024, **kw):
     """B searches in one obstacle field on the host threads of the library (obca_plan_hybrid_astar_batch): returns a list of (path, dir, expansions) / None
     (no path, or the start / goal pose collides)."""
-    o = dict(DEFAULT_OPTS); o.update(kw)
-    opts = np.array([o[k] for k in DEFAULT_OPTS], float)
-    vOb = np.ascontiguousarray(vOb, np.int32); A = np.ascontiguousarray(A, float); b = np.ascontiguousarray(b, float)
     s = np.ascontiguousarray(np.asarray(starts, float)[:, :3]); g = np.ascontiguousarray(np.asarray(goals, float)[:, :3]); B = len(s)
-    e = np.ascontiguousarray(ego, float); xy = np.ascontiguousarray(XYbounds, float)
     paths = np.zeros((B, cap, 3)); dirs = np.zeros((B, cap), np.int32); cnt = np.zeros(B, np.int32); nexp = np.zeros(B, np.int32)
-    rc = _load().obca_plan_hybrid_astar_batch2(C.c_int(B), s.ctypes.data_as(_D), g.ctypes.data_as(_D), C.c_int(len(vOb)), vOb.ctypes.data_as(_I), A.ctypes.data_as(_D),
-                                               b.ctypes.data_as(_D), e.ctypes.data_as(_D), C.c_double(L), xy.ctypes.data_as(_D), opts.ctypes.data_as(_D), C.c_int(len(opts)),
-                                               paths.ctypes.data_as(_D), dirs.ctypes.data_as(_I), C.c_int(cap), cnt.ctypes.data_as(_I), nexp.ctypes.data_as(_I), C.c_int(int(threads or 0)))
+    rc = _load().obca_plan_hybrid_astar_batch2(B, s, g, *_search_args(vOb, A, b, ego, L, XYbounds, kw), paths, dirs, cap, cnt, nexp, int(threads or 0))
     if rc != 0:
         raise ValueError("bad arguments")
     out = []
@@ -310,8 +301,7 @@ def astar3d(start, goal, boxes=None, clear=0.4, room=QUAD_ROOM, res=0.25):
     boxes = np.ascontiguousarray(S.QUAD_OB if boxes is None else boxes, float).reshape(-1, 6)
     s = np.ascontiguousarray(start, float)[:3].copy(); g = np.ascontiguousarray(goal, float)[:3].copy(); rm = np.ascontiguousarray(room, float)
     cap = 4096; path = np.zeros((cap, 3)); nexp = C.c_int(0)
-    n = _load().obca_plan_astar3d(s.ctypes.data_as(_D), g.ctypes.data_as(_D), C.c_int(len(boxes)), boxes.ctypes.data_as(_D), C.c_double(clear),
-                                  rm.ctypes.data_as(_D), C.c_double(res), path.ctypes.data_as(_D), C.c_int(cap), C.byref(nexp))
+    n = _load().obca_plan_astar3d(s, g, len(boxes), boxes, clear, rm, res, path, cap, C.byref(nexp))
     if n == -1:
         raise ValueError("bad arguments")
     return None if n <= 0 else path[:n].copy()
@@ -347,13 +337,7 @@ def _load3d():
     if _lib3d is None:
         if not os.path.exists(_LIB3D):
             raise Plan3DError(f"{_LIB3D} is missing: build it with obca_amd.planner.build_plan3d_library() / __graft_entry__.build(); there is no CPU fallback")
-        lib = C.CDLL(_LIB3D)
-        lib.obca_plan3d_last_error.restype = C.c_char_p; lib.obca_plan3d_last_error.argtypes = [C.c_void_p]
-        lib.obca_plan3d_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]; lib.obca_plan3d_destroy.argtypes = [C.c_void_p]
-        lib.obca_plan3d_paths_batch.argtypes = [C.c_void_p, C.c_int, _D, _D, C.c_int, _D, C.c_double, _D, C.c_double, _D, C.c_int, _I, _I]
-        lib.obca_plan3d_warm_start_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, _D, _D, C.c_int, _D, C.c_double, _D, C.c_double, _D, _I]
-        lib.obca_plan3d_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        _lib3d = lib
+        _lib3d = cabi.bind(C.CDLL(_LIB3D), "obca_plan3d.h")
     return _lib3d
 
 
@@ -375,17 +359,13 @@ def _boxes3d(boxes, B):
     return np.ascontiguousarray(np.broadcast_to(bx, (B,) + bx.shape[-2:]))
 
 
-def _dp(a):
-    return a.ctypes.data_as(_D)
-
-
 def plan3d_paths(starts, goals, boxes=None, clear=0.4, room=QUAD_ROOM, res=0.25, device=0, cap=256):
     """the C call as it is: (paths (B, cap, 3), counts (B,), sweeps (B,), kernel ms).  counts as obca_plan_astar3d returns them per instance; -1: more than cap way-points."""
     s = np.ascontiguousarray(np.asarray(starts, float).reshape(-1, np.shape(starts)[-1])[:, :3]); g = np.ascontiguousarray(np.asarray(goals, float).reshape(-1, np.shape(goals)[-1])[:, :3]); B = len(s)
     bx = _boxes3d(boxes, B); rm = np.ascontiguousarray(room, float)
     paths = np.zeros((B, max(int(cap), 0), 3)); cnt = np.zeros(B, np.int32); sw = np.zeros(B, np.int32); ms = C.c_float(0)
     h = plan3d_context(device); lib = _load3d()
-    if lib.obca_plan3d_paths_batch(h, B, _dp(s), _dp(g), bx.shape[1], _dp(bx), float(clear), _dp(rm), float(res), _dp(paths), int(cap), cnt.ctypes.data_as(_I), sw.ctypes.data_as(_I)) != 0:
+    if lib.obca_plan3d_paths_batch(h, B, s, g, bx.shape[1], bx, clear, rm, res, paths, int(cap), cnt, sw) != 0:
         raise Plan3DError(lib.obca_plan3d_last_error(h).decode())
     lib.obca_plan3d_kernel_ms(h, C.byref(ms))
     return paths, cnt, sw, ms.value
@@ -415,7 +395,7 @@ def quad_warm_start_many(x0, xF, N, boxes=None, clear=0.4, room=QUAD_ROOM, res=0
     bx = _boxes3d(boxes, B); rm = np.ascontiguousarray(room, float)
     xWS = np.zeros((B, int(N) + 1, 12)); cnt = np.zeros(B, np.int32); ms = C.c_float(0)
     h = plan3d_context(device); lib = _load3d()
-    if lib.obca_plan3d_warm_start_batch(h, B, int(N), _dp(a), _dp(b), bx.shape[1], _dp(bx), float(clear), _dp(rm), float(res), _dp(xWS), cnt.ctypes.data_as(_I)) != 0:
+    if lib.obca_plan3d_warm_start_batch(h, B, int(N), a, b, bx.shape[1], bx, clear, rm, res, xWS, cnt) != 0:
         raise Plan3DError(lib.obca_plan3d_last_error(h).decode())
     if np.any((cnt == -1) | (cnt == -3)):
         raise Plan3DError("instances %s: path longer than %d way-points, or the relaxation did not settle" % (np.flatnonzero((cnt == -1) | (cnt == -3)).tolist(), PLAN3D_WS_CAP))

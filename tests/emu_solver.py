@@ -6,18 +6,14 @@ import os
 import numpy as np
 import packing as P
 from obca_amd import buildflags
+from obca_amd.api import Opts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 D = C.POINTER(C.c_double)
 dp = lambda a: a.ctypes.data_as(D)
 
 
-class EOpts(C.Structure):
-    _fields_ = [("tol", C.c_double), ("max_iter", C.c_int)] + \
-        [(n, C.c_double) for n in ("mu_init kappa_eps kappa_mu theta_mu tau_min bound_push bound_frac dw_min dw0 dw_max "
-                                   "kw_inc0 kw_inc kw_dec dc_bar kappa_c gamma_theta gamma_phi delta s_theta s_phi eta_phi "
-                                   "gamma_alpha s_max kappa_sigma constr_viol_tol dual_inf_tol compl_inf_tol rho_term").split()] + \
-        [("max_soc", C.c_int), ("recalc_y", C.c_int), ("lsq_init", C.c_int), ("obj_scaling", C.c_int), ("restoration", C.c_int)]
+EOpts = Opts      # the emulation compiles the kernels' own `obca_opts` (include/obca_hip.h): one record, read from the header
 
 
 _VARIANTS = {None: {}}      # variant -> what it replaces of the table entry "emu" (obca_amd/buildflags.py): output path and flags
