@@ -52,6 +52,7 @@ def _load():
     # batches in flight (profiles/r06_hw_queues.txt).  Read by the runtime at its first call in the process; a value the caller has set stays.
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     _lib = cabi.bind(C.CDLL(_LIBPATH), "obca_hip.h")      # every prototype of the header: the call sites below pass numbers and prepared arrays
+    cabi.bind(_lib, "obca_path_ws.h")                     # the warm start from planner paths: the same library, a header of its own
     return _lib
 
 
@@ -64,6 +65,10 @@ EXPORTS = ["obca_create", "obca_create_multi", "obca_device_count", "obca_visibl
            "obca_quadcopter_default_opts", "obca_quadcopter_reference_opts", "obca_quadcopter_signed_dist_batch", "obca_quadcopter_dist_batch", "obca_quad_batch_create", "obca_quad_batch_destroy",
            "obca_quad_batch_upload", "obca_quad_batch_solve", "obca_quad_batch_sync", "obca_quad_batch_shift_warm_start", "obca_quad_batch_kernel_ms",
            "obca_quad_batch_download", "obca_quad_batch_scratch_bytes"]
+# include/obca_path_ws.h: warm starts from planner paths on the device (planner.path_to_warm_start_many, Batch.set_path_warm_start)
+PATH_WS_EXPORTS = ["obca_parking_path_warm_start_batch", "obca_batch_set_path_warm_start", "obca_batch_path_ws_ms"]
+PATH_WS_MAXNODES = 1024      # OBCA_PATH_WS_MAXNODES
+PATH_WS_STATUS = {0: "written", -1: "no path", -2: "more nodes than rows, or than PATH_WS_MAXNODES", -3: "a non-finite pose", -4: "the path length is not positive"}
 
 
 def selftest(device=0, repeats=4, opts=None):
@@ -241,6 +246,14 @@ def _norm_obstacles(B, vOb, A, b):
     return np.full(B, len(v), np.int32), np.tile(v, B), np.tile(A, (B, 1)), np.tile(b, B)
 
 
+def _path_arrays(paths, dirs, counts, B):
+    """the planner's dense output as the ABI takes it: paths (B, cap, 3) float64, dirs (B, cap) int32, counts (B,) int32 -- arrays of that kind pass unconverted"""
+    paths = _in(paths); dirs = _in(dirs, np.int32); counts = _in(counts, np.int32)
+    if paths.ndim != 3 or paths.shape[0] != B or paths.shape[2] != 3 or dirs.shape != paths.shape[:2] or counts.shape != (B,):
+        raise ObcaError(f"paths must be (B, cap, 3), dirs (B, cap), counts (B,) with B = {B}; got {paths.shape}, {dirs.shape}, {counts.shape}")
+    return paths, dirs, counts, int(paths.shape[1])
+
+
 def _warm_start(xWS, uWS, B, N):
     """xWS (B, >= N+1, 4), uWS (B, >= N, 2) cut to the horizon -- checked here, because the C side reads N+1 / N rows through raw pointers"""
     xWS = np.asarray(xWS, float).reshape(B, -1, 4); uWS = np.asarray(uWS, float).reshape(B, -1, 2)
@@ -331,7 +344,24 @@ class Batch(_DeviceBatch):
         self.nObs, self.Ms, prob = _problem(B, Ts, L, ego, XYbounds, fixTime, x0, xF, vOb, A, b)
         self.vflat = prob[8]
         lWS, nWS = _dual_start(lWS, nWS, int(self.Ms.sum()), int(self.nObs.sum()), N)
-        self._call("upload", *prob, *(_in(np.reshape(r, (B, N + 1))) for r in (rx, ry, ryaw)), *(_in(w) for w in _warm_start(xWS, uWS, B, N)), _in(lWS), _in(nWS))
+        ws = (None, None) if xWS is None and uWS is None else _warm_start(xWS, uWS, B, N)      # (both None: zeros, for a start that set_path_warm_start writes on the device)
+        self._call("upload", *prob, *(_in(np.reshape(r, (B, N + 1))) for r in (rx, ry, ryaw)), *(_in(w) for w in ws), _in(lWS), _in(nWS))
+
+    def set_path_warm_start(self, paths, dirs, counts, v_nom=0.5, smooth=False, use_xF=True):
+        """The warm start of planner.path_to_warm_start, computed ON THE DEVICE from the planner's dense arrays (obca_batch_set_path_warm_start; paths (B, cap, 3), dirs
+        (B, cap), counts (B,) as obca_plan_hybrid_astar_batch2 writes them) and written into the uploaded batch: Ts, the tracking reference, the x / u start, t = 1; the
+        next solve runs DualMultWS.  use_xF: the uploaded goal replaces the last pose; smooth: the speed profile goes through velo_smooth at 0.3 m/s^2.  Returns the status
+        per instance (PATH_WS_STATUS; an instance with a negative one keeps what was uploaded)."""
+        paths, dirs, counts, cap = _path_arrays(paths, dirs, counts, self.B)
+        st = np.zeros(self.B, np.int32)
+        self._call("set_path_warm_start", paths, dirs, counts, cap, bool(use_xF), float(v_nom), 0.3 if smooth else 0.0, st)
+        return st
+
+    def path_ws_ms(self):
+        """HIP-event duration of the last set_path_warm_start kernel"""
+        a = C.c_float(0)
+        self._call("path_ws_ms", C.byref(a))
+        return a.value
 
     def shift_warm_start(self, shift, x0_new=None):
         """receding-horizon restart: the next solve starts from the last solution advanced by `shift` stages (kept on the device)."""

@@ -6,6 +6,7 @@
 //   obca_quad_ipm_kernel    : the same for the quadcopter NLP (obca_quad_solver.h).
 //   obca_dualws_kernel      : one lane per (instance, stage, obstacle) convex sub-problem of DualMultWS (obca_model.h).
 //   obca_validate_*_kernel  : one wavefront per instance, the a-posteriori feasibility classes of a solution or of a caller's trajectory (obca_validate.h).
+//   obca_path_ws_*_kernel   : one wavefront per instance, the parking warm start from a planner path (obca_path_ws.h): into host-bound arrays or into a resident batch.
 //   obca_shift_kernel, obca_quad_shift_kernel : receding-horizon restarts, one workgroup per instance: the warm start of the next solve from the last solution
 //                             (parking: below; quadcopter: obca_quad_shift.h).
 // Memory (per instance, fp64, all in HBM; sizes for N=80, 3 obstacles / 5 rows in brackets):
@@ -26,7 +27,9 @@
 #include "obca_quad_solver.h"
 #include "obca_validate.h"
 #include "obca_quad_shift.h"
+#include "obca_path_ws.h"
 #include "../../include/obca_hip.h"
+#include "../../include/obca_path_ws.h"
 
 using namespace obca;
 #ifdef OBCA_POISON
@@ -37,6 +40,7 @@ using namespace obca;
 
 static_assert(sizeof(obca_opts) == sizeof(OptsAbi) && offsetof(obca_opts, max_soc) == offsetof(OptsAbi, max_soc), "obca_opts must mirror obca::OptsAbi");
 static_assert(OBCA_QUAD_NMAX == QNMAX, "ABI limits must match the kernels");
+static_assert(OBCA_PATH_WS_MAXNODES == PW_MAXNODES, "ABI limits must match the kernels");
 static_assert(OBCA_VMAX == OB_VMAX && OBCA_NOBMAX == OB_NOBMAX && OBCA_NMAX == OB_NMAX && OBCA_MMAX == OB_MMAX, "ABI limits must match the kernels");
 
 struct DevBufs {
@@ -285,6 +289,28 @@ __global__ __launch_bounds__(QNT) void obca_validate_quad_kernel(int B, int N, c
     val::validate_quad_instance(N, prob + (size_t)inst * s_prob, v + ox, v + ou, v + ot, tstride, v + olam, tol, out + (size_t)inst * QV_OUT);
 }
 
+// warm starts from planner paths (obca_path_ws.h): one wavefront per instance.  paths / dirs: B x rows (x 3) dense on the device -- the rows below the longest count of the
+// call --, `cap` the rows of the caller's arrays (what a count is checked against).  Host-pointer call: outputs per instance, zeros where the status is negative.
+__global__ __launch_bounds__(OB_NT) void obca_path_ws_host_kernel(int B, int N, const double *paths, const int *dirs, const int *counts, int rows, int cap, const double *xF /* 4 x B or NULL */,
+                                                                  double v_nom, double L, double a_max, double *Ts, double *xWS, double *uWS, int *status) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    double *ts = Ts + inst, *x = xWS + (size_t)inst * 4 * (N + 1), *u = uWS + (size_t)inst * 2 * N;
+    int st = pw::path_ws_count_status(counts[inst], cap);
+    if (!st) st = pw::path_ws_instance(N, counts[inst], paths + (size_t)inst * rows * 3, dirs + (size_t)inst * rows, xF ? xF + (size_t)inst * 4 : nullptr, v_nom, L, a_max, ts, x, u);
+    if (st) pw::path_ws_zero(N, ts, x, u);
+    if (threadIdx.x == 0) status[inst] = st;
+}
+// resident call: into the problem record and the start iterate of the batch's instances
+__global__ __launch_bounds__(OB_NT) void obca_path_ws_batch_kernel(int B, int N, const double *paths, const int *dirs, const int *counts, int rows, int cap, int use_xF, double v_nom, double a_max,
+                                                                   DevBufs b, int *status) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    const int st = pw::path_ws_record(N, counts[inst], cap, paths + (size_t)inst * rows * 3, dirs + (size_t)inst * rows, use_xF, v_nom, a_max,
+                                      b.prob + (size_t)inst * b.s_prob, b.z0 + (size_t)inst * b.s_z, (int)b.s_z);
+    if (threadIdx.x == 0) status[inst] = st;
+}
+
 // rows of a strided device array <-> a dense staging array (one contiguous PCIe transfer per direction instead of a 2-D copy):
 //   scatter: dst[i * ds + j] = j < W ? src[i * W + j] : 0   for j < zero_to   (upload: primal prefix of the iterate, rest of the row cleared)
 //   gather : dst[i * W + j] = src[i * ss + j]                                   (download: the output prefix of the iterate)
@@ -310,10 +336,12 @@ __global__ __launch_bounds__(256) void obca_gather_rows_kernel(double *dst, size
 struct obca_batch;
 struct obca_quad_batch;
 struct Slot { int device; hipStream_t stream; obca_batch *pb; obca_quad_batch *qb; int cus; };
+namespace { struct PathWsBufs; }
 struct obca_ctx {
     int device; hipStream_t stream;         // primary device / stream (= slots[0]): the device-resident obca_batch_* API runs here
     std::vector<int> devices; std::vector<Slot> slots;
     std::string err; std::string name; int cus;
+    PathWsBufs *pw = nullptr;               // staging of obca_parking_path_warm_start_batch (primary device), created by its first call
 };
 static std::string g_create_err;
 
@@ -361,6 +389,11 @@ struct DevBuf {
         return e;
     }
 };
+// staging of the path warm-start calls (obca_path_ws.h): one device block and its pinned mirror, the events around the kernel
+struct PathWsBufs {
+    DevBuf dev; PinnedBuf host; hipEvent_t e0 = nullptr, e1 = nullptr; int have_ev = 0, timed = 0;
+    void release() { dev.release(); host.release(); if (have_ev) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); } have_ev = timed = 0; }
+};
 }  // namespace
 
 // buffers of the validate calls of a batch: device input (row lengths; a host-pointer call's trajectory extras) and output, their pinned mirrors, the events around the kernel
@@ -395,6 +428,7 @@ struct obca_batch : BatchCore {
     hipEvent_t e2 = nullptr;      // e0 .. e1: DualMultWS, e1 .. e2: interior point
     int sliced = 0;      // slice length (passes) of the last solve if it used the two-launch schedule, else 0
     int val_rl = 0;      // the row lengths of the uploaded instances are in val.d_in (resident validate)
+    PathWsBufs pw;       // obca_batch_set_path_warm_start
 };
 
 #define HIPCHK(bt, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (bt)->err = std::string(#call) + ": " + hipGetErrorString(e_); return -2; } } while (0)
@@ -518,6 +552,7 @@ int obca_destroy(obca_ctx *c) {
         if (s.qb) obca_quad_batch_destroy(s.qb);
         if (s.stream) { use_device(s.device); (void)hipStreamDestroy(s.stream); }
     }
+    if (c->pw) { use_device(c->device); c->pw->release(); delete c->pw; }
     delete c; return 0;
 }
 const char *obca_last_error(const obca_ctx *c) { return c ? c->err.c_str() : g_create_err.c_str(); }
@@ -933,7 +968,7 @@ int obca_batch_create(obca_ctx *ctx, int B, int N, obca_batch **out) {
 int obca_batch_destroy(obca_batch *bt) {
     if (!bt) return -1;
     use_device(bt->device);
-    free_dev(bt); core_release(bt); (void)hipEventDestroy(bt->e2); bt->h_zin.release(); bt->h_zout.release();
+    free_dev(bt); core_release(bt); (void)hipEventDestroy(bt->e2); bt->h_zin.release(); bt->h_zout.release(); bt->pw.release();
     delete bt; return 0;
 }
 #ifdef OBCA_PROFILE
@@ -1058,6 +1093,96 @@ int obca_dualmult_ws_batch(obca_ctx *ctx, int B, int N, const double ego[4], con
     ParkIn in = {Ts.data(), 1.0, ego, XYb, 0, nullptr, nullptr, nOb, vOb, A, b, rx, ry, ryaw, nullptr, nullptr, nullptr, nullptr, {}, {}};
     ParkOut o = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, lWS, nWS, dd};
     return parking_call(ctx, 0, 1, B, N, in, nullptr, o);
+}
+
+}  // extern "C"
+
+// ---- warm starts from planner paths (obca_path_ws.h, include/obca_path_ws.h)
+// What both calls send up, packed on the host into the pinned mirror so that ONE contiguous transfer carries it and only the rows below the longest usable count of the
+// call cross the bus: doubles [ paths B x rows x 3 | xF 4 x B (host-pointer call) ], then ints [ dirs B x rows | counts B ]; behind them, device only, [ status B ] and
+// `out_doubles` of output.  Device pointers in `d`.
+struct PathWsDev { const double *paths, *xF; const int *dirs, *counts; int *status; double *out; int rows; };
+static int path_ws_stage(std::string &err, PathWsBufs &w, hipStream_t stream, int B, const double *paths, const int *dirs, const int *counts, int cap, const double *xF,
+                         size_t out_doubles, PathWsDev &d) {
+    int rows = 0;
+    for (int i = 0; i < B; i++) if (!pw::path_ws_count_status(counts[i], cap)) rows = std::max(rows, counts[i]);
+    const size_t np = (size_t)B * rows * 3, nd = np + (xF ? (size_t)B * 4 : 0), ni = (size_t)B * rows + B, up = nd + (ni + 1) / 2, st = (ni + B + 1) / 2;
+    if (!w.have_ev) {
+        if (hipEventCreate(&w.e0) != hipSuccess) { err = "hipEventCreate failed"; return -2; }
+        if (hipEventCreate(&w.e1) != hipSuccess) { (void)hipEventDestroy(w.e0); err = "hipEventCreate failed"; return -2; }
+        w.have_ev = 1;
+    }
+    if (w.dev.reserve(nd + st + out_doubles, stream) != hipSuccess) { err = "hipMalloc(path warm start) failed"; return -2; }
+    if (w.host.reserve(err, up)) return -2;
+    double *h = w.host; int *hi = (int *)(h + nd);
+    for (int i = 0; i < B; i++) {
+        const int c = pw::path_ws_count_status(counts[i], cap) ? 0 : counts[i];      // nothing of an instance without a usable path is read
+        memcpy(h + (size_t)i * rows * 3, paths + (size_t)i * cap * 3, sizeof(double) * 3 * c);
+        memset(h + (size_t)i * rows * 3 + 3 * (size_t)c, 0, sizeof(double) * 3 * (rows - c));
+        memcpy(hi + (size_t)i * rows, dirs + (size_t)i * cap, sizeof(int) * c);
+        memset(hi + (size_t)i * rows + c, 0, sizeof(int) * (rows - c));
+    }
+    if (xF) memcpy(h + np, xF, sizeof(double) * 4 * B);
+    memcpy(hi + (size_t)B * rows, counts, sizeof(int) * B);
+    if (hipMemcpyAsync(w.dev, w.host, nd * sizeof(double) + ni * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) { err = "path warm start: H2D failed"; return -2; }
+    double *dv = w.dev; int *di = (int *)(dv + nd);
+    d.paths = dv; d.xF = xF ? dv + np : nullptr; d.dirs = di; d.counts = di + (size_t)B * rows; d.status = di + ni; d.out = dv + nd + st; d.rows = rows;
+    return 0;
+}
+
+extern "C" {
+
+int obca_parking_path_warm_start_batch(obca_ctx *ctx, int B, int N, const double *paths, const int *dirs, const int *counts, int cap, const double *xF,
+                                       double v_nom, double L, double a_max, double *Ts, double *xWS, double *uWS, int *status) {
+    if (!ctx) return -1;
+    if (const char *bad = pw::path_ws_check_args(B, N, cap, v_nom, L, a_max, paths && dirs && counts && Ts && xWS && uWS && status)) {
+        ctx->err = std::string("obca_parking_path_warm_start_batch: ") + bad; return -1;
+    }
+    use_device(ctx->device);
+    if (!ctx->pw) ctx->pw = new PathWsBufs();
+    PathWsBufs &w = *ctx->pw;
+    const size_t nx = (size_t)B * 4 * (N + 1), nu = (size_t)B * 2 * N;
+    PathWsDev d;
+    if (int rc = path_ws_stage(ctx->err, w, ctx->stream, B, paths, dirs, counts, cap, xF, (size_t)B + nx + nu, d)) return rc;
+    double *dTs = d.out, *dx = d.out + B, *du = d.out + B + nx;
+    bool ok = hipEventRecord(w.e0, ctx->stream) == hipSuccess;
+    hipLaunchKernelGGL(obca_path_ws_host_kernel, dim3(B), dim3(OB_NT), 0, ctx->stream, B, N, d.paths, d.dirs, d.counts, d.rows, cap, d.xF, v_nom, L, a_max, dTs, dx, du, d.status);
+    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(w.e1, ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(Ts, dTs, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(xWS, dx, nx * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(uWS, du, nu * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(status, d.status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess || !ok) { ctx->err = "obca_parking_path_warm_start_batch: kernel or copy failed"; return -2; }
+    w.timed = 1;
+    return 0;
+}
+
+int obca_batch_set_path_warm_start(obca_batch *bt, const double *paths, const int *dirs, const int *counts, int cap, int use_xF, double v_nom, double a_max, int *status) {
+    if (!bt) return -1;
+    obca_ctx *ctx = bt->ctx;
+    if (!bt->uploaded) { ctx->err = "obca_batch_set_path_warm_start: nothing uploaded"; return -1; }
+    if (const char *bad = pw::path_ws_check_args(bt->B, bt->N, cap, v_nom, 1.0, a_max, paths && dirs && counts && status)) {
+        ctx->err = std::string("obca_batch_set_path_warm_start: ") + bad; return -1;
+    }
+    use_device(bt->device);
+    PathWsBufs &w = bt->pw;
+    PathWsDev d;
+    if (int rc = path_ws_stage(bt->err, w, bt->stream, bt->B, paths, dirs, counts, cap, nullptr, 0, d)) return fin(bt, rc);
+    // from here on the record and the start iterate may be rewritten, whatever becomes of the call: d.z no longer answers the problem, and the start's multipliers
+    // count as cleared -- the next solve runs DualMultWS
+    bt->solved = 0; bt->have_duals = 0;
+    bool ok = hipEventRecord(w.e0, bt->stream) == hipSuccess;
+    hipLaunchKernelGGL(obca_path_ws_batch_kernel, dim3(bt->B), dim3(OB_NT), 0, bt->stream, bt->B, bt->N, d.paths, d.dirs, d.counts, d.rows, cap, use_xF ? 1 : 0, v_nom, a_max, bt->d, d.status);
+    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(w.e1, bt->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(status, d.status, (size_t)bt->B * sizeof(int), hipMemcpyDeviceToHost, bt->stream) == hipSuccess;
+    if (hipStreamSynchronize(bt->stream) != hipSuccess || !ok) { ctx->err = "obca_batch_set_path_warm_start: kernel or copy failed"; return -2; }
+    w.timed = 1;
+    return 0;
+}
+
+int obca_batch_path_ws_ms(obca_batch *bt, float *ms) {
+    if (!bt || !ms) return -1;
+    return core_elapsed_ms(bt, bt->pw.timed != 0, bt->pw.e0, bt->pw.e1, ms, "obca_batch_path_ws_ms: no path warm start has run on this batch");
 }
 
 }  // extern "C"

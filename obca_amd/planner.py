@@ -182,6 +182,22 @@ def path_to_warm_start(path, dr, N, xF=None, v_nom=0.5, L=S.L_WHEELBASE, smooth=
     return Ts, np.stack([X, Y, yaw, v], 1), np.stack([delta, a], 1)
 
 
+def path_to_warm_start_many(paths, dirs, counts, N, xF=None, v_nom=0.5, L=S.L_WHEELBASE, smooth=False, device=0):
+    """path_to_warm_start of a batch ON THE GPU (obca_parking_path_warm_start_batch, include/obca_path_ws.h; one wavefront per instance): paths (B, cap, 3), dirs (B, cap),
+    counts (B,) are the dense arrays obca_plan_hybrid_astar_batch2 writes, xF (B, 4) or None.  Returns (Ts (B,), xWS (B, N+1, 4), uWS (B, N, 2), ok (B,) bool); the rows of an
+    instance without a usable path (count < 2, more than api.PATH_WS_MAXNODES nodes, a non-finite pose, zero length) are zero and its ok False.  smooth: velo_smooth at
+    0.3 m/s^2.  There is no CPU fallback: without the library and a device this raises ObcaError."""
+    from . import api
+    B = len(counts); N = int(N)
+    paths, dirs, counts, cap = api._path_arrays(paths, dirs, counts, B)
+    ctx = api._ctx(device)
+    Ts = np.zeros(B); xWS = np.zeros((B, N + 1, 4)); uWS = np.zeros((B, N, 2)); st = np.zeros(B, np.int32)
+    rc = api._load().obca_parking_path_warm_start_batch(ctx._h, B, N, paths, dirs, counts, cap, None if xF is None else api._in(np.reshape(xF, (B, 4))),
+                                                        float(v_nom), float(L), 0.3 if smooth else 0.0, Ts, xWS, uWS, st)
+    ctx._check(rc, "obca_parking_path_warm_start_batch")
+    return Ts, xWS, uWS, st == 0
+
+
 def velo_smooth(v, amax, Ts):
     """Velocity smoother of the warm-start pipeline (behaviour of AutonomousParking/veloSmooth.jl:29-109, used at main.jl:230-231): the planner's
     speed profile is piecewise constant at +-v_nom (0 at the end); every jump of the profile is replaced by a ramp of slope amax --
@@ -259,14 +275,20 @@ def effective_cpus():
     return n
 
 
-def hybrid_astar_many(starts, goals, vOb, A, b, ego=S.EGO, L=S.L_WHEELBASE, XYbounds=S.XYBOUNDS, threads=0, cap=1024, **kw):
-    """B searches in one obstacle field on the host threads of the library (obca_plan_hybrid_astar_batch): returns a list of (path, dir, expansions) / None
-    (no path, or the start / goal pose collides)."""
+def _hybrid_astar_dense(starts, goals, vOb, A, b, ego, L, XYbounds, threads, cap, kw):
+    """obca_plan_hybrid_astar_batch2 as it is: (starts (B,3), goals (B,3), paths (B,cap,3), dirs (B,cap), counts (B,), expansions (B,))"""
     s = np.ascontiguousarray(np.asarray(starts, float)[:, :3]); g = np.ascontiguousarray(np.asarray(goals, float)[:, :3]); B = len(s)
     paths = np.zeros((B, cap, 3)); dirs = np.zeros((B, cap), np.int32); cnt = np.zeros(B, np.int32); nexp = np.zeros(B, np.int32)
     rc = _load().obca_plan_hybrid_astar_batch2(B, s, g, *_search_args(vOb, A, b, ego, L, XYbounds, kw), paths, dirs, cap, cnt, nexp, int(threads or 0))
     if rc != 0:
         raise ValueError("bad arguments")
+    return s, g, paths, dirs, cnt, nexp
+
+
+def hybrid_astar_many(starts, goals, vOb, A, b, ego=S.EGO, L=S.L_WHEELBASE, XYbounds=S.XYBOUNDS, threads=0, cap=1024, **kw):
+    """B searches in one obstacle field on the host threads of the library (obca_plan_hybrid_astar_batch): returns a list of (path, dir, expansions) / None
+    (no path, or the start / goal pose collides)."""
+    s, g, paths, dirs, cnt, nexp = _hybrid_astar_dense(starts, goals, vOb, A, b, ego, L, XYbounds, threads, cap, kw); B = len(s)
     out = []
     for i in range(B):
         if cnt[i] == -1:          # a path longer than cap nodes (or bad arguments, which the single call reports)
@@ -279,17 +301,31 @@ def hybrid_astar_many(starts, goals, vOb, A, b, ego=S.EGO, L=S.L_WHEELBASE, XYbo
     return out
 
 
-def warm_start_many(sc, x0, xF, N, workers=None, smooth=False, **kw):
+def warm_start_many(sc, x0, xF, N, workers=None, smooth=False, device=None, **kw):
     """warm starts of a batch: the searches run on the host threads of the planner library (one call, no worker processes: safe next to a live HIP runtime, so
-    every rank of a multi-GPU job plans its own slice after its device is up); resampling to the horizon is numpy per instance.  workers = threads (default: all)."""
+    every rank of a multi-GPU job plans its own slice after its device is up); resampling to the horizon is numpy per instance.  workers = threads (default: all).
+    device (an index or an api.Context): the planner's dense arrays go to path_to_warm_start_many unconverted and the resampling runs on that GPU; a path of more than
+    1 024 nodes is searched again on its own and resampled by numpy, as without a device."""
     A, b, vrows = S.scenario_hrep(sc)
     o, v_nom = SCENARIO_OPTS.get(sc["name"], (dict(), 0.5))
     o = dict(o); o.update(kw)
     x0 = np.asarray(x0, float); xF = np.asarray(xF, float)
     if len(x0) == 0:
         return []
-    res = hybrid_astar_many(x0[:, :3], xF[:, :3], vrows, A, b, threads=workers or effective_cpus(), **o)
-    return [None if r is None else path_to_warm_start(r[0], r[1], N, xF[i], v_nom=v_nom, smooth=smooth) for i, r in enumerate(res)]
+    if device is None:
+        res = hybrid_astar_many(x0[:, :3], xF[:, :3], vrows, A, b, threads=workers or effective_cpus(), **o)
+        return [None if r is None else path_to_warm_start(r[0], r[1], N, xF[i], v_nom=v_nom, smooth=smooth) for i, r in enumerate(res)]
+    geo = dict(ego=o.pop("ego", S.EGO), L=o.pop("L", S.L_WHEELBASE), XYbounds=o.pop("XYbounds", S.XYBOUNDS)); cap = o.pop("cap", 1024)      # hybrid_astar_many's named parameters
+    s, g, paths, dirs, cnt, _ = _hybrid_astar_dense(x0[:, :3], xF[:, :3], vrows, A, b, geo["ego"], geo["L"], geo["XYbounds"], workers or effective_cpus(), cap, o)
+    Ts, xWS, uWS, ok = path_to_warm_start_many(paths, dirs, cnt, N, xF, v_nom=v_nom, smooth=smooth, device=device)
+    out = [(float(Ts[i]), xWS[i], uWS[i]) if ok[i] else None for i in range(len(cnt))]
+    for i in np.flatnonzero(cnt == -1):
+        try:
+            r = hybrid_astar(s[i], g[i], vrows, A, b, **geo, **o)
+        except ValueError:
+            r = None
+        out[i] = None if r is None else path_to_warm_start(r[0], r[1], N, xF[i], v_nom=v_nom, smooth=smooth)
+    return out
 
 
 # ---------------------------------------------------------------- quadcopter: 3-D grid A* (a_star_3D.jl, mainQuadcopter.jl:108-138)
