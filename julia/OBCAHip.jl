@@ -352,4 +352,73 @@ function batch_shift_warm_start!(h::Ptr{Cvoid}, shift::Integer; x0_new=nothing)
     return nothing
 end
 
+# ---- clearance between the nodes (include/obca_clearance.h; the entry points live in the same library)
+const CLR = LIB
+const CLR_OUT = 24      # OBCA_CLR_OUT
+
+"the records (24 x B, see include/obca_clearance.h) as a named tuple: min, min_nodes, sample, stage, substep, obstacle, below, samples, per_obstacle (nOb x B), finite"
+function _clearance(rec::Matrix{Float64}, S::Integer, nOb::Integer)
+    q = Int.(rec[3, :])
+    return (min=rec[1, :], min_nodes=rec[2, :], sample=q, stage=[v >= 0 ? div(v, S) : -1 for v in q], substep=[v >= 0 ? rem(v, S) : -1 for v in q], obstacle=Int.(rec[4, :]),
+            below=Int.(rec[5, :]), samples=Int.(rec[6, :]), per_obstacle=rec[9:8+nOb, :], finite=rec[7, :] .== 0)
+end
+
+"""
+    clearance(h, B; substeps=8, need=0.05, nOb=16)
+
+Clearance of the last solution of the resident parking batch `h` (an obca_batch handle of B instances) BETWEEN its nodes: every interval is sampled `substeps` times with the
+discretisation's own partial step, the car's distance to every obstacle is computed anew (0 = touches or overlaps).  `context`: the context `h` was created on.
+"""
+function clearance(h::Ptr{Cvoid}, B::Integer; substeps::Integer=8, need=0.05, nOb::Integer=16, context::Context=ctx())
+    rec = zeros(CLR_OUT, B)
+    rc = ccall((:obca_batch_clearance, CLR), Cint, (Ptr{Cvoid}, Cint, Cdouble, Ptr{Cdouble}), h, substeps, need, rec)
+    rc == 0 || error("obca_batch_clearance failed: " * lasterr(context))
+    return _clearance(rec, substeps, nOb)
+end
+function clearance_ms(h::Ptr{Cvoid})
+    ms = Ref{Cfloat}(0)
+    ccall((:obca_batch_clearance_ms, CLR), Cint, (Ptr{Cvoid}, Ref{Cfloat}), h, ms) == 0 || error("obca_batch_clearance_ms failed")
+    return Float64(ms[])
+end
+
+"the same for the last solution of a QuadBatch: the straight segment of every interval, clearance = distance of the point to a box - R"
+function clearance(b::QuadBatch; substeps::Integer=8, need=0.0)
+    rec = zeros(CLR_OUT, b.B)
+    _qcheck(b, ccall((:obca_quad_batch_clearance, CLR), Cint, (Ptr{Cvoid}, Cint, Cdouble, Ptr{Cdouble}), b.h, substeps, need, rec), "obca_quad_batch_clearance")
+    return _clearance(rec, substeps, 5)
+end
+function clearance_ms(b::QuadBatch)
+    ms = Ref{Cfloat}(0)
+    _qcheck(b, ccall((:obca_quad_batch_clearance_ms, CLR), Cint, (Ptr{Cvoid}, Ref{Cfloat}), b.h, ms), "obca_quad_batch_clearance_ms")
+    return Float64(ms[])
+end
+
+"""
+    ParkingClearance_batch(N, Ts, L, ego, nOb, vOb, A, b, x, u; timeScale=nothing, substeps=8, need=0.05)
+
+Clearance between the nodes of B arbitrary parking trajectories: x 4 x (N+1) x B, u 2 x N x B, timeScale (N+1) x B or nothing (= 1), Ts B; nOb (B, Cint), vOb, A (rows as
+2 x M columns), b packed per instance as for ParkingConstraints_batch.
+"""
+function ParkingClearance_batch(N::Integer, Ts, L, ego, nOb, vOb, A, b, x, u; timeScale=nothing, substeps::Integer=8, need=0.05, context::Context=ctx())
+    xs = f64(x); B = size(xs, 3)
+    ts = timeScale === nothing ? C_NULL : f64(timeScale)
+    rec = zeros(CLR_OUT, B)
+    rc = ccall((:obca_parking_clearance_batch, CLR), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{Cdouble}),
+               context.h, B, N, f64(Ts), L, f64(ego), convert(Array{Cint}, nOb), convert(Array{Cint}, vOb), f64(A), f64(b), xs, f64(u), ts, substeps, need, rec)
+    rc == 0 || error("obca_parking_clearance_batch failed: " * lasterr(context))
+    return _clearance(rec, substeps, Int(maximum(nOb)))
+end
+
+"the same for B quadcopter trajectories: x 12 x (N+1) x B, timeScale (N+1) x B, ob 6 x 5 x B ([hi; -lo] per box), Ts B"
+function QuadcopterClearance_batch(x, timeScale, Ts, ob, R; substeps::Integer=8, need=0.0, context::Context=ctx())
+    xs = f64(x); B = size(xs, 3); N = size(xs, 2) - 1
+    rec = zeros(CLR_OUT, B)
+    rc = ccall((:obca_quadcopter_clearance_batch, CLR), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{Cdouble}),
+               context.h, B, N, f64(Ts), R, f64(ob), xs, f64(timeScale), substeps, need, rec)
+    rc == 0 || error("obca_quadcopter_clearance_batch failed: " * lasterr(context))
+    return _clearance(rec, substeps, 5)
+end
+
 end # module

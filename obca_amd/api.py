@@ -21,7 +21,7 @@ import time
 import numpy as np
 from . import buildflags, cabi
 from .cabi import Opts      # `typedef struct obca_opts` of include/obca_hip.h, read from the header
-from .validate import VIOL_NAMES, QUAD_VIOL_NAMES
+from .validate import VIOL_NAMES, QUAD_VIOL_NAMES, DMIN, CLR_OUT
 
 _LIBPATH = os.environ.get("OBCA_HIP_LIBRARY") or buildflags.PIECES["hip"].out   # override: diagnostic builds
 _lib = None
@@ -53,6 +53,7 @@ def _load():
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     _lib = cabi.bind(C.CDLL(_LIBPATH), "obca_hip.h")      # every prototype of the header: the call sites below pass numbers and prepared arrays
     cabi.bind(_lib, "obca_path_ws.h")                     # the warm start from planner paths: the same library, a header of its own
+    cabi.bind(_lib, "obca_clearance.h")                   # the clearance between the nodes: likewise
     return _lib
 
 
@@ -68,6 +69,9 @@ EXPORTS = ["obca_create", "obca_create_multi", "obca_device_count", "obca_visibl
 # include/obca_path_ws.h: warm starts from planner paths on the device (planner.path_to_warm_start_many, Batch.set_path_warm_start)
 PATH_WS_EXPORTS = ["obca_parking_path_warm_start_batch", "obca_batch_set_path_warm_start", "obca_batch_path_ws_ms"]
 PATH_WS_MAXNODES = 1024      # OBCA_PATH_WS_MAXNODES
+# include/obca_clearance.h: clearance of trajectories between their nodes (Batch.clearance, QuadBatch.clearance, parking_clearance_batch, quadcopter_clearance_batch)
+CLEARANCE_EXPORTS = ["obca_batch_clearance", "obca_batch_clearance_ms", "obca_parking_clearance_batch", "obca_quad_batch_clearance", "obca_quad_batch_clearance_ms",
+                     "obca_quadcopter_clearance_batch"]
 PATH_WS_STATUS = {0: "written", -1: "no path", -2: "more nodes than rows, or than PATH_WS_MAXNODES", -3: "a non-finite pose", -4: "the path length is not positive"}
 
 
@@ -165,6 +169,17 @@ def _verdict(B, names, call, ref_ok=False):
     ok = np.zeros(B, np.int32); rok = [np.zeros(B, np.int32)] if ref_ok else []; viol = np.zeros((B, len(names)))
     call(ok, *rok, viol)
     return dict(ok=ok.astype(bool), **({"ref_ok": rok[0].astype(bool)} if ref_ok else {}), viol=viol, names=names)
+
+
+def _clearance(B, substeps, nOb, call):
+    """the records of a clearance entry point, `call(out)` with out (B, CLR_OUT), and the dict they are returned in: min, min_nodes (B,); sample q = stage * substeps + substep of
+    the minimum, obstacle (-1 where not finite); below = samples whose smallest clearance is < need, samples = N substeps + 1; per_obstacle (B, nOb) (+inf behind an
+    instance's own obstacles); finite (B,) bool -- False: a non-finite number in the trajectory, the values of that instance are NaN"""
+    rec = np.zeros((B, CLR_OUT))
+    call(rec)
+    q = rec[:, 2].astype(np.int64); S = int(substeps)
+    return dict(min=rec[:, 0], min_nodes=rec[:, 1], sample=q, stage=np.where(q >= 0, q // S, -1), substep=np.where(q >= 0, q % S, -1), obstacle=rec[:, 3].astype(np.int64),
+                below=rec[:, 4].astype(np.int64), samples=rec[:, 5].astype(np.int64), per_obstacle=rec[:, 8:8 + int(nOb)], finite=rec[:, 6] == 0)
 
 
 class _Handle:
@@ -331,6 +346,12 @@ class _DeviceBatch(_Handle):
         self._call("validate_ms", C.byref(a))
         return a.value
 
+    def clearance_ms(self):
+        """HIP-event duration of the last clearance kernel"""
+        a = C.c_float(0)
+        self._call("clearance_ms", C.byref(a))
+        return a.value
+
 
 class Batch(_DeviceBatch):
     """Device-resident batch: upload once, solve (repeatedly), download."""
@@ -392,6 +413,13 @@ class Batch(_DeviceBatch):
         parking_constraints_ref_worst): dict(ok (B,) bool -- every class except penetration <= tol --, ref_ok (B,) bool -- the reference's own test at 5e-5 --,
         viol (B, 14) in the order of `names` = VIOL_NAMES).  Only these 16 numbers per instance are downloaded."""
         return _verdict(self.B, VIOL_NAMES, lambda *out: self._call("validate", tol, *out), ref_ok=True)
+
+    def clearance(self, substeps=8, need=DMIN):
+        """Clearance of the last solution BETWEEN its nodes, ON THE DEVICE (obca_batch_clearance; the numpy statement is obca_amd.validate.parking_samples + a DualMultWS
+        distance per pose): every interval is sampled `substeps` times with the discretisation's own partial step and the car's distance to every obstacle computed anew,
+        0 = touches or overlaps.  validate() looks at the nodes only; a solution can pass it and cut a corner in between.  Returns the dict of _clearance; only 24 numbers
+        per instance are downloaded."""
+        return _clearance(self.B, substeps, int(self.nObs.max()), lambda out: self._call("clearance", int(substeps), float(need), out))
 
 
 def parking_signed_dist_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, lWS=None, nWS=None,
@@ -483,6 +511,20 @@ def parking_constraints_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, x, u, 
     ins = (*prob, bool(dist), _in(np.transpose(x, (0, 2, 1))), _in(np.transpose(u, (0, 2, 1))), _time_scale(timeScale, B, N + 1), _pack_cols(l, B, Ms, N + 1, "l"),
            _pack_cols(n, B, 4 * nObs, N + 1, "n"), _pack_cols(sl, B, nObs, N + 1, "sl") if sl is not None else None, tol)
     return _verdict(B, VIOL_NAMES, lambda *out: ctx._check(_load().obca_parking_constraints_batch(ctx._h, B, N, *ins, *out), "obca_parking_constraints_batch"), ref_ok=True)
+
+
+def parking_clearance_batch(N, Ts, L, ego, vOb, A, b, x, u, timeScale=None, substeps=8, need=DMIN, device=0):
+    """Batch.clearance for arbitrary trajectories (obca_parking_clearance_batch): x (B,4,N+1), u (B,2,N) -- the shapes the solve calls return --, timeScale scalar, (B,),
+    (B,N+1) or None (= 1).  The arguments are those of parking_constraints_batch, in its order, that the check reads: no start, goal, bounds or multipliers.  Obstacles and
+    `device` as in parking_signed_dist_batch.  Returns the dict of Batch.clearance."""
+    x = np.asarray(x, float); u = np.asarray(u, float); N = int(N); B = x.shape[0]
+    if x.shape != (B, 4, N + 1) or u.shape != (B, 2, N):
+        raise ObcaError(f"x must be (B,4,N+1) and u (B,2,N); got {x.shape}, {u.shape}")
+    ctx = _ctx(device)
+    nObs, vflat, Aflat, bflat = _norm_obstacles(B, vOb, A, b)
+    ins = (_per_instance(Ts, B), L, _in(ego), _in(nObs, np.int32), _in(vflat, np.int32), _in(Aflat), _in(bflat), _in(np.transpose(x, (0, 2, 1))), _in(np.transpose(u, (0, 2, 1))),
+           None if timeScale is None else _time_scale(timeScale, B, N + 1), int(substeps), float(need))
+    return _clearance(B, substeps, int(nObs.max()), lambda out: ctx._check(_load().obca_parking_clearance_batch(ctx._h, B, N, *ins, out), "obca_parking_clearance_batch"))
 
 
 def ParkingConstraints(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, u, l, n, timeScale, fixTime, sd, device=0):
@@ -584,6 +626,11 @@ class QuadBatch(_DeviceBatch):
         """constrSatisfaction on the last solution, on the device (obca_quad_batch_validate): dict(ok (B,) bool, viol (B, 9) in the order of `names` = QUAD_VIOL_NAMES)"""
         return _verdict(self.B, QUAD_VIOL_NAMES, lambda *out: self._call("validate", tol, *out))
 
+    def clearance(self, substeps=8, need=0.0):
+        """Clearance of the last solution between its nodes, on the device (obca_quad_batch_clearance; numpy: obca_amd.validate.quad_clearance): the straight segment of every
+        interval is sampled `substeps` times, clearance = distance of the point to a box - R (-R inside the box).  Returns the dict of Batch.clearance, 5 obstacles."""
+        return _clearance(self.B, substeps, 5, lambda out: self._call("clearance", int(substeps), float(need), out))
+
 
 def quadcopter_signed_dist_batch(x0, xF, N, Ts, R, ob, xWS, timeWS, dual_ws=True, opts=None, device=0, dist=False):
     """Batched QuadcopterSignedDist / QuadcopterDist through the host-pointer entry points (what the Julia shim calls):
@@ -615,6 +662,17 @@ def quadcopter_constr_satisfaction_batch(x, u, timeScale, x0, xF, Ts, lam, ob, R
            _in(np.transpose(x, (0, 2, 1))), _in(np.transpose(u, (0, 2, 1))), _time_scale(timeScale, B, N1), _in(np.transpose(lam, (0, 2, 1))), tol)
     return _verdict(B, QUAD_VIOL_NAMES, lambda *out: ctx._check(_load().obca_quadcopter_constr_satisfaction_batch(ctx._h, B, N, *ins, *out),
                                                                 "obca_quadcopter_constr_satisfaction_batch"))
+
+
+def quadcopter_clearance_batch(x, timeScale, Ts, ob, R, substeps=8, need=0.0, device=0):
+    """QuadBatch.clearance for arbitrary trajectories (obca_quadcopter_clearance_batch): x (B,12,N+1), timeScale scalar, (B,) or (B,N+1), ob (5,6) shared or (B,5,6) -- the
+    arguments of quadcopter_constr_satisfaction_batch, in its order, that the check reads."""
+    x = np.asarray(x, float); B, _, N1 = x.shape
+    if x.shape != (B, 12, N1):
+        raise ObcaError(f"x must be (B,12,N+1); got {x.shape}")
+    ctx = _ctx(device)
+    ins = (_per_instance(Ts, B), R, _boxes(ob, B), _in(np.transpose(x, (0, 2, 1))), _time_scale(timeScale, B, N1), int(substeps), float(need))
+    return _clearance(B, substeps, 5, lambda out: ctx._check(_load().obca_quadcopter_clearance_batch(ctx._h, B, N1 - 1, *ins, out), "obca_quadcopter_clearance_batch"))
 
 
 def constrSatisfaction(x, u, timeScale, x0, xF, Ts, lam, ob1, ob2, ob3, ob4, ob5, R, device=0):

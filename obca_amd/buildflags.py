@@ -1,5 +1,5 @@
 """ONE place for how every native piece is built: the compile flags, the table of the pieces (PIECES: product library, its diagnostic variants, device and host planner, the
-host emulations of the tests; TEST_PIECES: an emulation only its own tests build) and the one rule that compiles them (compile_if_stale: globbed dependencies, compile aside, rename into place).  The build functions of the
+host emulations of the tests; TEST_PIECES, CHECK_PIECES: emulations only their own tests build) and the one rule that compiles them (compile_if_stale: globbed dependencies, compile aside, rename into place).  The build functions of the
 package, the lazy builds of the tests, __graft_entry__.build() and the shell scripts under tools/ all go through build(NAME):
 
     python -m obca_amd.buildflags build NAME...     builds the named pieces (those that are out of date)
@@ -53,6 +53,9 @@ for _name, _src, _flags, _libs in (("emu", "obca_emu.cpp", ["-O1"], ["-ldl"]), (
 # Emulations that only their own tests build (lazily, through build(NAME) like every piece; __graft_entry__.build() does not compile them): tests/emu/NAME.cpp -> libobca_NAME.so.
 # tests/test_path_ws_cpu.py pins the argv and walks the include closure of path_ws_emu as tests/test_build_cpu.py does for the pieces of PIECES.
 TEST_PIECES = {"path_ws_emu": _piece(GXX, ["-O1"], os.path.join(_EMU, "libobca_path_ws_emu.so"), os.path.join(_EMU, "path_ws_emu.cpp"))}      # obca_amd/csrc/obca_path_ws.h for the host
+# The same kind of piece, in a table of its own because tests/test_path_ws_cpu.py pins TEST_PIECES at its one entry: obca_amd/csrc/obca_clearance.h for the host
+# (tests/test_clearance_cpu.py pins this one's argv and walks its include closure).
+CHECK_PIECES = {"clearance_emu": _piece(GXX, ["-O1"], os.path.join(_EMU, "libobca_clearance_emu.so"), os.path.join(_EMU, "clearance_emu.cpp"))}
 DEFAULT = [n for n in PIECES if n not in ("hip_prof", "hip_poison", "hip_poison_1e30")]      # what __graft_entry__.build() compiles
 
 
@@ -80,9 +83,9 @@ def compile_if_stale(out, cmd, sources, force=False, libs=()):
 
 
 def build(name, force=False, out=None, flags=None):
-    """build a piece of the table (PIECES, or TEST_PIECES); `out` / `flags` replace the entry's output path / extra flags (the OBCA_HIP_LIBRARY override, the checking builds of the emulation,
+    """build a piece of the table (PIECES, TEST_PIECES or CHECK_PIECES); `out` / `flags` replace the entry's output path / extra flags (the OBCA_HIP_LIBRARY override, the checking builds of the emulation,
     the tuning variants of tools/plan3d_rate.py)"""
-    p = PIECES[name] if name in PIECES else TEST_PIECES[name]
+    p = PIECES[name] if name in PIECES else (TEST_PIECES[name] if name in TEST_PIECES else CHECK_PIECES[name])
     return compile_if_stale(out or p.out, p.cc + (p.flags if flags is None else list(flags)), p.sources, force, p.libs)
 
 

@@ -6,6 +6,7 @@
 //   obca_quad_ipm_kernel    : the same for the quadcopter NLP (obca_quad_solver.h).
 //   obca_dualws_kernel      : one lane per (instance, stage, obstacle) convex sub-problem of DualMultWS (obca_model.h).
 //   obca_validate_*_kernel  : one wavefront per instance, the a-posteriori feasibility classes of a solution or of a caller's trajectory (obca_validate.h).
+//   obca_clearance_*_kernel : one wavefront per instance, the clearance of a solution or of a caller's trajectory between its nodes (obca_clearance.h).
 //   obca_path_ws_*_kernel   : one wavefront per instance, the parking warm start from a planner path (obca_path_ws.h): into host-bound arrays or into a resident batch.
 //   obca_shift_kernel, obca_quad_shift_kernel : receding-horizon restarts, one workgroup per instance: the warm start of the next solve from the last solution
 //                             (parking: below; quadcopter: obca_quad_shift.h).
@@ -28,8 +29,10 @@
 #include "obca_validate.h"
 #include "obca_quad_shift.h"
 #include "obca_path_ws.h"
+#include "obca_clearance.h"
 #include "../../include/obca_hip.h"
 #include "../../include/obca_path_ws.h"
+#include "../../include/obca_clearance.h"
 
 using namespace obca;
 #ifdef OBCA_POISON
@@ -41,6 +44,7 @@ using namespace obca;
 static_assert(sizeof(obca_opts) == sizeof(OptsAbi) && offsetof(obca_opts, max_soc) == offsetof(OptsAbi, max_soc), "obca_opts must mirror obca::OptsAbi");
 static_assert(OBCA_QUAD_NMAX == QNMAX, "ABI limits must match the kernels");
 static_assert(OBCA_PATH_WS_MAXNODES == PW_MAXNODES, "ABI limits must match the kernels");
+static_assert(OBCA_CLR_OUT == CL_OUT && OBCA_CLR_MAXSUB == CL_SMAX && OBCA_CLR_TOUCH == CL_TOUCH, "ABI limits must match the kernels");
 static_assert(OBCA_VMAX == OB_VMAX && OBCA_NOBMAX == OB_NOBMAX && OBCA_NMAX == OB_NMAX && OBCA_MMAX == OB_MMAX, "ABI limits must match the kernels");
 
 struct DevBufs {
@@ -289,6 +293,22 @@ __global__ __launch_bounds__(QNT) void obca_validate_quad_kernel(int B, int N, c
     val::validate_quad_instance(N, prob + (size_t)inst * s_prob, v + ox, v + ou, v + ot, tstride, v + olam, tol, out + (size_t)inst * QV_OUT);
 }
 
+// clearance between the nodes (obca_clearance.h): one wavefront per instance; z: points in the solver's layout (resident: the last solution; host-pointer entry: the packed
+// trajectory), ts: (N + 1) timeScale values per instance or NULL (the point's own t); VM: the row class of the batch's widest obstacle, as for obca_dualws_kernel
+template <int VM>
+__global__ __launch_bounds__(OB_NT) void obca_clearance_parking_kernel(int B, int N, const double *prob, size_t s_prob, const double *z, size_t s_z, const double *ts, int S, double need, double *out) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    clr::clearance_parking_instance<VM>(N, prob + (size_t)inst * s_prob, z + (size_t)inst * s_z, ts ? ts + (size_t)inst * (N + 1) : nullptr, S, need, 0, out + (size_t)inst * CL_OUT);
+}
+// x: 12 x (N + 1) per instance at stride s_x, ts[k * tstride] at stride s_ts (resident: both inside the iterate, one t; host-pointer entry: x in the problem record, timeScale beside it)
+__global__ __launch_bounds__(QNT) void obca_clearance_quad_kernel(int B, int N, const double *prob, size_t s_prob, const double *x, size_t s_x, const double *ts, size_t s_ts, int tstride,
+                                                                  int S, double need, double *out) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    clr::clearance_quad_instance(N, prob + (size_t)inst * s_prob, x + (size_t)inst * s_x, ts + (size_t)inst * s_ts, tstride, S, need, 0, out + (size_t)inst * CL_OUT);
+}
+
 // warm starts from planner paths (obca_path_ws.h): one wavefront per instance.  paths / dirs: B x rows (x 3) dense on the device -- the rows below the longest count of the
 // call --, `cap` the rows of the caller's arrays (what a count is checked against).  Host-pointer call: outputs per instance, zeros where the status is negative.
 __global__ __launch_bounds__(OB_NT) void obca_path_ws_host_kernel(int B, int N, const double *paths, const int *dirs, const int *counts, int rows, int cap, const double *xF /* 4 x B or NULL */,
@@ -409,6 +429,7 @@ struct BatchCore {
     PinnedBuf h_prob, h_info;                               // pinned host staging
     hipEvent_t e0 = nullptr, e1 = nullptr;                  // around the kernels of the last solve
     ValBufs val;
+    ValBufs clr;                                            // the same set for the clearance calls (obca_clearance.h): a clearance call leaves validate's row lengths and events alone
     BatchCore(obca_ctx *c, int dev, hipStream_t s, int B_, int N_) : ctx(c), device(dev), stream(s), B(B_), cap(B_), N(N_) {}
 };
 struct obca_quad_batch : BatchCore {
@@ -453,6 +474,10 @@ static int core_validate_ms(BatchCore *bt, float *ms, const char *what) {
     if (!bt || !ms) return -1;
     return core_elapsed_ms(bt, bt->val.timed != 0, bt->val.e0, bt->val.e1, ms, what);
 }
+static int core_clearance_ms(BatchCore *bt, float *ms, const char *what) {
+    if (!bt || !ms) return -1;
+    return core_elapsed_ms(bt, bt->clr.timed != 0, bt->clr.e0, bt->clr.e1, ms, what);
+}
 static int core_scratch_bytes(const BatchCore *bt, long long *bytes) { if (!bt || !bytes) return -1; *bytes = bt->bytes; return 0; }
 #ifdef OBCA_PROFILE      /* the per-phase clocks exist in the profiling build only (libobca_hip_prof.so, tools/phase_profile.py): not an entry point of the product */
 static int core_phase_cycles(BatchCore *bt, const double *prof, double *out /* B x 16 */, const char *what) {
@@ -464,9 +489,11 @@ static int core_phase_cycles(BatchCore *bt, const double *prof, double *out /* B
 #endif
 // everything of the core that a batch's destroy releases, except `stage` (it goes with the family's device buffers); the batch's device is selected
 static void core_release(BatchCore *bt) {
-    ValBufs &v = bt->val;
-    v.d_in.release(); v.d_out.release(); v.h_in.release(); v.h_out.release();
-    if (v.have_ev) { (void)hipEventDestroy(v.e0); (void)hipEventDestroy(v.e1); }
+    for (ValBufs *pv : {&bt->val, &bt->clr}) {
+        ValBufs &v = *pv;
+        v.d_in.release(); v.d_out.release(); v.h_in.release(); v.h_out.release();
+        if (v.have_ev) { (void)hipEventDestroy(v.e0); (void)hipEventDestroy(v.e1); }
+    }
     bt->h_prob.release(); bt->h_info.release();
     (void)hipEventDestroy(bt->e0); (void)hipEventDestroy(bt->e1);
 }
@@ -831,15 +858,14 @@ static int val_reserve(std::string &err, ValBufs &v, size_t in_doubles, size_t o
     if (v.h_in.reserve(err, in_doubles) || v.h_out.reserve(err, out_doubles)) return -2;
     return 0;
 }
-// One validate call over the batch's instances, on its stream: reserve the buffers -> if `upload`, pack(i, row) fills instance i's `s_in` doubles of val.h_in
-// and they travel up to val.d_in (else val.d_in is left as it is) -> launch() between the two events -> the `s_out` result doubles per instance come down -> unpack(i, row) reads instance i's.
+// One validate (v = bt->val) or clearance (v = bt->clr) call over the batch's instances, on its stream: reserve the buffers -> if `upload`, pack(i, row) fills instance i's `s_in` doubles of v.h_in
+// and they travel up to v.d_in (else v.d_in is left as it is) -> launch() between the two events -> the `s_out` result doubles per instance come down -> unpack(i, row) reads instance i's.
 // Synchronises the batch's stream.
 template <typename Pack, typename Launch, typename Unpack>
-static int run_validate(BatchCore *bt, size_t s_in, bool upload, size_t s_out, Pack &&pack, Launch &&launch, Unpack &&unpack) {
+static int run_validate(BatchCore *bt, ValBufs &v, size_t s_in, bool upload, size_t s_out, Pack &&pack, Launch &&launch, Unpack &&unpack) {
     const int B = bt->B;
     use_device(bt->device);
-    if (int rc = val_reserve(bt->err, bt->val, std::max<size_t>(1, (size_t)bt->cap * s_in), (size_t)bt->cap * s_out, bt->stream)) return rc;
-    ValBufs &v = bt->val;
+    if (int rc = val_reserve(bt->err, v, std::max<size_t>(1, (size_t)bt->cap * s_in), (size_t)bt->cap * s_out, bt->stream)) return rc;
     if (upload) {
         for (int i = 0; i < B; i++) pack(i, v.h_in + (size_t)i * s_in);
         HIPCHK(bt, hipMemcpyAsync(v.d_in, v.h_in, (size_t)B * s_in * sizeof(double), hipMemcpyHostToDevice, bt->stream));
@@ -862,7 +888,7 @@ static int batch_validate_range(obca_batch *bt, const double *ts, const double *
     const int B = bt->B, N = bt->N, N1 = N + 1, MMax = bt->MMax;
     const bool host = ts != nullptr;
     const size_t s_aux = (size_t)MMax + (host ? (size_t)N1 + (size_t)bt->nObMax * N1 : 0);
-    const int rc = run_validate(bt, s_aux, host || !bt->val_rl, PV_OUT, [&](int i, double *a) {
+    const int rc = run_validate(bt, bt->val, s_aux, host || !bt->val_rl, PV_OUT, [&](int i, double *a) {
         const double *rl = bt->rowLen.data() + (bt->rowOff[i] - bt->rowOff[0]);
         for (int r = 0; r < MMax; r++) a[r] = r < bt->M[i] ? rl[r] : 1.0;
         if (host) {
@@ -881,6 +907,21 @@ static int batch_validate_range(obca_batch *bt, const double *ts, const double *
     });
     if (!rc && !host) bt->val_rl = 1;      // the row lengths stay in val.d_in until the next upload: the next resident validate skips its H2D
     return rc;
+}
+
+// Clearance between the nodes of the batch's instances (obca_clearance.h): resident (`host` false: the last solution in d.z) or a caller's trajectory that batch_upload_range
+// has just packed into d.z0 (ts: (N + 1) per instance of the call, or nullptr = 1: the t of the packed point).  Instance i of the batch is instance lo + i of the call.
+// Only CL_OUT doubles per instance come back.
+static int batch_clearance_range(obca_batch *bt, bool host, const double *ts, int S, double need, int lo, double *out) {
+    const int B = bt->B, N = bt->N, N1 = N + 1;
+    return run_validate(bt, bt->clr, ts ? (size_t)N1 : 0, ts != nullptr, CL_OUT, [&](int i, double *a) {
+        memcpy(a, ts + ((size_t)lo + i) * N1, sizeof(double) * N1);
+    }, [&] {
+        const double *z = host ? bt->d.z0 : bt->d.z, *dts = ts ? (const double *)bt->clr.d_in : nullptr;
+#define CLR_LAUNCH(VM) hipLaunchKernelGGL(obca_clearance_parking_kernel<VM>, dim3(B), dim3(OB_NT), 0, bt->stream, B, N, (const double *)bt->d.prob, bt->d.s_prob, z, bt->d.s_z, dts, S, need, bt->clr.d_out)
+        if (bt->vmax <= 2) CLR_LAUNCH(2); else if (bt->vmax <= OB_VMID) CLR_LAUNCH(OB_VMID); else CLR_LAUNCH(OB_VMAX);      // (the row class of launch_dualws)
+#undef CLR_LAUNCH
+    }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * CL_OUT, o, sizeof(double) * CL_OUT); });
 }
 
 // ---- chunked execution of a host-pointer call over the slots of the context (work queue)
@@ -1056,6 +1097,37 @@ int obca_parking_constraints_batch(obca_ctx *ctx, int B, int N, const double *Ts
         obca_batch *bt = s.pb; bt->dist = dist ? 1 : 0;
         rc = batch_upload_range(bt, in, lo, cnt);
         if (!rc) rc = batch_validate_range(bt, timeScale, sl, tl, lo, ok, ref_ok, viol);
+        if (rc) err = bt->err;
+        return rc;
+    });
+}
+
+int obca_batch_clearance(obca_batch *bt, int substeps, double need, double *out) {
+    if (!bt) return -1;
+    if (!out) { bt->ctx->err = "obca_batch_clearance: NULL argument"; return -1; }
+    if (const char *bad = clr::clearance_check_args(substeps, need)) { bt->ctx->err = std::string("obca_batch_clearance: ") + bad; return -1; }
+    if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_batch_clearance: nothing has been solved since the last upload or shift"; return -1; }
+    if (bt->N < 1) { bt->ctx->err = "obca_batch_clearance: needs a horizon N>=1"; return -1; }
+    return fin(bt, batch_clearance_range(bt, false, nullptr, substeps, need, 0, out));
+}
+int obca_batch_clearance_ms(obca_batch *bt, float *ms) { return core_clearance_ms(bt, ms, "obca_batch_clearance_ms: no clearance call has run on this batch"); }
+int obca_parking_clearance_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const int *nOb, const int *vOb, const double *A, const double *b,
+                                 const double *x, const double *u, const double *timeScale, int substeps, double need, double *out) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 1 || N > OBCA_NMAX) { ctx->err = "obca_parking_clearance_batch: need B>=1, 1<=N<=OBCA_NMAX"; return -1; }
+    if (!Ts || !ego || !nOb || !vOb || !A || !b || !x || !u || !out) { ctx->err = "obca_parking_clearance_batch: NULL argument"; return -1; }
+    if (const char *bad = clr::clearance_check_args(substeps, need)) { ctx->err = std::string("obca_parking_clearance_batch: ") + bad; return -1; }
+    const std::vector<double> zero((size_t)B * (N + 1), 0.0);      // the tracking reference of a solve: the check does not read it (nor the bounds, the start and the goal)
+    const double XYb[4] = {0, 0, 0, 0};
+    ParkIn in = {Ts, L, ego, XYb, 0, nullptr, nullptr, nOb, vOb, A, b, zero.data(), zero.data(), zero.data(), x, u, nullptr, nullptr, {}, {}};
+    if (int rc = park_prefix(ctx->err, B, nOb, vOb, in)) return rc;
+    const int chunk = pick_chunk(ctx, B, 4);
+    return run_chunks(ctx, B, chunk, [&](Slot &s, int lo, int cnt, std::string &err) -> int {
+        int rc = slot_batch(ctx, s, s.pb, obca_batch_destroy, std::min(chunk, B), std::min(chunk, B), N, err);
+        if (rc) return rc;
+        obca_batch *bt = s.pb; bt->dist = 0;
+        rc = batch_upload_range(bt, in, lo, cnt);
+        if (!rc) rc = batch_clearance_range(bt, true, timeScale, substeps, need, lo, out);
         if (rc) err = bt->err;
         return rc;
     });
@@ -1319,7 +1391,7 @@ static int quad_validate_range(obca_quad_batch *bt, const double *x, const doubl
     const bool host = x != nullptr;
     const size_t nx = (size_t)QX * N1, nu = (size_t)QU * N, nl = (size_t)QL * QOB * N1, W = nx + nu + N1 + nl;
     quad::QLay l; quad::q_make_layout(N, l);
-    return run_validate(bt, host ? W : 0, host, QV_OUT, [&](int i, double *a) {
+    return run_validate(bt, bt->val, host ? W : 0, host, QV_OUT, [&](int i, double *a) {
         const size_t g = (size_t)lo + i;
         memcpy(a, x + g * nx, sizeof(double) * nx); memcpy(a + nx, u + g * nu, sizeof(double) * nu);
         memcpy(a + nx + nu, ts + g * N1, sizeof(double) * N1); memcpy(a + nx + nu + N1, lam + g * nl, sizeof(double) * nl);
@@ -1331,6 +1403,18 @@ static int quad_validate_range(obca_quad_batch *bt, const double *x, const doubl
         if (viol) memcpy(viol + g * QV_NCLS, o, sizeof(double) * QV_NCLS);
         if (ok) ok[g] = o[QV_NCLS] != 0.0;
     });
+}
+// the clearance of the batch's quadcopter instances between their nodes (obca_clearance.h): resident (ts == nullptr: the last solution in d.z, its one t) or a caller's trajectory
+// that quad_upload_range has just put behind the problem header (the slot of the warm start), with ts: (N + 1) per instance of the call
+static int quad_clearance_range(obca_quad_batch *bt, const double *ts, int S, double need, int lo, double *out) {
+    const int B = bt->B, N = bt->N, N1 = N + 1; const QDevBufs &d = bt->d;
+    quad::QLay l; quad::q_make_layout(N, l);
+    return run_validate(bt, bt->clr, ts ? (size_t)N1 : 0, ts != nullptr, CL_OUT, [&](int i, double *a) {
+        memcpy(a, ts + ((size_t)lo + i) * N1, sizeof(double) * N1);
+    }, [&] {
+        if (ts) hipLaunchKernelGGL(obca_clearance_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)d.prob + QPH_SIZE, d.s_prob, (const double *)bt->clr.d_in, (size_t)N1, 1, S, need, bt->clr.d_out);
+        else hipLaunchKernelGGL(obca_clearance_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)d.z + l.x, d.s_z, (const double *)d.z + l.t, d.s_z, 0, S, need, bt->clr.d_out);
+    }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * CL_OUT, o, sizeof(double) * CL_OUT); });
 }
 // instances (one wavefront each) resident per CU, as OBCA_RESIDENT_PER_CU for the parking kernel: what pick_chunk sizes a quadcopter chunk by
 static const int QUAD_RESIDENT_PER_CU = (QNT == 64 ? 4 : 2) * OBCA_QUAD_WAVES_PER_EU;
@@ -1403,6 +1487,32 @@ int obca_quadcopter_constr_satisfaction_batch(obca_ctx *ctx, int B, int N, const
         obca_quad_batch *bt = s.qb;
         rc = quad_upload_range(bt, in, lo, cnt);
         if (!rc) rc = quad_validate_range(bt, x, u, timeScale, lambda, tl, lo, ok, viol);
+        if (rc) err = bt->err;
+        return rc;
+    });
+}
+int obca_quad_batch_clearance(obca_quad_batch *bt, int substeps, double need, double *out) {
+    if (!bt) return -1;
+    if (!out) { bt->ctx->err = "obca_quad_batch_clearance: NULL argument"; return -1; }
+    if (const char *bad = clr::clearance_check_args(substeps, need)) { bt->ctx->err = std::string("obca_quad_batch_clearance: ") + bad; return -1; }
+    if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_quad_batch_clearance: nothing has been solved since the last upload or shift"; return -1; }
+    return fin(bt, quad_clearance_range(bt, nullptr, substeps, need, 0, out));
+}
+int obca_quad_batch_clearance_ms(obca_quad_batch *bt, float *ms) { return core_clearance_ms(bt, ms, "obca_quad_batch_clearance_ms: no clearance call has run on this batch"); }
+int obca_quadcopter_clearance_batch(obca_ctx *ctx, int B, int N, const double *Ts, double R, const double *ob, const double *x, const double *timeScale, int substeps, double need, double *out) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 2 || N > OBCA_QUAD_NMAX) { ctx->err = "obca_quadcopter_clearance_batch: need B>=1, 2<=N<=OBCA_QUAD_NMAX"; return -1; }
+    if (!Ts || !ob || !x || !timeScale || !out) { ctx->err = "obca_quadcopter_clearance_batch: NULL argument"; return -1; }
+    if (const char *bad = clr::clearance_check_args(substeps, need)) { ctx->err = std::string("obca_quadcopter_clearance_batch: ") + bad; return -1; }
+    const std::vector<double> zero((size_t)B * QX, 0.0), one((size_t)B, 1.0);      // start, goal and timeWS of a solve: the check reads none of them
+    const QuadIn in = {Ts, R, zero.data(), zero.data(), ob, x, one.data(), 0, 0};
+    const int chunk = pick_chunk(ctx, B, QUAD_RESIDENT_PER_CU);
+    return run_chunks(ctx, B, chunk, [&](Slot &s, int lo, int cnt, std::string &err) -> int {
+        int rc = slot_batch(ctx, s, s.qb, obca_quad_batch_destroy, cnt, std::min(chunk, B), N, err);
+        if (rc) return rc;
+        obca_quad_batch *bt = s.qb;
+        rc = quad_upload_range(bt, in, lo, cnt);
+        if (!rc) rc = quad_clearance_range(bt, timeScale, substeps, need, lo, out);
         if (rc) err = bt->err;
         return rc;
     });

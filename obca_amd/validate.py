@@ -12,6 +12,8 @@ parking_constraints_full : a correct checker of every constraint class of Parkin
     returning the individual maxima.
 validate_parking : (ok, violations) of one returned parking solution; validate_quadcopter: restatement of
     /root/reference/QuadcopterNavigation/constrSatisfaction.jl:25-204 (tolerance 1e-3; single-index gyroscopic quirk included).
+parking_samples, quad_clearance, clearance_record : the numpy statement of the between-node clearance check (obca_amd/csrc/obca_clearance.h, Batch.clearance):
+    the sample poses of a parking trajectory, the clearance record of a quadcopter trajectory, and the record of any (samples, obstacles) table of clearances.
 Shapes follow the reference: x (4,N+1), u (2,N), l (M,N+1), n (4nOb,N+1), timeScale (N+1,) .
 """
 import numpy as np
@@ -175,3 +177,55 @@ def validate_quadcopter(x, u, timeScale, x0, xF, Ts, lam, ob, R, tol=1e-3):
     bad = w["start"] > tol or w["end"] > tol or w["u_bounds"] > 0 or w["x_bounds"] > 0 or w["dyn"] > tol or w["ts_chain"] > tol or \
         w["dual_pos"] > tol or w["norm"] > tol or w["sep"] > tol
     return (not bad), w
+
+
+# ---------------------------------------------------------------- clearance between the nodes (obca_amd/csrc/obca_clearance.h)
+CLR_OUT = 24          # doubles of a record: min, min_nodes, sample, obstacle, below, samples, bad, 0, then 16 per-obstacle minima
+CLR_TOUCH = 1e-7      # a parking distance below this counts as 0: "touches or overlaps"
+
+
+def _stage_scale(timeScale, N):
+    return np.array(np.broadcast_to(np.ravel(np.asarray(timeScale, float)), (N + 1,)), float)
+
+
+def parking_samples(x, u, timeScale, Ts, L, substeps):
+    """(N S + 1, 3) poses (x, y, yaw) of the samples q = k S + s of a parking trajectory x (4,N+1), u (2,N): sub-step s of interval k is the discretisation's own step
+    (ParkingSignedDist.jl:147-150, `_dyn`) from node k with u_k over (s / S) timeScale[k] Ts; s = 0 and the last sample are the nodes themselves."""
+    x = np.asarray(x, float); u = np.asarray(u, float); N = x.shape[1] - 1; S = int(substeps); ts = _stage_scale(timeScale, N)
+    out = np.zeros((N * S + 1, 3))
+    for k in range(N):
+        out[k * S] = x[:3, k]
+        for s in range(1, S):
+            out[k * S + s] = _dyn(x[:, k], u[:, k], s / S * ts[k], Ts, L)[:3]
+    out[N * S] = x[:3, N]
+    return out
+
+
+def clearance_record(c, substeps, need, finite=True):
+    """the record of a table c (N S + 1, nOb) of clearances: ties of the minimum go to the smallest sample, then the smallest obstacle; `below` counts the samples whose
+    smallest clearance is < need.  Not finite (an input was not, or an entry of c is not): NaN / -1 / below = samples."""
+    c = np.asarray(c, float); nS, nOb = c.shape; S = int(substeps)
+    r = np.zeros(CLR_OUT); r[5] = nS; r[8:] = np.inf
+    if not (finite and np.isfinite(c).all()):
+        r[[0, 1]] = np.nan; r[[2, 3]] = -1; r[4] = nS; r[6] = 1; r[8:] = np.nan
+        return r
+    q, j = np.unravel_index(np.argmin(c), c.shape)      # the first minimum in row-major order: smallest sample, then smallest obstacle
+    nodes = np.r_[np.arange(0, nS - 1, S), nS - 1]
+    r[0] = c[q, j]; r[1] = c[nodes].min(); r[2] = q; r[3] = j; r[4] = int((c.min(axis=1) < need).sum()); r[8:8 + nOb] = c.min(axis=0)
+    return r
+
+
+def quad_clearance(x, timeScale, Ts, ob, R, substeps, need=0.0):
+    """the clearance record of a quadcopter trajectory x (12,N+1): sample (k, s) is the point p_k + (s / S) timeScale[k] Ts v_k (QuadcopterSignedDist.jl:138-140), its
+    clearance to box j (ob (5,6) as [hi; -lo]) the Euclidean distance to the box (0 inside) minus R."""
+    x = np.asarray(x, float); N = x.shape[1] - 1; S = int(substeps); ts = _stage_scale(timeScale, N); ob = np.asarray(ob, float).reshape(5, 6)
+    finite = bool(np.isfinite(x).all() and np.isfinite(ts).all() and np.isfinite(Ts))
+    c = np.zeros((N * S + 1, 5))
+    with np.errstate(invalid="ignore", over="ignore"):
+        for q in range(N * S + 1):
+            k, s = divmod(q, S)
+            pt = x[:3, k] + s / S * ts[k] * Ts * x[6:9, k] if s else x[:3, k]
+            for j in range(5):
+                e = np.maximum(np.maximum(-ob[j, 3:] - pt, pt - ob[j, :3]), 0.0)
+                c[q, j] = np.sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]) - R
+    return clearance_record(c, S, need, finite)
