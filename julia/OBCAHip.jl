@@ -421,4 +421,47 @@ function QuadcopterClearance_batch(x, timeScale, Ts, ob, R; substeps::Integer=8,
     return _clearance(rec, substeps, 5)
 end
 
+# ---- solved parking batches on a finer horizon (include/obca_refine.h; the entry points live in the same library)
+const RFN = LIB
+const REFINE_MAXFACTOR = 32      # OBCA_REFINE_MAXFACTOR
+
+"""
+    refine(dst, src, factor; select=nothing, duals=false) -> status
+
+Instance `select[j]` (0-based indices into the solved resident parking batch `src`; nothing: 0 .. n-1 with n = `count`) becomes instance j of the resident batch `dst`, whose
+horizon is factor times src's: the same NLP with Ts / factor, the tracking reference interpolated, started from the solution -- its nodes, between them the poses
+clearance(substeps=factor) sampled, u held, t = 1.  duals=false: dst's next solve runs DualMultWS; duals=true: stage q starts from the multipliers of stage div(q, factor).
+`dst` and `src` are obca_batch handles of one context.  Returns the status per instance: 0 refined from the solution, 1 from the start iterate, -1 zero start.
+"""
+function refine(dst::Ptr{Cvoid}, src::Ptr{Cvoid}, factor::Integer; select=nothing, count::Integer=0, duals::Bool=false, context::Context=ctx())
+    sel = select === nothing ? C_NULL : convert(Array{Cint}, select)
+    n = select === nothing ? count : length(select)
+    status = zeros(Cint, max(n, 1))
+    rc = ccall((:obca_batch_refine_into, RFN), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Cint}, Cint, Ptr{Cint}), dst, src, factor, duals ? 1 : 0, sel, n, status)
+    rc == 0 || error("obca_batch_refine_into failed: " * lasterr(context))
+    return Int.(status[1:n])
+end
+function refine_ms(dst::Ptr{Cvoid})
+    ms = Ref{Cfloat}(0)
+    ccall((:obca_batch_refine_ms, RFN), Cint, (Ptr{Cvoid}, Ref{Cfloat}), dst, ms) == 0 || error("obca_batch_refine_ms failed")
+    return Float64(ms[])
+end
+
+"""
+    ParkingRefine_batch(N, factor, Ts, L, x, u; timeScale=nothing) -> (Ts_f, x_f, u_f)
+
+The primal part of `refine` for B arbitrary parking trajectories: x 4 x (N+1) x B, u 2 x N x B, timeScale (N+1) x B or nothing (= 1), Ts B.  Returns Ts / factor (B),
+x_f 4 x (factor N + 1) x B and u_f 2 x factor N x B; an instance with a non-finite number among its inputs comes back as NaN.
+"""
+function ParkingRefine_batch(N::Integer, factor::Integer, Ts, L, x, u; timeScale=nothing, context::Context=ctx())
+    xs = f64(x); B = size(xs, 3); Nf = N * factor
+    ts = timeScale === nothing ? C_NULL : f64(timeScale)
+    Tsf = zeros(B); xf = zeros(4, Nf + 1, B); uf = zeros(2, Nf, B)
+    rc = ccall((:obca_parking_refine_batch, RFN), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+               context.h, B, N, factor, f64(Ts), L, xs, f64(u), ts, Tsf, xf, uf)
+    rc == 0 || error("obca_parking_refine_batch failed: " * lasterr(context))
+    return Tsf, xf, uf
+end
+
 end # module

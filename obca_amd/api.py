@@ -54,6 +54,7 @@ def _load():
     _lib = cabi.bind(C.CDLL(_LIBPATH), "obca_hip.h")      # every prototype of the header: the call sites below pass numbers and prepared arrays
     cabi.bind(_lib, "obca_path_ws.h")                     # the warm start from planner paths: the same library, a header of its own
     cabi.bind(_lib, "obca_clearance.h")                   # the clearance between the nodes: likewise
+    cabi.bind(_lib, "obca_refine.h")                      # solved batches on a finer horizon: likewise
     return _lib
 
 
@@ -72,6 +73,10 @@ PATH_WS_MAXNODES = 1024      # OBCA_PATH_WS_MAXNODES
 # include/obca_clearance.h: clearance of trajectories between their nodes (Batch.clearance, QuadBatch.clearance, parking_clearance_batch, quadcopter_clearance_batch)
 CLEARANCE_EXPORTS = ["obca_batch_clearance", "obca_batch_clearance_ms", "obca_parking_clearance_batch", "obca_quad_batch_clearance", "obca_quad_batch_clearance_ms",
                      "obca_quadcopter_clearance_batch"]
+# include/obca_refine.h: solved parking batches on a finer horizon (Batch.refine, parking_refine_batch)
+REFINE_EXPORTS = ["obca_batch_refine_into", "obca_batch_refine_ms", "obca_parking_refine_batch"]
+REFINE_MAXFACTOR = 32      # OBCA_REFINE_MAXFACTOR
+REFINE_STATUS = {0: "refined from the solution", 1: "refined from the start iterate (the last solve failed, or its iterate is not finite)", -1: "zero start (the start iterate is not finite either)"}
 PATH_WS_STATUS = {0: "written", -1: "no path", -2: "more nodes than rows, or than PATH_WS_MAXNODES", -3: "a non-finite pose", -4: "the path length is not positive"}
 
 
@@ -311,6 +316,7 @@ class _DeviceBatch(_Handle):
 
     def __init__(self, ctx, B, N):
         self.ctx, self.B, self.N = ctx, int(B), int(N)
+        self.capacity = self.B      # (B is the number of instances the batch holds: a refine into it may leave fewer)
         self._h = C.c_void_p()
         self._call("create", ctx._h, self.B, self.N, C.byref(self._h), handle=False)
 
@@ -361,7 +367,7 @@ class Batch(_DeviceBatch):
         """lWS/nWS, when given, are packed per instance as (N+1, M_i) / (N+1, 4 nOb_i) row-major blocks (= the reference's
         column-major l (M x N+1) and n (4nOb x N+1))."""
         self._call("set_formulation", bool(dist))
-        B, N = self.B, self.N
+        B = self.B = self.capacity; N = self.N      # (an upload fills the batch)
         self.nObs, self.Ms, prob = _problem(B, Ts, L, ego, XYbounds, fixTime, x0, xF, vOb, A, b)
         self.vflat = prob[8]
         lWS, nWS = _dual_start(lWS, nWS, int(self.Ms.sum()), int(self.nObs.sum()), N)
@@ -420,6 +426,60 @@ class Batch(_DeviceBatch):
         0 = touches or overlaps.  validate() looks at the nodes only; a solution can pass it and cut a corner in between.  Returns the dict of _clearance; only 24 numbers
         per instance are downloaded."""
         return _clearance(self.B, substeps, int(self.nObs.max()), lambda out: self._call("clearance", int(substeps), float(need), out))
+
+
+    def refine(self, factor=2, select=None, duals=False, into=None):
+        """The solved instances `select` (an index array or a boolean mask over this batch's instances; None: all, duplicates allowed) on the horizon factor * N, ON THE
+        DEVICE (obca_batch_refine_into; the numpy statement is obca_amd.validate.refine_parking): the same NLP with Ts / factor, the tracking reference interpolated, and
+        as start the solution itself -- its nodes, between them the poses clearance(substeps=factor) sampled, u held, t = 1.  duals=False: the next solve runs DualMultWS;
+        duals=True: stage q starts from the multipliers of stage q // factor (solve with warm_restart_opts(): about 0.55 of the iterations on the oracle; the default is the
+        safer one).  into: a Batch of this context with horizon factor * N and room for the selection; None: a new one.  Returns (batch, status) with status (n,) int32,
+        REFINE_STATUS: 0 refined from the solution, 1 from the start iterate (the last solve failed or left non-finite numbers), -1 zero start.  The result is uploaded, not
+        solved; only `status` crosses the bus."""
+        if select is None:
+            sel = np.arange(self.B, dtype=np.int32)
+        else:
+            sel = np.asarray(select)
+            sel = np.flatnonzero(sel).astype(np.int32) if sel.dtype == bool else np.ascontiguousarray(sel, np.int32).ravel()
+        n = int(sel.size); factor = int(factor)
+        if n < 1:
+            raise ObcaError("refine: the selection is empty")
+        if sel.min() < 0 or sel.max() >= self.B:
+            raise ObcaError(f"refine: an index outside 0 .. {self.B - 1}")
+        if into is None and not (1 <= factor <= REFINE_MAXFACTOR):
+            raise ObcaError(f"refine: need 1 <= factor <= {REFINE_MAXFACTOR}")
+        dst = into if into is not None else Batch(self.ctx, n, factor * self.N)
+        st = np.zeros(n, np.int32)
+        try:
+            self.ctx._check(_load().obca_batch_refine_into(dst._h, self._h, factor, int(duals), sel, n, st), "obca_batch_refine_into")
+        except ObcaError:
+            if into is None:
+                dst.close()
+            raise
+        dst.B = n; dst.nObs = self.nObs[sel]; dst.Ms = self.Ms[sel]
+        ends = np.cumsum(self.nObs); dst.vflat = np.concatenate([self.vflat[ends[i] - self.nObs[i]:ends[i]] for i in sel.tolist()])
+        return dst, st
+
+    def refine_ms(self):
+        """HIP-event duration of the last refine kernel that wrote into THIS batch (the destination of refine)"""
+        a = C.c_float(0)
+        self._call("refine_ms", C.byref(a))
+        return a.value
+
+
+def parking_refine_batch(N, Ts, L, x, u, timeScale=None, factor=2, device=0):
+    """The primal part of Batch.refine for arbitrary trajectories (obca_parking_refine_batch): x (B,4,N+1), u (B,2,N) -- the shapes the solve calls return --, timeScale scalar,
+    (B,), (B,N+1) or None (= 1), used per stage as in parking_clearance_batch.  Returns dict(Ts (B,) = Ts / factor, x (B,4,factor N+1), u (B,2,factor N)); an instance with a
+    non-finite number among its inputs comes back as NaN."""
+    x = np.asarray(x, float); u = np.asarray(u, float); N = int(N); B = x.shape[0]; r = int(factor)
+    if x.shape != (B, 4, N + 1) or u.shape != (B, 2, N):
+        raise ObcaError(f"x must be (B,4,N+1) and u (B,2,N); got {x.shape}, {u.shape}")
+    ctx = _ctx(device)
+    Nf = N * max(r, 0); Tsf = np.zeros(B); xf = np.zeros((B, Nf + 1, 4)); uf = np.zeros((B, Nf, 2))
+    rc = _load().obca_parking_refine_batch(ctx._h, B, N, r, _per_instance(Ts, B), float(L), _in(np.transpose(x, (0, 2, 1))), _in(np.transpose(u, (0, 2, 1))),
+                                           None if timeScale is None else _time_scale(timeScale, B, N + 1), Tsf, xf, uf)
+    ctx._check(rc, "obca_parking_refine_batch")
+    return dict(Ts=Tsf, x=np.transpose(xf, (0, 2, 1)), u=np.transpose(uf, (0, 2, 1)))
 
 
 def parking_signed_dist_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, lWS=None, nWS=None,

@@ -1,5 +1,5 @@
 """ONE place for how every native piece is built: the compile flags, the table of the pieces (PIECES: product library, its diagnostic variants, device and host planner, the
-host emulations of the tests; TEST_PIECES, CHECK_PIECES: emulations only their own tests build) and the one rule that compiles them (compile_if_stale: globbed dependencies, compile aside, rename into place).  The build functions of the
+host emulations of the tests; TEST_PIECES, CHECK_PIECES, EMU_PIECES: emulations only their own tests build) and the one rule that compiles them (compile_if_stale: globbed dependencies, compile aside, rename into place).  The build functions of the
 package, the lazy builds of the tests, __graft_entry__.build() and the shell scripts under tools/ all go through build(NAME):
 
     python -m obca_amd.buildflags build NAME...     builds the named pieces (those that are out of date)
@@ -56,6 +56,9 @@ TEST_PIECES = {"path_ws_emu": _piece(GXX, ["-O1"], os.path.join(_EMU, "libobca_p
 # The same kind of piece, in a table of its own because tests/test_path_ws_cpu.py pins TEST_PIECES at its one entry: obca_amd/csrc/obca_clearance.h for the host
 # (tests/test_clearance_cpu.py pins this one's argv and walks its include closure).
 CHECK_PIECES = {"clearance_emu": _piece(GXX, ["-O1"], os.path.join(_EMU, "libobca_clearance_emu.so"), os.path.join(_EMU, "clearance_emu.cpp"))}
+# Every later emulation of this kind joins THIS table (the two above are pinned at their one entry by their tests): tests/emu/NAME.cpp -> libobca_NAME.so, -O1, built
+# lazily by its own tests through build(NAME), not by __graft_entry__.build().  refine_emu: obca_amd/csrc/obca_refine.h for the host (tests/test_refine_cpu.py).
+EMU_PIECES = {_n: _piece(GXX, ["-O1"], os.path.join(_EMU, "libobca_%s.so" % _n), os.path.join(_EMU, _n + ".cpp")) for _n in ("refine_emu",)}
 DEFAULT = [n for n in PIECES if n not in ("hip_prof", "hip_poison", "hip_poison_1e30")]      # what __graft_entry__.build() compiles
 
 
@@ -83,9 +86,9 @@ def compile_if_stale(out, cmd, sources, force=False, libs=()):
 
 
 def build(name, force=False, out=None, flags=None):
-    """build a piece of the table (PIECES, TEST_PIECES or CHECK_PIECES); `out` / `flags` replace the entry's output path / extra flags (the OBCA_HIP_LIBRARY override, the checking builds of the emulation,
+    """build a piece of the table (PIECES, TEST_PIECES, CHECK_PIECES or EMU_PIECES); `out` / `flags` replace the entry's output path / extra flags (the OBCA_HIP_LIBRARY override, the checking builds of the emulation,
     the tuning variants of tools/plan3d_rate.py)"""
-    p = PIECES[name] if name in PIECES else (TEST_PIECES[name] if name in TEST_PIECES else CHECK_PIECES[name])
+    p = {**EMU_PIECES, **CHECK_PIECES, **TEST_PIECES, **PIECES}[name]
     return compile_if_stale(out or p.out, p.cc + (p.flags if flags is None else list(flags)), p.sources, force, p.libs)
 
 

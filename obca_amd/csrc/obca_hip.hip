@@ -7,6 +7,7 @@
 //   obca_dualws_kernel      : one lane per (instance, stage, obstacle) convex sub-problem of DualMultWS (obca_model.h).
 //   obca_validate_*_kernel  : one wavefront per instance, the a-posteriori feasibility classes of a solution or of a caller's trajectory (obca_validate.h).
 //   obca_clearance_*_kernel : one wavefront per instance, the clearance of a solution or of a caller's trajectory between its nodes (obca_clearance.h).
+//   obca_refine_*_kernel    : one wavefront per destination instance, a solved parking instance on a finer horizon (obca_refine.h): into a second resident batch or host-bound arrays.
 //   obca_path_ws_*_kernel   : one wavefront per instance, the parking warm start from a planner path (obca_path_ws.h): into host-bound arrays or into a resident batch.
 //   obca_shift_kernel, obca_quad_shift_kernel : receding-horizon restarts, one workgroup per instance: the warm start of the next solve from the last solution
 //                             (parking: below; quadcopter: obca_quad_shift.h).
@@ -30,9 +31,11 @@
 #include "obca_quad_shift.h"
 #include "obca_path_ws.h"
 #include "obca_clearance.h"
+#include "obca_refine.h"
 #include "../../include/obca_hip.h"
 #include "../../include/obca_path_ws.h"
 #include "../../include/obca_clearance.h"
+#include "../../include/obca_refine.h"
 
 using namespace obca;
 #ifdef OBCA_POISON
@@ -45,6 +48,7 @@ static_assert(sizeof(obca_opts) == sizeof(OptsAbi) && offsetof(obca_opts, max_so
 static_assert(OBCA_QUAD_NMAX == QNMAX, "ABI limits must match the kernels");
 static_assert(OBCA_PATH_WS_MAXNODES == PW_MAXNODES, "ABI limits must match the kernels");
 static_assert(OBCA_CLR_OUT == CL_OUT && OBCA_CLR_MAXSUB == CL_SMAX && OBCA_CLR_TOUCH == CL_TOUCH, "ABI limits must match the kernels");
+static_assert(OBCA_REFINE_MAXFACTOR == RF_MAXFACTOR, "ABI limits must match the kernels");
 static_assert(OBCA_VMAX == OB_VMAX && OBCA_NOBMAX == OB_NOBMAX && OBCA_NMAX == OB_NMAX && OBCA_MMAX == OB_MMAX, "ABI limits must match the kernels");
 
 struct DevBufs {
@@ -331,6 +335,23 @@ __global__ __launch_bounds__(OB_NT) void obca_path_ws_batch_kernel(int B, int N,
     if (threadIdx.x == 0) status[inst] = st;
 }
 
+// a solved instance on a finer horizon (obca_refine.h): one wavefront per DESTINATION instance.  Resident call: instance sel[j] of the source batch `s` (horizon N: record, last
+// iterate, start iterate, info) becomes instance j of the batch `d` (horizon r N: record and start iterate, every word of both)
+__global__ __launch_bounds__(OB_NT) void obca_refine_batch_kernel(int n, int N, int r, int duals, const int *sel, DevBufs s, DevBufs d, int *status) {
+    const int j = blockIdx.x;
+    if (j >= n) return;
+    const size_t i = (size_t)sel[j];
+    const int st = rfn::refine_record(N, r, duals, s.prob + i * s.s_prob, s.z + i * s.s_z, s.z0 + i * s.s_z, s.info + i * 8, 0, d.prob + (size_t)j * d.s_prob, d.z0 + (size_t)j * d.s_z, (int)d.s_z);
+    if (threadIdx.x == 0) status[j] = st;
+}
+// host-pointer call: dense arrays per instance, ts: (N + 1) per instance or NULL
+__global__ __launch_bounds__(OB_NT) void obca_refine_host_kernel(int B, int N, int r, const double *Ts, double L, const double *x, const double *u, const double *ts, double *Tsf, double *xf, double *uf) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    const size_t i = inst, Nf = (size_t)N * r;
+    (void)rfn::refine_host_instance(N, r, Ts[i], L, x + i * 4 * (N + 1), u + i * 2 * N, ts ? ts + i * (N + 1) : nullptr, 0, Tsf + i, xf + i * 4 * (Nf + 1), uf + i * 2 * Nf);
+}
+
 // rows of a strided device array <-> a dense staging array (one contiguous PCIe transfer per direction instead of a 2-D copy):
 //   scatter: dst[i * ds + j] = j < W ? src[i * W + j] : 0   for j < zero_to   (upload: primal prefix of the iterate, rest of the row cleared)
 //   gather : dst[i * W + j] = src[i * ss + j]                                   (download: the output prefix of the iterate)
@@ -362,6 +383,7 @@ struct obca_ctx {
     std::vector<int> devices; std::vector<Slot> slots;
     std::string err; std::string name; int cus;
     PathWsBufs *pw = nullptr;               // staging of obca_parking_path_warm_start_batch (primary device), created by its first call
+    PathWsBufs *rf = nullptr;               // the same set for obca_parking_refine_batch
 };
 static std::string g_create_err;
 
@@ -450,6 +472,8 @@ struct obca_batch : BatchCore {
     int sliced = 0;      // slice length (passes) of the last solve if it used the two-launch schedule, else 0
     int val_rl = 0;      // the row lengths of the uploaded instances are in val.d_in (resident validate)
     PathWsBufs pw;       // obca_batch_set_path_warm_start
+    PathWsBufs rf;       // obca_batch_refine_into, this batch the destination: selection and status on the device, the events around the kernel
+    std::vector<int> vmx;                                   // per instance: most rows of one of its obstacles (a refined selection takes its own row class along)
 };
 
 #define HIPCHK(bt, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (bt)->err = std::string(#call) + ": " + hipGetErrorString(e_); return -2; } } while (0)
@@ -580,6 +604,7 @@ int obca_destroy(obca_ctx *c) {
         if (s.stream) { use_device(s.device); (void)hipStreamDestroy(s.stream); }
     }
     if (c->pw) { use_device(c->device); c->pw->release(); delete c->pw; }
+    if (c->rf) { use_device(c->device); c->rf->release(); delete c->rf; }
     delete c; return 0;
 }
 const char *obca_last_error(const obca_ctx *c) { return c ? c->err.c_str() : g_create_err.c_str(); }
@@ -623,23 +648,9 @@ static int park_prefix(std::string &err, int B, const int *nOb, const int *vOb, 
     return 0;
 }
 
-// instances lo .. lo+n-1 of the call become instances 0 .. n-1 of the batch (n <= capacity)
-static int batch_upload_range(obca_batch *bt, const ParkIn &in, int lo, int n) {
+// device buffers of the batch for instances of up to nObMax obstacles and MMax rows (a cached batch keeps the largest shape it has seen); the batch's device is selected
+static int batch_reserve_shape(obca_batch *bt, int nObMax, int MMax) {
     const int N = bt->N, N1 = N + 1;
-    if (n < 1 || n > bt->cap) { bt->err = "obca_batch_upload: more instances than the batch was created for"; return -1; }
-    bt->B = n; bt->solved = 0; bt->val_rl = 0;
-    bt->nOb.assign(n, 0); bt->M.assign(n, 0); bt->obOff.assign(n + 1, 0); bt->rowOff.assign(n + 1, 0);
-    int nObMax = 0, MMax = 0; bt->vmax = 0;
-    for (int i = 0; i < n; i++) {
-        const int g = lo + i;
-        for (int j = in.obOff[g]; j < in.obOff[g + 1]; j++) bt->vmax = std::max(bt->vmax, in.vOb[j]);
-        bt->nOb[i] = in.obOff[g + 1] - in.obOff[g]; bt->M[i] = in.rowOff[g + 1] - in.rowOff[g];
-        bt->obOff[i] = in.obOff[g]; bt->rowOff[i] = in.rowOff[g];
-        nObMax = std::max(nObMax, bt->nOb[i]); MMax = std::max(MMax, bt->M[i]);
-    }
-    bt->obOff[n] = in.obOff[lo + n]; bt->rowOff[n] = in.rowOff[lo + n];
-    bt->rowLen.assign((size_t)(bt->rowOff[n] - bt->rowOff[0]), 1.0);
-    use_device(bt->device);
     const size_t B = bt->cap;
     if (!bt->uploaded || nObMax > bt->nObMax || MMax > bt->MMax) {       // (a cached batch keeps the largest shape it has seen)
         // (re)allocation: the batch counts as empty until every buffer exists -- a failed hipMalloc must leave a state the next call can recover from,
@@ -666,6 +677,29 @@ static int batch_upload_range(obca_batch *bt, const ParkIn &in, int lo, int n) {
 #undef ALLOC
         bt->bytes = (long long)tot;
     }
+    return 0;
+}
+
+// instances lo .. lo+n-1 of the call become instances 0 .. n-1 of the batch (n <= capacity)
+static int batch_upload_range(obca_batch *bt, const ParkIn &in, int lo, int n) {
+    const int N = bt->N, N1 = N + 1;
+    if (n < 1 || n > bt->cap) { bt->err = "obca_batch_upload: more instances than the batch was created for"; return -1; }
+    bt->B = n; bt->solved = 0; bt->val_rl = 0;
+    bt->nOb.assign(n, 0); bt->M.assign(n, 0); bt->obOff.assign(n + 1, 0); bt->rowOff.assign(n + 1, 0); bt->vmx.assign(n, 0);
+    int nObMax = 0, MMax = 0; bt->vmax = 0;
+    for (int i = 0; i < n; i++) {
+        const int g = lo + i;
+        for (int j = in.obOff[g]; j < in.obOff[g + 1]; j++) bt->vmx[i] = std::max(bt->vmx[i], in.vOb[j]);
+        bt->vmax = std::max(bt->vmax, bt->vmx[i]);
+        bt->nOb[i] = in.obOff[g + 1] - in.obOff[g]; bt->M[i] = in.rowOff[g + 1] - in.rowOff[g];
+        bt->obOff[i] = in.obOff[g]; bt->rowOff[i] = in.rowOff[g];
+        nObMax = std::max(nObMax, bt->nOb[i]); MMax = std::max(MMax, bt->M[i]);
+    }
+    bt->obOff[n] = in.obOff[lo + n]; bt->rowOff[n] = in.rowOff[lo + n];
+    bt->rowLen.assign((size_t)(bt->rowOff[n] - bt->rowOff[0]), 1.0);
+    use_device(bt->device);
+    const size_t B = bt->cap;
+    if (int rc = batch_reserve_shape(bt, nObMax, MMax)) return rc;
     const DevBufs &d = bt->d;
     Lay lmax; make_layout(N, bt->nObMax, bt->MMax, lmax);
     const bool duals = in.lWS && in.nWS;
@@ -1009,7 +1043,7 @@ int obca_batch_create(obca_ctx *ctx, int B, int N, obca_batch **out) {
 int obca_batch_destroy(obca_batch *bt) {
     if (!bt) return -1;
     use_device(bt->device);
-    free_dev(bt); core_release(bt); (void)hipEventDestroy(bt->e2); bt->h_zin.release(); bt->h_zout.release(); bt->pw.release();
+    free_dev(bt); core_release(bt); (void)hipEventDestroy(bt->e2); bt->h_zin.release(); bt->h_zout.release(); bt->pw.release(); bt->rf.release();
     delete bt; return 0;
 }
 #ifdef OBCA_PROFILE
@@ -1255,6 +1289,100 @@ int obca_batch_set_path_warm_start(obca_batch *bt, const double *paths, const in
 int obca_batch_path_ws_ms(obca_batch *bt, float *ms) {
     if (!bt || !ms) return -1;
     return core_elapsed_ms(bt, bt->pw.timed != 0, bt->pw.e0, bt->pw.e1, ms, "obca_batch_path_ws_ms: no path warm start has run on this batch");
+}
+
+}  // extern "C"
+
+// ---- solved batches on a finer horizon (obca_refine.h, include/obca_refine.h)
+static int refine_events(std::string &err, PathWsBufs &w) {
+    if (w.have_ev) return 0;
+    if (hipEventCreate(&w.e0) != hipSuccess) { err = "hipEventCreate failed"; return -2; }
+    if (hipEventCreate(&w.e1) != hipSuccess) { (void)hipEventDestroy(w.e0); err = "hipEventCreate failed"; return -2; }
+    w.have_ev = 1;
+    return 0;
+}
+
+extern "C" {
+
+int obca_batch_refine_into(obca_batch *dst, obca_batch *src, int factor, int duals, const int *sel, int n, int *status) {
+    if (!dst || !src) return -1;
+    obca_ctx *ctx = dst->ctx;
+    const char *bad = nullptr;
+    if (!status) bad = "NULL argument";
+    else if (dst == src || dst->ctx != src->ctx || dst->stream != src->stream) bad = "source and destination must be two batches of one context";
+    else if (!src->uploaded || !src->solved) bad = "nothing has been solved on the source since its last upload, shift or path warm start";
+    else if ((bad = rfn::refine_check_args(n, src->N, factor, duals)) != nullptr) {}
+    else if (dst->N != factor * src->N) bad = "the destination's horizon must be factor * the source's";
+    else if (n > dst->cap) bad = "more instances than the destination was created for";
+    for (int j = 0; !bad && sel && j < n; j++) if (sel[j] < 0 || sel[j] >= src->B) bad = "an index outside 0 .. B - 1 of the source";
+    if (!bad && !sel && n > src->B) bad = "an index outside 0 .. B - 1 of the source";
+    if (bad) { ctx->err = std::string("obca_batch_refine_into: ") + bad; return -1; }
+    // the host records of the selection, in its order: the packed outputs of a later download follow the running sums, lambda goes back through the source's row lengths
+    dst->B = n; dst->solved = 0; dst->val_rl = 0;
+    dst->nOb.assign(n, 0); dst->M.assign(n, 0); dst->obOff.assign(n + 1, 0); dst->rowOff.assign(n + 1, 0); dst->vmx.assign(n, 0); dst->rowLen.clear();
+    int nObMax = 0, MMax = 0; dst->vmax = 0;
+    for (int j = 0; j < n; j++) {
+        const int i = sel ? sel[j] : j;
+        dst->nOb[j] = src->nOb[i]; dst->M[j] = src->M[i]; dst->vmx[j] = src->vmx[i];
+        dst->obOff[j + 1] = dst->obOff[j] + dst->nOb[j]; dst->rowOff[j + 1] = dst->rowOff[j] + dst->M[j];
+        const double *rl = src->rowLen.data() + (src->rowOff[i] - src->rowOff[0]);
+        dst->rowLen.insert(dst->rowLen.end(), rl, rl + src->M[i]);
+        nObMax = std::max(nObMax, dst->nOb[j]); MMax = std::max(MMax, dst->M[j]); dst->vmax = std::max(dst->vmax, dst->vmx[j]);
+    }
+    dst->dist = src->dist; dst->fixTime = src->fixTime; dst->have_duals = duals;
+    use_device(dst->device);
+    if (int rc = batch_reserve_shape(dst, nObMax, MMax)) return fin(dst, rc);
+    PathWsBufs &w = dst->rf;
+    if (int rc = refine_events(dst->err, w)) return fin(dst, rc);
+    if (w.dev.reserve((size_t)dst->cap + 1, dst->stream) != hipSuccess) { ctx->err = "obca_batch_refine_into: hipMalloc failed"; return -2; }      // ints: [ sel cap | status cap ]
+    if (w.host.reserve(dst->err, ((size_t)dst->cap + 1) / 2 + 1)) return fin(dst, -2);
+    int *hs = (int *)w.host.p, *dsel = (int *)w.dev.p, *dst_st = dsel + dst->cap;
+    dst->uploaded = 0;      // until the kernel has written every record and every row
+    for (int j = 0; j < n; j++) hs[j] = sel ? sel[j] : j;
+    bool ok = hipMemcpyAsync(dsel, hs, (size_t)n * sizeof(int), hipMemcpyHostToDevice, dst->stream) == hipSuccess;
+    ok = ok && hipEventRecord(w.e0, dst->stream) == hipSuccess;
+    hipLaunchKernelGGL(obca_refine_batch_kernel, dim3(n), dim3(OB_NT), 0, dst->stream, n, src->N, factor, duals, (const int *)dsel, src->d, dst->d, dst_st);
+    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(w.e1, dst->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(status, dst_st, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, dst->stream) == hipSuccess;
+    if (hipStreamSynchronize(dst->stream) != hipSuccess || !ok) { ctx->err = "obca_batch_refine_into: kernel or copy failed"; return -2; }
+    w.timed = 1; dst->uploaded = 1;
+    return 0;
+}
+
+int obca_batch_refine_ms(obca_batch *dst, float *ms) {
+    if (!dst || !ms) return -1;
+    return core_elapsed_ms(dst, dst->rf.timed != 0, dst->rf.e0, dst->rf.e1, ms, "obca_batch_refine_ms: no refine call has written into this batch");
+}
+
+int obca_parking_refine_batch(obca_ctx *ctx, int B, int N, int factor, const double *Ts, double L, const double *x, const double *u, const double *timeScale,
+                              double *Ts_f, double *x_f, double *u_f) {
+    if (!ctx) return -1;
+    const char *bad = rfn::refine_check_args(B, N, factor, 0);
+    if (!bad && !(Ts && x && u && Ts_f && x_f && u_f)) bad = "NULL argument";
+    if (bad) { ctx->err = std::string("obca_parking_refine_batch: ") + bad; return -1; }
+    use_device(ctx->device);
+    if (!ctx->rf) ctx->rf = new PathWsBufs();
+    PathWsBufs &w = *ctx->rf;
+    if (int rc = refine_events(ctx->err, w)) return rc;
+    const size_t Nf = (size_t)N * factor, nx = (size_t)B * 4 * (N + 1), nu = (size_t)B * 2 * N, nt = timeScale ? (size_t)B * (N + 1) : 0, nin = B + nx + nu + nt;
+    const size_t nxf = (size_t)B * 4 * (Nf + 1), nuf = (size_t)B * 2 * Nf;
+    if (w.dev.reserve(nin + B + nxf + nuf, ctx->stream) != hipSuccess) { ctx->err = "obca_parking_refine_batch: hipMalloc failed"; return -2; }
+    if (w.host.reserve(ctx->err, nin)) return -2;
+    double *h = w.host, *d = w.dev;      // one contiguous transfer up: [ Ts B | x | u | timeScale ]
+    memcpy(h, Ts, sizeof(double) * B); memcpy(h + B, x, sizeof(double) * nx); memcpy(h + B + nx, u, sizeof(double) * nu);
+    if (nt) memcpy(h + B + nx + nu, timeScale, sizeof(double) * nt);
+    double *dTsf = d + nin, *dxf = dTsf + B, *duf = dxf + nxf;
+    bool ok = hipMemcpyAsync(d, h, nin * sizeof(double), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    ok = ok && hipEventRecord(w.e0, ctx->stream) == hipSuccess;
+    hipLaunchKernelGGL(obca_refine_host_kernel, dim3(B), dim3(OB_NT), 0, ctx->stream, B, N, factor, (const double *)d, L, (const double *)(d + B), (const double *)(d + B + nx),
+                       (const double *)(nt ? d + B + nx + nu : nullptr), dTsf, dxf, duf);
+    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(w.e1, ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(Ts_f, dTsf, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(x_f, dxf, nxf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(u_f, duf, nuf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess || !ok) { ctx->err = "obca_parking_refine_batch: kernel or copy failed"; return -2; }
+    w.timed = 1;
+    return 0;
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@ validate_parking : (ok, violations) of one returned parking solution; validate_q
     /root/reference/QuadcopterNavigation/constrSatisfaction.jl:25-204 (tolerance 1e-3; single-index gyroscopic quirk included).
 parking_samples, quad_clearance, clearance_record : the numpy statement of the between-node clearance check (obca_amd/csrc/obca_clearance.h, Batch.clearance):
     the sample poses of a parking trajectory, the clearance record of a quadcopter trajectory, and the record of any (samples, obstacles) table of clearances.
+refine_parking : the numpy statement of the refinement of a solved parking instance onto a finer horizon (obca_amd/csrc/obca_refine.h, Batch.refine).
 Shapes follow the reference: x (4,N+1), u (2,N), l (M,N+1), n (4nOb,N+1), timeScale (N+1,) .
 """
 import numpy as np
@@ -198,6 +199,36 @@ def parking_samples(x, u, timeScale, Ts, L, substeps):
         for s in range(1, S):
             out[k * S + s] = _dyn(x[:, k], u[:, k], s / S * ts[k], Ts, L)[:3]
     out[N * S] = x[:3, N]
+    return out
+
+
+def refine_parking(x, u, timeScale, Ts, L, factor, ref=None, lam=None, mu=None):
+    """A parking trajectory x (4,N+1), u (2,N) on the horizon N' = r N, r = factor: the start of the same NLP on a grid of step Ts / r (obca_amd/csrc/obca_refine.h is
+    the device's text of this statement).  With q = k r + s, 0 <= s < r, and q = r N the last node:
+      x'[q] = x[k] at s = 0, else the discretisation's own step `_dyn` from node k with u_k over (s / r) timeScale[k] Ts -- the pose parking_samples(..., substeps=r) gives for
+              sample q, so the refined NLP constrains the very poses the clearance check sampled;  x'[r N] = x[N]
+      u'[q] = u[k] (zero-order hold);  Ts' = Ts / r
+      ref'[q] = ref[k] + (s / r)(ref[k+1] - ref[k]) for the rows of `ref` (3,N+1: rx, ry, ryaw), ref[k] itself at s = 0
+      lam'[q], mu'[q] = the columns q // r of lam (M,N+1) and mu (4nOb,N+1), the last node takes N
+    timeScale: a scalar or (N+1,).  Returns dict(x (4,rN+1), u (2,rN), Ts, ref, lam, mu) -- None where nothing was given."""
+    x = np.asarray(x, float); u = np.asarray(u, float); N = x.shape[1] - 1; r = int(factor); ts = _stage_scale(timeScale, N)
+    assert r >= 1 and u.shape == (2, N) and x.shape[0] == 4
+    Nf = N * r; xf = np.zeros((4, Nf + 1)); uf = np.zeros((2, Nf)); k_of = np.minimum(np.arange(Nf + 1) // r, N)
+    for q in range(Nf + 1):
+        k, s = divmod(q, r)
+        xf[:, q] = _dyn(x[:, k], u[:, k], s / r * ts[k], Ts, L) if s else x[:, k]
+        if q < Nf:
+            uf[:, q] = u[:, k]
+    out = dict(x=xf, u=uf, Ts=Ts / r, ref=None, lam=None, mu=None)
+    if ref is not None:
+        ref = np.asarray(ref, float).reshape(3, N + 1); rf = np.zeros((3, Nf + 1))
+        for q in range(Nf + 1):
+            k, s = divmod(q, r)
+            rf[:, q] = ref[:, k] + (s / r) * (ref[:, k + 1] - ref[:, k]) if s else ref[:, k]
+        out["ref"] = rf
+    for name, a in (("lam", lam), ("mu", mu)):
+        if a is not None:
+            out[name] = np.asarray(a, float)[:, k_of].copy()
     return out
 
 
