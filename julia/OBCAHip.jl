@@ -464,4 +464,48 @@ function ParkingRefine_batch(N::Integer, factor::Integer, Ts, L, x, u; timeScale
     return Tsf, xf, uf
 end
 
+# ---- solved quadcopter batches on a finer horizon (include/obca_quad_subdivide.h; the entry points live in the same library)
+const QSD = LIB
+const QUAD_SUBDIVIDE_MAXFACTOR = 32      # OBCA_QUAD_SUBDIVIDE_MAXFACTOR
+
+"""
+    refine(dst::QuadBatch, src::QuadBatch, factor; select=nothing, margin=0.0) -> status
+
+Instance `select[j]` (0-based indices into the solved resident batch `src`; nothing: all of them) becomes instance j of the resident batch `dst`, whose horizon is factor times
+src's: the same NLP with Ts / factor and the radius R + margin, warm-started from the solution -- its nodes, between them the points clearance(substeps=factor) sampled and the
+other nine states interpolated, timeWS = the solution's t, closed-form duals.  `validate` and `clearance` of `dst` use R + margin: clearance against the true radius is
+`clearance(dst; need=-margin)`.  Returns the status per instance: 0 refined from the solution, 1 interpolated from the uploaded warm start, -1 zero warm start.
+"""
+function refine(dst::QuadBatch, src::QuadBatch, factor::Integer; select=nothing, margin=0.0)
+    sel = select === nothing ? C_NULL : convert(Array{Cint}, select)
+    n = select === nothing ? src.B : length(select)
+    status = zeros(Cint, max(n, 1))
+    _qcheck(dst, ccall((:obca_quad_batch_subdivide_into, QSD), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Ptr{Cint}, Cint, Ptr{Cint}), dst.h, src.h, factor, margin, sel, n, status),
+            "obca_quad_batch_subdivide_into")
+    dst.B = n
+    return Int.(status[1:n])
+end
+function refine_ms(dst::QuadBatch)
+    ms = Ref{Cfloat}(0)
+    _qcheck(dst, ccall((:obca_quad_batch_subdivide_ms, QSD), Cint, (Ptr{Cvoid}, Ref{Cfloat}), dst.h, ms), "obca_quad_batch_subdivide_ms")
+    return Float64(ms[])
+end
+
+"""
+    QuadcopterRefine_batch(factor, Ts, x; timeScale=nothing) -> (Ts_f, x_f)
+
+The trajectory part of `refine` for B arbitrary quadcopter trajectories: x 12 x (N+1) x B, timeScale (N+1) x B or nothing (= 1), Ts B.  Returns Ts / factor (B) and
+x_f 12 x (factor N + 1) x B; an instance with a non-finite number among its inputs comes back as NaN.
+"""
+function QuadcopterRefine_batch(factor::Integer, Ts, x; timeScale=nothing, context::Context=ctx())
+    xs = f64(x); B = size(xs, 3); N = size(xs, 2) - 1
+    ts = timeScale === nothing ? C_NULL : f64(timeScale)
+    Tsf = zeros(B); xf = zeros(12, N * factor + 1, B)
+    rc = ccall((:obca_quadcopter_subdivide_batch, QSD), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+               context.h, B, N, factor, f64(Ts), xs, ts, Tsf, xf)
+    rc == 0 || error("obca_quadcopter_subdivide_batch failed: " * lasterr(context))
+    return Tsf, xf
+end
+
 end # module

@@ -55,6 +55,7 @@ def _load():
     cabi.bind(_lib, "obca_path_ws.h")                     # the warm start from planner paths: the same library, a header of its own
     cabi.bind(_lib, "obca_clearance.h")                   # the clearance between the nodes: likewise
     cabi.bind(_lib, "obca_refine.h")                      # solved batches on a finer horizon: likewise
+    cabi.bind(_lib, "obca_quad_subdivide.h")              # ... and solved quadcopter batches
     return _lib
 
 
@@ -76,6 +77,11 @@ CLEARANCE_EXPORTS = ["obca_batch_clearance", "obca_batch_clearance_ms", "obca_pa
 # include/obca_refine.h: solved parking batches on a finer horizon (Batch.refine, parking_refine_batch)
 REFINE_EXPORTS = ["obca_batch_refine_into", "obca_batch_refine_ms", "obca_parking_refine_batch"]
 REFINE_MAXFACTOR = 32      # OBCA_REFINE_MAXFACTOR
+# include/obca_quad_subdivide.h: solved quadcopter batches on a finer horizon (QuadBatch.refine, quadcopter_refine_batch)
+QUAD_SUBDIVIDE_EXPORTS = ["obca_quad_batch_subdivide_into", "obca_quad_batch_subdivide_ms", "obca_quadcopter_subdivide_batch"]
+QUAD_SUBDIVIDE_MAXFACTOR = 32      # OBCA_QUAD_SUBDIVIDE_MAXFACTOR
+QUAD_REFINE_STATUS = {0: "refined from the solution", 1: "interpolated from the uploaded warm start (the last solve failed, or its iterate is not finite)",
+                      -1: "zero warm start (the uploaded one is not finite either)"}
 REFINE_STATUS = {0: "refined from the solution", 1: "refined from the start iterate (the last solve failed, or its iterate is not finite)", -1: "zero start (the start iterate is not finite either)"}
 PATH_WS_STATUS = {0: "written", -1: "no path", -2: "more nodes than rows, or than PATH_WS_MAXNODES", -3: "a non-finite pose", -4: "the path length is not positive"}
 
@@ -660,7 +666,7 @@ class QuadBatch(_DeviceBatch):
     _c = "obca_quad_batch"
 
     def upload(self, x0, xF, Ts, R, ob, xWS, timeWS, dual_ws=True, dist=False):
-        B, N = self.B, self.N
+        B = self.B = self.capacity; N = self.N      # (an upload fills the batch)
         xw = _in(np.asarray(xWS, float)[:, :N + 1]); assert xw.shape == (B, N + 1, 12)
         self._call("upload", _per_instance(Ts, B), R, _in(np.reshape(x0, (B, 12))), _in(np.reshape(xF, (B, 12))), _boxes(ob, B), xw, _per_instance(timeWS, B), bool(dual_ws), bool(dist))
 
@@ -690,6 +696,60 @@ class QuadBatch(_DeviceBatch):
         """Clearance of the last solution between its nodes, on the device (obca_quad_batch_clearance; numpy: obca_amd.validate.quad_clearance): the straight segment of every
         interval is sampled `substeps` times, clearance = distance of the point to a box - R (-R inside the box).  Returns the dict of Batch.clearance, 5 obstacles."""
         return _clearance(self.B, substeps, 5, lambda out: self._call("clearance", int(substeps), float(need), out))
+
+    def refine(self, factor=2, select=None, margin=0.0, into=None):
+        """The solved instances `select` (an index array or a boolean mask over this batch's instances; None: all, duplicates allowed) on the horizon factor * N, ON THE
+        DEVICE (obca_quad_batch_subdivide_into; the numpy statement is obca_amd.validate.refine_quad): the same NLP with Ts / factor and the radius R + margin, and as
+        warm start the solution itself -- its nodes, between them the points clearance(substeps=factor) sampled (the forward-Euler partial step) and the other nine states
+        interpolated; timeWS = the solution's t, closed-form duals, as shift_warm_start leaves them.  A finer grid shrinks the cut between the nodes roughly with the square of
+        the step; the chord across a box's rounded corner still sags inside, and a small margin (0.005 at N = 60 x 2, 0.02 at N = 20 x 4 on make_quad_batch) closes it.
+        validate() and clearance() of the result use R + margin: clearance against the TRUE radius is clearance(need=-margin).  into: a QuadBatch of this context with
+        horizon factor * N and room for the selection; None: a new one.  Returns (batch, status) with status (n,) int32, QUAD_REFINE_STATUS: 0 refined from the solution,
+        1 interpolated from the uploaded warm start (the last solve failed or left non-finite numbers), -1 zero warm start.  The result is uploaded, not solved; only the
+        selection and `status` cross the bus."""
+        if select is None:
+            sel = np.arange(self.B, dtype=np.int32)
+        else:
+            sel = np.asarray(select)
+            sel = np.flatnonzero(sel).astype(np.int32) if sel.dtype == bool else np.ascontiguousarray(sel, np.int32).ravel()
+        n = int(sel.size); factor = int(factor)
+        if n < 1:
+            raise ObcaError("refine: the selection is empty")
+        if sel.min() < 0 or sel.max() >= self.B:
+            raise ObcaError(f"refine: an index outside 0 .. {self.B - 1}")
+        if into is None and not (1 <= factor <= QUAD_SUBDIVIDE_MAXFACTOR):
+            raise ObcaError(f"refine: need 1 <= factor <= {QUAD_SUBDIVIDE_MAXFACTOR}")
+        dst = into if into is not None else QuadBatch(self.ctx, n, factor * self.N)
+        st = np.zeros(n, np.int32)
+        try:
+            self.ctx._check(_load().obca_quad_batch_subdivide_into(dst._h, self._h, factor, float(margin), sel, n, st), "obca_quad_batch_subdivide_into")
+        except ObcaError:
+            if into is None:
+                dst.close()
+            raise
+        dst.B = n
+        return dst, st
+
+    def refine_ms(self):
+        """HIP-event duration of the last refine kernel that wrote into THIS batch (the destination of refine)"""
+        a = C.c_float(0)
+        self._call("subdivide_ms", C.byref(a))
+        return a.value
+
+
+def quadcopter_refine_batch(x, timeScale, Ts, factor=2, device=0):
+    """The trajectory part of QuadBatch.refine for arbitrary trajectories (obca_quadcopter_subdivide_batch): x (B,12,N+1), timeScale scalar, (B,), (B,N+1) or None (= 1), used
+    per stage -- the arguments of quadcopter_clearance_batch that the call reads.  Returns dict(Ts (B,) = Ts / factor, x (B,12,factor N+1)); an instance with a non-finite
+    number among its inputs comes back as NaN."""
+    x = np.asarray(x, float); B, _, N1 = x.shape; N = N1 - 1; r = int(factor)
+    if x.shape != (B, 12, N1):
+        raise ObcaError(f"x must be (B,12,N+1); got {x.shape}")
+    ctx = _ctx(device)
+    Tsf = np.zeros(B); xf = np.zeros((B, N * max(r, 0) + 1, 12))
+    rc = _load().obca_quadcopter_subdivide_batch(ctx._h, B, N, r, _per_instance(Ts, B), _in(np.transpose(x, (0, 2, 1))),
+                                                 None if timeScale is None else _time_scale(timeScale, B, N1), Tsf, xf)
+    ctx._check(rc, "obca_quadcopter_subdivide_batch")
+    return dict(Ts=Tsf, x=np.transpose(xf, (0, 2, 1)))
 
 
 def quadcopter_signed_dist_batch(x0, xF, N, Ts, R, ob, xWS, timeWS, dual_ws=True, opts=None, device=0, dist=False):
@@ -725,13 +785,13 @@ def quadcopter_constr_satisfaction_batch(x, u, timeScale, x0, xF, Ts, lam, ob, R
 
 
 def quadcopter_clearance_batch(x, timeScale, Ts, ob, R, substeps=8, need=0.0, device=0):
-    """QuadBatch.clearance for arbitrary trajectories (obca_quadcopter_clearance_batch): x (B,12,N+1), timeScale scalar, (B,) or (B,N+1), ob (5,6) shared or (B,5,6) -- the
-    arguments of quadcopter_constr_satisfaction_batch, in its order, that the check reads."""
+    """QuadBatch.clearance for arbitrary trajectories (obca_quadcopter_clearance_batch): x (B,12,N+1), timeScale scalar, (B,), (B,N+1) or None (= 1), ob (5,6) shared or
+    (B,5,6) -- the arguments of quadcopter_constr_satisfaction_batch, in its order, that the check reads."""
     x = np.asarray(x, float); B, _, N1 = x.shape
     if x.shape != (B, 12, N1):
         raise ObcaError(f"x must be (B,12,N+1); got {x.shape}")
     ctx = _ctx(device)
-    ins = (_per_instance(Ts, B), R, _boxes(ob, B), _in(np.transpose(x, (0, 2, 1))), _time_scale(timeScale, B, N1), int(substeps), float(need))
+    ins = (_per_instance(Ts, B), R, _boxes(ob, B), _in(np.transpose(x, (0, 2, 1))), _time_scale(1.0 if timeScale is None else timeScale, B, N1), int(substeps), float(need))
     return _clearance(B, substeps, 5, lambda out: ctx._check(_load().obca_quadcopter_clearance_batch(ctx._h, B, N1 - 1, *ins, out), "obca_quadcopter_clearance_batch"))
 
 

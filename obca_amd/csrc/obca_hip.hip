@@ -8,6 +8,7 @@
 //   obca_validate_*_kernel  : one wavefront per instance, the a-posteriori feasibility classes of a solution or of a caller's trajectory (obca_validate.h).
 //   obca_clearance_*_kernel : one wavefront per instance, the clearance of a solution or of a caller's trajectory between its nodes (obca_clearance.h).
 //   obca_refine_*_kernel    : one wavefront per destination instance, a solved parking instance on a finer horizon (obca_refine.h): into a second resident batch or host-bound arrays.
+//   obca_quad_subdivide_*_kernel : the same for a solved quadcopter instance (obca_quad_subdivide.h): it rewrites a problem record.
 //   obca_path_ws_*_kernel   : one wavefront per instance, the parking warm start from a planner path (obca_path_ws.h): into host-bound arrays or into a resident batch.
 //   obca_shift_kernel, obca_quad_shift_kernel : receding-horizon restarts, one workgroup per instance: the warm start of the next solve from the last solution
 //                             (parking: below; quadcopter: obca_quad_shift.h).
@@ -32,10 +33,12 @@
 #include "obca_path_ws.h"
 #include "obca_clearance.h"
 #include "obca_refine.h"
+#include "obca_quad_subdivide.h"
 #include "../../include/obca_hip.h"
 #include "../../include/obca_path_ws.h"
 #include "../../include/obca_clearance.h"
 #include "../../include/obca_refine.h"
+#include "../../include/obca_quad_subdivide.h"
 
 using namespace obca;
 #ifdef OBCA_POISON
@@ -352,6 +355,23 @@ __global__ __launch_bounds__(OB_NT) void obca_refine_host_kernel(int B, int N, i
     (void)rfn::refine_host_instance(N, r, Ts[i], L, x + i * 4 * (N + 1), u + i * 2 * N, ts ? ts + i * (N + 1) : nullptr, 0, Tsf + i, xf + i * 4 * (Nf + 1), uf + i * 2 * Nf);
 }
 
+// a solved quadcopter instance on a finer horizon (obca_quad_subdivide.h): one wavefront per DESTINATION instance.  Resident call: instance sel[j] of the source batch `s`
+// (horizon N: record, last iterate, info) becomes instance j of the batch `d` (horizon r N: every word of its problem record)
+__global__ __launch_bounds__(QNT) void obca_quad_subdivide_batch_kernel(int n, int N, int r, double margin, const int *sel, QDevBufs s, QDevBufs d, int *status) {
+    const int j = blockIdx.x;
+    if (j >= n) return;
+    const size_t i = (size_t)sel[j];
+    const int st = qsd::subdivide_record(N, r, margin, s.prob + i * s.s_prob, s.z + i * s.s_z, s.info + i * 8, 0, d.prob + (size_t)j * d.s_prob);
+    if (threadIdx.x == 0) status[j] = st;
+}
+// host-pointer call: dense arrays per instance, ts: (N + 1) per instance or NULL
+__global__ __launch_bounds__(QNT) void obca_quad_subdivide_host_kernel(int B, int N, int r, const double *Ts, const double *x, const double *ts, double *Tsf, double *xf) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    const size_t i = inst;
+    (void)qsd::subdivide_host_instance(N, r, Ts[i], x + i * QX * (N + 1), ts ? ts + i * (N + 1) : nullptr, 0, Tsf + i, xf + i * QX * ((size_t)N * r + 1));
+}
+
 // rows of a strided device array <-> a dense staging array (one contiguous PCIe transfer per direction instead of a 2-D copy):
 //   scatter: dst[i * ds + j] = j < W ? src[i * W + j] : 0   for j < zero_to   (upload: primal prefix of the iterate, rest of the row cleared)
 //   gather : dst[i * W + j] = src[i * ss + j]                                   (download: the output prefix of the iterate)
@@ -384,6 +404,7 @@ struct obca_ctx {
     std::string err; std::string name; int cus;
     PathWsBufs *pw = nullptr;               // staging of obca_parking_path_warm_start_batch (primary device), created by its first call
     PathWsBufs *rf = nullptr;               // the same set for obca_parking_refine_batch
+    PathWsBufs *qsd = nullptr;              // and for obca_quadcopter_subdivide_batch
 };
 static std::string g_create_err;
 
@@ -458,6 +479,7 @@ struct obca_quad_batch : BatchCore {
     using BatchCore::BatchCore;
     QDevBufs d = {};
     PinnedBuf h_z;
+    PathWsBufs sd;       // obca_quad_batch_subdivide_into, this batch the destination: selection and status on the device, the events around the kernel
 };
 struct obca_batch : BatchCore {
     using BatchCore::BatchCore;
@@ -605,6 +627,7 @@ int obca_destroy(obca_ctx *c) {
     }
     if (c->pw) { use_device(c->device); c->pw->release(); delete c->pw; }
     if (c->rf) { use_device(c->device); c->rf->release(); delete c->rf; }
+    if (c->qsd) { use_device(c->device); c->qsd->release(); delete c->qsd; }
     delete c; return 0;
 }
 const char *obca_last_error(const obca_ctx *c) { return c ? c->err.c_str() : g_create_err.c_str(); }
@@ -1480,7 +1503,7 @@ int obca_quad_batch_create(obca_ctx *ctx, int B, int N, obca_quad_batch **out) {
 int obca_quad_batch_destroy(obca_quad_batch *bt) {
     if (!bt) return -1;
     use_device(bt->device);
-    free_dev(bt); core_release(bt); bt->h_z.release();
+    free_dev(bt); core_release(bt); bt->h_z.release(); bt->sd.release();
     delete bt; return 0;
 }
 #ifdef OBCA_PROFILE
@@ -1666,6 +1689,71 @@ int obca_quadcopter_dist_batch(obca_ctx *ctx, int B, int N, const double *Ts, do
     QuadIn in = {Ts, R, x0, xF, ob, xWS, timeWS, dual_ws, 1};
     QuadOut o = {xp, up, timeScale, exitflag, lp, nullptr, info};
     return quadcopter_call(ctx, B, N, in, opts, o);
+}
+
+/* ---- solved quadcopter batches on a finer horizon (obca_quad_subdivide.h, include/obca_quad_subdivide.h) */
+int obca_quad_batch_subdivide_into(obca_quad_batch *dst, obca_quad_batch *src, int factor, double margin, const int *sel, int n, int *status) {
+    if (!dst || !src) return -1;
+    obca_ctx *ctx = dst->ctx;
+    const char *bad = nullptr;
+    if (!status) bad = "NULL argument";
+    else if (dst == src || dst->ctx != src->ctx || dst->stream != src->stream) bad = "source and destination must be two batches of one context";
+    else if (!src->uploaded || !src->solved) bad = "nothing has been solved on the source since its last upload or shift";
+    else if ((bad = qsd::subdivide_check_args(n, src->N, factor, margin)) != nullptr) {}
+    else if (dst->N != factor * src->N) bad = "the destination's horizon must be factor * the source's";
+    else if (n > dst->cap) bad = "more instances than the destination was created for";
+    for (int j = 0; !bad && sel && j < n; j++) if (sel[j] < 0 || sel[j] >= src->B) bad = "an index outside 0 .. B - 1 of the source";
+    if (!bad && !sel && n > src->B) bad = "an index outside 0 .. B - 1 of the source";
+    if (bad) { ctx->err = std::string("obca_quad_batch_subdivide_into: ") + bad; return -1; }
+    use_device(dst->device);
+    PathWsBufs &w = dst->sd;
+    if (int rc = refine_events(dst->err, w)) return fin(dst, rc);
+    if (w.dev.reserve((size_t)dst->cap + 1, dst->stream) != hipSuccess) { ctx->err = "obca_quad_batch_subdivide_into: hipMalloc failed"; return -2; }      // ints: [ sel cap | status cap ]
+    if (w.host.reserve(dst->err, ((size_t)dst->cap + 1) / 2 + 1)) return fin(dst, -2);
+    int *hs = (int *)w.host.p, *dsel = (int *)w.dev.p, *dst_st = dsel + dst->cap;
+    dst->B = n; dst->solved = 0;
+    dst->uploaded = 0;      // until the kernel has written every record
+    for (int j = 0; j < n; j++) hs[j] = sel ? sel[j] : j;
+    bool ok = hipMemcpyAsync(dsel, hs, (size_t)n * sizeof(int), hipMemcpyHostToDevice, dst->stream) == hipSuccess;
+    ok = ok && hipEventRecord(w.e0, dst->stream) == hipSuccess;
+    hipLaunchKernelGGL(obca_quad_subdivide_batch_kernel, dim3(n), dim3(QNT), 0, dst->stream, n, src->N, factor, margin, (const int *)dsel, src->d, dst->d, dst_st);
+    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(w.e1, dst->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(status, dst_st, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, dst->stream) == hipSuccess;
+    if (hipStreamSynchronize(dst->stream) != hipSuccess || !ok) { ctx->err = "obca_quad_batch_subdivide_into: kernel or copy failed"; return -2; }
+    w.timed = 1; dst->uploaded = 1;
+    return 0;
+}
+
+int obca_quad_batch_subdivide_ms(obca_quad_batch *dst, float *ms) {
+    if (!dst || !ms) return -1;
+    return core_elapsed_ms(dst, dst->sd.timed != 0, dst->sd.e0, dst->sd.e1, ms, "obca_quad_batch_subdivide_ms: no subdivide call has written into this batch");
+}
+
+int obca_quadcopter_subdivide_batch(obca_ctx *ctx, int B, int N, int factor, const double *Ts, const double *x, const double *timeScale, double *Ts_f, double *x_f) {
+    if (!ctx) return -1;
+    const char *bad = qsd::subdivide_check_args(B, N, factor, 0.0);
+    if (!bad && !(Ts && x && Ts_f && x_f)) bad = "NULL argument";
+    if (bad) { ctx->err = std::string("obca_quadcopter_subdivide_batch: ") + bad; return -1; }
+    use_device(ctx->device);
+    if (!ctx->qsd) ctx->qsd = new PathWsBufs();
+    PathWsBufs &w = *ctx->qsd;
+    if (int rc = refine_events(ctx->err, w)) return rc;
+    const size_t Nf = (size_t)N * factor, nx = (size_t)B * QX * (N + 1), nt = timeScale ? (size_t)B * (N + 1) : 0, nin = B + nx + nt, nxf = (size_t)B * QX * (Nf + 1);
+    if (w.dev.reserve(nin + B + nxf, ctx->stream) != hipSuccess) { ctx->err = "obca_quadcopter_subdivide_batch: hipMalloc failed"; return -2; }
+    if (w.host.reserve(ctx->err, nin)) return -2;
+    double *h = w.host, *d = w.dev;      // one contiguous transfer up: [ Ts B | x | timeScale ]
+    memcpy(h, Ts, sizeof(double) * B); memcpy(h + B, x, sizeof(double) * nx);
+    if (nt) memcpy(h + B + nx, timeScale, sizeof(double) * nt);
+    double *dTsf = d + nin, *dxf = dTsf + B;
+    bool ok = hipMemcpyAsync(d, h, nin * sizeof(double), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    ok = ok && hipEventRecord(w.e0, ctx->stream) == hipSuccess;
+    hipLaunchKernelGGL(obca_quad_subdivide_host_kernel, dim3(B), dim3(QNT), 0, ctx->stream, B, N, factor, (const double *)d, (const double *)(d + B), (const double *)(nt ? d + B + nx : nullptr), dTsf, dxf);
+    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(w.e1, ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(Ts_f, dTsf, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(x_f, dxf, nxf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess || !ok) { ctx->err = "obca_quadcopter_subdivide_batch: kernel or copy failed"; return -2; }
+    w.timed = 1;
+    return 0;
 }
 
 }  // extern "C"

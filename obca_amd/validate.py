@@ -15,6 +15,7 @@ validate_parking : (ok, violations) of one returned parking solution; validate_q
 parking_samples, quad_clearance, clearance_record : the numpy statement of the between-node clearance check (obca_amd/csrc/obca_clearance.h, Batch.clearance):
     the sample poses of a parking trajectory, the clearance record of a quadcopter trajectory, and the record of any (samples, obstacles) table of clearances.
 refine_parking : the numpy statement of the refinement of a solved parking instance onto a finer horizon (obca_amd/csrc/obca_refine.h, Batch.refine).
+refine_quad : the same for a solved quadcopter instance (obca_amd/csrc/obca_quad_subdivide.h, QuadBatch.refine).
 Shapes follow the reference: x (4,N+1), u (2,N), l (M,N+1), n (4nOb,N+1), timeScale (N+1,) .
 """
 import numpy as np
@@ -230,6 +231,29 @@ def refine_parking(x, u, timeScale, Ts, L, factor, ref=None, lam=None, mu=None):
         if a is not None:
             out[name] = np.asarray(a, float)[:, k_of].copy()
     return out
+
+
+def refine_quad(x, timeScale, Ts, factor, euler=True):
+    """A quadcopter trajectory x (12,N+1) on the horizon N' = r N, r = factor: the warm start of the same NLP on a grid of step Ts / r (obca_amd/csrc/obca_quad_subdivide.h is
+    the device's text of this statement).  With q = k r + s, 0 <= s < r, and q = r N the last node:
+      x'[q] = x[k] at s = 0;  x'[r N] = x[N]
+      rows 0-2 at s > 0: p_k + (s / r) timeScale[k] Ts v_k -- the point quad_clearance(..., substeps=r) gives for sample q (the discretisation is forward Euler: it is also
+              the partial step), so the refined NLP constrains the very points the clearance check sampled;  euler=False: interpolated like the other rows
+      rows 3-11 at s > 0: x[k] + (s / r)(x[k+1] - x[k])
+    timeScale: a scalar or (N+1,).  Returns dict(x (12,rN+1), Ts = Ts / r)."""
+    x = np.asarray(x, float); N = x.shape[1] - 1; r = int(factor); ts = _stage_scale(timeScale, N)
+    assert r >= 1 and x.shape[0] == 12
+    Nf = N * r; xf = np.zeros((12, Nf + 1))
+    with np.errstate(invalid="ignore", over="ignore"):
+        for q in range(Nf + 1):
+            k, s = divmod(q, r)
+            if not s:
+                xf[:, q] = x[:, k]
+                continue
+            xf[:, q] = x[:, k] + (s / r) * (x[:, k + 1] - x[:, k])
+            if euler:
+                xf[:3, q] = x[:3, k] + s / r * ts[k] * Ts * x[6:9, k]
+    return dict(x=xf, Ts=Ts / r)
 
 
 def clearance_record(c, substeps, need, finite=True):
