@@ -56,6 +56,7 @@ def _load():
     cabi.bind(_lib, "obca_clearance.h")                   # the clearance between the nodes: likewise
     cabi.bind(_lib, "obca_refine.h")                      # solved batches on a finer horizon: likewise
     cabi.bind(_lib, "obca_quad_subdivide.h")              # ... and solved quadcopter batches
+    cabi.bind(_lib, "obca_plan_device.h")                 # the parking planner on the device
     return _lib
 
 
@@ -80,6 +81,10 @@ REFINE_MAXFACTOR = 32      # OBCA_REFINE_MAXFACTOR
 # include/obca_quad_subdivide.h: solved quadcopter batches on a finer horizon (QuadBatch.refine, quadcopter_refine_batch)
 QUAD_SUBDIVIDE_EXPORTS = ["obca_quad_batch_subdivide_into", "obca_quad_batch_subdivide_ms", "obca_quadcopter_subdivide_batch"]
 QUAD_SUBDIVIDE_MAXFACTOR = 32      # OBCA_QUAD_SUBDIVIDE_MAXFACTOR
+# include/obca_plan_device.h: the parking planner on the device (planner.hybrid_astar_many(device=...), planner.warm_start_many(search="device"), hybrid_configure, hybrid_ms)
+PLAN_DEVICE_EXPORTS = ["obca_hybrid_configure", "obca_hybrid_astar_batch", "obca_hybrid_ms"]
+HYBRID_MAXMAP, HYBRID_MAXCELLS, HYBRID_MAXSLOTS, HYBRID_MAXNODES, HYBRID_DEFAULT_WIDTH = 35000, 6000000, 256, 1 << 20, 0.2      # the limits of include/obca_plan_device.h
+HYBRID_STATUS = {0: "no path", -1: "more nodes than cap", -2: "the start or goal pose collides", -3: "a sizing limit of the slot was hit (node pool, chunk pool)"}
 QUAD_REFINE_STATUS = {0: "refined from the solution", 1: "interpolated from the uploaded warm start (the last solve failed, or its iterate is not finite)",
                       -1: "zero warm start (the uploaded one is not finite either)"}
 REFINE_STATUS = {0: "refined from the solution", 1: "refined from the start iterate (the last solve failed, or its iterate is not finite)", -1: "zero start (the start iterate is not finite either)"}
@@ -471,6 +476,32 @@ class Batch(_DeviceBatch):
         a = C.c_float(0)
         self._call("refine_ms", C.byref(a))
         return a.value
+
+
+def hybrid_configure(slots=0, max_nodes=0, max_chunks=0, device=0):
+    """the slots of the device planner of a context (obca_hybrid_configure): searches in flight, nodes and bucket chunks per search; 0 = the default"""
+    ctx = _ctx(device)
+    ctx._check(_load().obca_hybrid_configure(ctx._h, int(slots), int(max_nodes), int(max_chunks)), "obca_hybrid_configure")
+
+
+def hybrid_ms(device=0):
+    """HIP-event duration of the last search kernel of the context's device planner [ms]"""
+    ctx = _ctx(device); a = C.c_float(0)
+    ctx._check(_load().obca_hybrid_ms(ctx._h, C.byref(a)), "obca_hybrid_ms")
+    return a.value
+
+
+def hybrid_astar_batch(starts, goals, vOb, A, b, ego, L, XYbounds, opts=None, bucket_width=None, cap=1024, device=0):
+    """obca_hybrid_astar_batch as it is: B Hybrid A* searches in one obstacle field on the GPU, one workgroup each.  starts, goals (B, >= 3); opts: the option array of
+    obca_plan.h or None.  Returns (paths (B, cap, 3), dirs (B, cap), counts (B,), expansions (B,), rounds (B,)); counts as the host planner's, -3: HYBRID_STATUS."""
+    s = np.ascontiguousarray(np.asarray(starts, float)[:, :3]); g = np.ascontiguousarray(np.asarray(goals, float)[:, :3]); B = len(s); cap = int(cap)
+    vOb = np.ascontiguousarray(vOb, np.int32); o = None if opts is None else np.ascontiguousarray(opts, float)
+    paths = np.zeros((B, max(cap, 0), 3)); dirs = np.zeros((B, max(cap, 0)), np.int32); cnt = np.zeros(B, np.int32); nexp = np.zeros(B, np.int32); rounds = np.zeros(B, np.int32)
+    ctx = _ctx(device)
+    rc = _load().obca_hybrid_astar_batch(ctx._h, B, s, g, len(vOb), vOb, _in(A), _in(b), _in(ego), float(L), _in(XYbounds), o, 0 if o is None else len(o),
+                                         0.0 if bucket_width is None else float(bucket_width), paths, dirs, cap, cnt, nexp, rounds)
+    ctx._check(rc, "obca_hybrid_astar_batch")
+    return paths, dirs, cnt, nexp, rounds
 
 
 def parking_refine_batch(N, Ts, L, x, u, timeScale=None, factor=2, device=0):

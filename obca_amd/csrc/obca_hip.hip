@@ -397,7 +397,7 @@ __global__ __launch_bounds__(256) void obca_gather_rows_kernel(double *dst, size
 struct obca_batch;
 struct obca_quad_batch;
 struct Slot { int device; hipStream_t stream; obca_batch *pb; obca_quad_batch *qb; int cus; };
-namespace { struct PathWsBufs; }
+namespace { struct PathWsBufs; struct HybridBufs; }
 struct obca_ctx {
     int device; hipStream_t stream;         // primary device / stream (= slots[0]): the device-resident obca_batch_* API runs here
     std::vector<int> devices; std::vector<Slot> slots;
@@ -405,6 +405,7 @@ struct obca_ctx {
     PathWsBufs *pw = nullptr;               // staging of obca_parking_path_warm_start_batch (primary device), created by its first call
     PathWsBufs *rf = nullptr;               // the same set for obca_parking_refine_batch
     PathWsBufs *qsd = nullptr;              // and for obca_quadcopter_subdivide_batch
+    HybridBufs *hyb = nullptr;              // the planner's slots and staging (obca_hybrid_astar_batch), created by its first call or by obca_hybrid_configure
 };
 static std::string g_create_err;
 
@@ -456,6 +457,19 @@ struct DevBuf {
 struct PathWsBufs {
     DevBuf dev; PinnedBuf host; hipEvent_t e0 = nullptr, e1 = nullptr; int have_ev = 0, timed = 0;
     void release() { dev.release(); host.release(); if (have_ev) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); } have_ev = timed = 0; }
+};
+// the planner (obca_hybrid.h): the configuration, the slots' memory (kept while the next call fits it), the staging block of a call, the events around the kernel
+struct HybridBufs {
+    int slots = 0, max_nodes = 0, max_chunks = 0;      // as configured (0 = default)
+    char *slotmem = nullptr; size_t slot_bytes = 0; int nslots = 0, ncell = 0, nodes = 0, chunks = 0;
+    char *io = nullptr; size_t io_bytes = 0; int lds_set = 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr; int have_ev = 0, timed = 0;
+    void release() {
+        if (slotmem) (void)hipFree(slotmem);
+        if (io) (void)hipFree(io);
+        if (have_ev) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
+        slotmem = io = nullptr; slot_bytes = io_bytes = 0; nslots = have_ev = timed = 0;
+    }
 };
 }  // namespace
 
@@ -628,6 +642,7 @@ int obca_destroy(obca_ctx *c) {
     if (c->pw) { use_device(c->device); c->pw->release(); delete c->pw; }
     if (c->rf) { use_device(c->device); c->rf->release(); delete c->rf; }
     if (c->qsd) { use_device(c->device); c->qsd->release(); delete c->qsd; }
+    if (c->hyb) { use_device(c->device); c->hyb->release(); delete c->hyb; }
     delete c; return 0;
 }
 const char *obca_last_error(const obca_ctx *c) { return c ? c->err.c_str() : g_create_err.c_str(); }
@@ -1755,5 +1770,124 @@ int obca_quadcopter_subdivide_batch(obca_ctx *ctx, int B, int N, int factor, con
     w.timed = 1;
     return 0;
 }
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------- the parking planner on the device.  LAST in this file: obca_hybrid.h switches fp contraction off from its
+   include to the end of the translation unit, and no other kernel may be compiled under that. */
+#include "obca_hybrid.h"
+#include "../../include/obca_plan_device.h"
+
+// the parking planner (obca_hybrid.h): `slots` persistent workgroups, workgroup s runs the searches s, s + slots, ... in its slot of the planner's memory.  LDS: the
+// holonomic map (nmap floats, padded to an even count), then the bucket heads and control words.
+__global__ __launch_bounds__(HY_NT) void obca_hybrid_kernel(int B, int slots, const hy::Params *__restrict__ Pp, hy::Field F, const unsigned char *__restrict__ blocked,
+                                                            const double *__restrict__ inst, char *slotmem, size_t slot_bytes, double *paths, int *dirs, int *counts, int *nexp, int *rounds) {
+    extern __shared__ float hy_lds[];
+    const hy::Params &P = *Pp;
+    if ((int)blockIdx.x >= slots) return;
+    const hy::SlotMem M = hy::carve(slotmem + (size_t)blockIdx.x * slot_bytes, P.ncell, P.maxnodes, P.maxchunks);
+    int *li = (int *)(hy_lds + ((P.nmap + 1) & ~1));
+    for (int i = blockIdx.x; i < B; i += slots)
+        hy::search(P, F, blocked, inst + (size_t)i * 10, M, hy_lds, li, paths + (size_t)i * P.cap * 3, dirs + (size_t)i * P.cap, counts + i, nexp + i, rounds + i);
+}
+
+extern "C" {
+
+// ---- the parking planner on the device (obca_hybrid.h, include/obca_plan_device.h)
+#define OBCA_HYBRID_BUDGET ((size_t)16 << 30)      // bytes the slots take by default
+int obca_hybrid_configure(obca_ctx *ctx, int slots, int max_nodes, int max_chunks) {
+    if (!ctx) return -1;
+    if (slots < 0 || slots > OBCA_HYBRID_MAXSLOTS || max_nodes < 0 || max_nodes > OBCA_HYBRID_MAXNODES || max_chunks < 0 || max_chunks > (1 << 24)) {
+        ctx->err = "obca_hybrid_configure: need 0 <= slots <= OBCA_HYBRID_MAXSLOTS, 0 <= max_nodes <= OBCA_HYBRID_MAXNODES, 0 <= max_chunks <= 2^24"; return -1;
+    }
+    if (!ctx->hyb) ctx->hyb = new HybridBufs();
+    ctx->hyb->slots = slots; ctx->hyb->max_nodes = max_nodes; ctx->hyb->max_chunks = max_chunks;
+    return 0;
+}
+
+int obca_hybrid_astar_batch(obca_ctx *ctx, int B, const double *starts, const double *goals, int nOb, const int *vOb, const double *A, const double *b,
+                            const double ego[4], double L, const double XYbounds[4], const double *opts, int nopts, double bucket_width,
+                            double *paths, int *dirs, int cap, int *counts, int *expansions, int *rounds) {
+    if (!ctx) return -1;
+    if (!ctx->hyb) ctx->hyb = new HybridBufs();
+    HybridBufs &h = *ctx->hyb;
+    const int mn = h.max_nodes ? h.max_nodes : OBCA_HYBRID_MAXNODES, mc = h.max_chunks ? h.max_chunks : hy::default_chunks(mn);
+    hy::Params P; hy::HostField W; std::vector<unsigned char> blocked; std::vector<double> inst;
+    const char *bad = (paths && dirs && counts) ? hy::make_params(B, starts, goals, nOb, vOb, A, b, ego, L, XYbounds, opts, nopts, bucket_width, cap, mn, mc, P, W, blocked, inst)
+                                                : "NULL output array";
+    if (bad) { ctx->err = std::string("obca_hybrid_astar_batch: ") + bad; return -1; }
+    use_device(ctx->device);
+    if (!h.have_ev) {
+        if (hipEventCreate(&h.e0) != hipSuccess) { ctx->err = "hipEventCreate failed"; return -2; }
+        if (hipEventCreate(&h.e1) != hipSuccess) { (void)hipEventDestroy(h.e0); ctx->err = "hipEventCreate failed"; return -2; }
+        h.have_ev = 1;
+    }
+    h.timed = 0;
+    // the slots: as many as configured, else what the budget holds, never more than searches
+    const size_t sb = hy::slot_bytes(P.ncell, mn, mc);
+    int slots = h.slots ? h.slots : (int)std::min<size_t>(OBCA_HYBRID_MAXSLOTS, std::max<size_t>(1, OBCA_HYBRID_BUDGET / sb));
+    slots = std::min(slots, B);
+    if (!h.slotmem || h.nslots < slots || h.ncell != P.ncell || h.nodes != mn || h.chunks != mc) {
+        if (h.slotmem) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.slotmem); h.slotmem = nullptr; h.nslots = 0; }
+        if (hipMalloc((void **)&h.slotmem, sb * slots) != hipSuccess) { h.slotmem = nullptr; ctx->err = "obca_hybrid_astar_batch: hipMalloc of the slots failed (fewer slots or nodes: obca_hybrid_configure)"; return -2; }
+        h.slot_bytes = sb; h.nslots = slots; h.ncell = P.ncell; h.nodes = mn; h.chunks = mc;
+        bool ok = true;      // claim words and cell table: all ones; a search leaves them so
+        for (int s = 0; s < slots && ok; s++) ok = hipMemsetAsync(h.slotmem + (size_t)s * sb, 0xFF, hy::slot_init_bytes(P.ncell), ctx->stream) == hipSuccess;
+        if (!ok) { ctx->err = "obca_hybrid_astar_batch: hipMemsetAsync failed"; return -2; }
+    }
+    // one block up: [ Params | inst B x 10 | A | b | rn | vert | v off voff (ints) | blocked (bytes) ], one block down: [ paths | dirs | counts | expansions | rounds ]
+    auto up8 = [](size_t n) { return (n + 7) / 8 * 8; };
+    const size_t M_ = W.b.size(), nv = W.vert.size();
+    const size_t o_inst = up8(sizeof(hy::Params)), o_A = o_inst + inst.size() * 8, o_b = o_A + 2 * M_ * 8, o_rn = o_b + M_ * 8, o_vert = o_rn + M_ * 8, o_int = o_vert + nv * 8,
+                 o_blk = o_int + up8((size_t)(3 * nOb + 2) * 4), n_in = up8(o_blk + blocked.size());
+    const size_t o_paths = n_in, o_dirs = o_paths + (size_t)B * cap * 24, o_cnt = o_dirs + up8((size_t)B * cap * 4), n_all = o_cnt + up8((size_t)3 * B * 4);
+    if (h.io_bytes < n_all) {
+        if (h.io) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.io); h.io = nullptr; h.io_bytes = 0; }
+        if (hipMalloc((void **)&h.io, n_all) != hipSuccess) { h.io = nullptr; ctx->err = "obca_hybrid_astar_batch: hipMalloc failed"; return -2; }
+        h.io_bytes = n_all;
+    }
+    std::vector<char> up(n_in, 0);
+    memcpy(up.data(), &P, sizeof P); memcpy(up.data() + o_inst, inst.data(), inst.size() * 8);
+    if (M_) { memcpy(up.data() + o_A, W.A.data(), 2 * M_ * 8); memcpy(up.data() + o_b, W.b.data(), M_ * 8); memcpy(up.data() + o_rn, W.rn.data(), M_ * 8); }
+    if (nv) memcpy(up.data() + o_vert, W.vert.data(), nv * 8);
+    int *ip = (int *)(up.data() + o_int);
+    for (int j = 0; j < nOb; j++) ip[j] = W.v[j];
+    for (int j = 0; j <= nOb; j++) { ip[nOb + j] = W.off[j]; ip[2 * nOb + 1 + j] = W.voff[j]; }
+    memcpy(up.data() + o_blk, blocked.data(), blocked.size());
+    char *d = h.io;
+    hy::Field F; F.nOb = nOb; F.v = (const int *)(d + o_int); F.off = F.v + nOb; F.voff = F.off + nOb + 1;
+    F.A = (const double *)(d + o_A); F.b = (const double *)(d + o_b); F.rn = (const double *)(d + o_rn); F.vert = (const double *)(d + o_vert);
+    const int lds = (((P.nmap + 1) & ~1) + HY_LDS_INTS) * (int)sizeof(float);
+    if (lds > h.lds_set) {
+        if (hipFuncSetAttribute((const void *)obca_hybrid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) { ctx->err = "obca_hybrid_astar_batch: hipFuncSetAttribute failed"; return -2; }
+        h.lds_set = lds;
+    }
+    int *dcnt = (int *)(d + o_cnt);
+    bool ok = hipMemcpyAsync(d, up.data(), n_in, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess;      // (`up` is pageable and leaves scope)
+    ok = ok && hipEventRecord(h.e0, ctx->stream) == hipSuccess;
+    hipLaunchKernelGGL(obca_hybrid_kernel, dim3(slots), dim3(HY_NT), lds, ctx->stream, B, slots, (const hy::Params *)d, F, (const unsigned char *)(d + o_blk), (const double *)(d + o_inst),
+                       h.slotmem, sb, (double *)(d + o_paths), (int *)(d + o_dirs), dcnt, dcnt + B, dcnt + 2 * B);
+    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(h.e1, ctx->stream) == hipSuccess;
+    std::vector<int> tail((size_t)3 * B);
+    ok = ok && hipMemcpyAsync(paths, d + o_paths, (size_t)B * cap * 24, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(dirs, d + o_dirs, (size_t)B * cap * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(tail.data(), dcnt, (size_t)3 * B * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess || !ok) {
+        ctx->err = "obca_hybrid_astar_batch: kernel or copy failed";
+        h.release();      // the slots may hold a half-finished search: the next call starts from fresh ones
+        return -2;
+    }
+    for (int i = 0; i < B; i++) { counts[i] = tail[i]; if (expansions) expansions[i] = tail[B + i]; if (rounds) rounds[i] = tail[2 * B + i]; }
+    h.timed = 1;
+    return 0;
+}
+
+int obca_hybrid_ms(obca_ctx *ctx, float *ms) {
+    if (!ctx || !ms) return -1;
+    if (!ctx->hyb || !ctx->hyb->timed || hipEventElapsedTime(ms, ctx->hyb->e0, ctx->hyb->e1) != hipSuccess) { ctx->err = "obca_hybrid_ms: no search has run on this context"; return -2; }
+    return 0;
+}
+
 
 }  // extern "C"

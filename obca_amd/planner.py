@@ -285,9 +285,29 @@ def _hybrid_astar_dense(starts, goals, vOb, A, b, ego, L, XYbounds, threads, cap
     return s, g, paths, dirs, cnt, nexp
 
 
-def hybrid_astar_many(starts, goals, vOb, A, b, ego=S.EGO, L=S.L_WHEELBASE, XYbounds=S.XYBOUNDS, threads=0, cap=1024, **kw):
+def _hybrid_astar_dense_device(starts, goals, vOb, A, b, ego, L, XYbounds, cap, kw, device, bucket_width=None):
+    """obca_hybrid_astar_batch (include/obca_plan_device.h) with the return value of _hybrid_astar_dense: the searches run on the GPU, one workgroup each"""
+    from . import api
+    s = np.ascontiguousarray(np.asarray(starts, float)[:, :3]); g = np.ascontiguousarray(np.asarray(goals, float)[:, :3])
+    nOb, v, A_, b_, ego_, L_, xy, opts, _ = _search_args(vOb, A, b, ego, L, XYbounds, kw)
+    paths, dirs, cnt, nexp, _ = api.hybrid_astar_batch(s, g, v, A_, b_, ego_, L_, xy, opts, bucket_width, cap, device)
+    return s, g, paths, dirs, cnt, nexp      # (cnt -3: that search outgrew its slot -- api.hybrid_configure; it ends alone and counts as "no path" for the callers below)
+
+
+def hybrid_astar_many(starts, goals, vOb, A, b, ego=S.EGO, L=S.L_WHEELBASE, XYbounds=S.XYBOUNDS, threads=0, cap=1024, device=None, bucket_width=None, **kw):
     """B searches in one obstacle field on the host threads of the library (obca_plan_hybrid_astar_batch): returns a list of (path, dir, expansions) / None
-    (no path, or the start / goal pose collides)."""
+    (no path, or the start / goal pose collides).  device (an index or an api.Context): the searches run on that GPU instead (obca_hybrid_astar_batch: a round-synchronous
+    Hybrid A* with open-set buckets of width bucket_width, None = the library's default); a path of more than cap nodes is searched again there with room for 20000; an
+    instance whose search outgrew its slot (count -3, api.HYBRID_STATUS) is None like one without a path, the others keep their results."""
+    if device is not None:
+        s, g, paths, dirs, cnt, nexp = _hybrid_astar_dense_device(starts, goals, vOb, A, b, ego, L, XYbounds, cap, kw, device, bucket_width)
+        long_ = np.flatnonzero(cnt == -1)
+        out = [(paths[i, :cnt[i]].copy(), dirs[i, :cnt[i]].copy(), int(nexp[i])) if cnt[i] > 0 else None for i in range(len(s))]
+        if len(long_):
+            _, _, p2, d2, c2, n2 = _hybrid_astar_dense_device(s[long_], g[long_], vOb, A, b, ego, L, XYbounds, 20000, kw, device, bucket_width)
+            for j, i in enumerate(long_):
+                out[i] = (p2[j, :c2[j]].copy(), d2[j, :c2[j]].copy(), int(n2[j])) if c2[j] > 0 else None
+        return out
     s, g, paths, dirs, cnt, nexp = _hybrid_astar_dense(starts, goals, vOb, A, b, ego, L, XYbounds, threads, cap, kw); B = len(s)
     out = []
     for i in range(B):
@@ -301,11 +321,17 @@ def hybrid_astar_many(starts, goals, vOb, A, b, ego=S.EGO, L=S.L_WHEELBASE, XYbo
     return out
 
 
-def warm_start_many(sc, x0, xF, N, workers=None, smooth=False, device=None, **kw):
+def warm_start_many(sc, x0, xF, N, workers=None, smooth=False, device=None, search="host", bucket_width=None, **kw):
     """warm starts of a batch: the searches run on the host threads of the planner library (one call, no worker processes: safe next to a live HIP runtime, so
     every rank of a multi-GPU job plans its own slice after its device is up); resampling to the horizon is numpy per instance.  workers = threads (default: all).
     device (an index or an api.Context): the planner's dense arrays go to path_to_warm_start_many unconverted and the resampling runs on that GPU; a path of more than
-    1 024 nodes is searched again on its own and resampled by numpy, as without a device."""
+    1 024 nodes is searched again on its own and resampled by numpy, as without a device.
+    search="device" (needs `device`): the searches run on that GPU too (obca_hybrid_astar_batch, bucket_width as in hybrid_astar_many), then path_to_warm_start_many; a path of
+    more than `cap` nodes is searched again ON THE DEVICE with room for 20000 and resampled by numpy; an instance whose search outgrew its slot (count -3) is None, alone."""
+    if search not in ("host", "device"):
+        raise ValueError("search must be 'host' or 'device'")
+    if search == "device" and device is None:
+        raise ValueError("search='device' needs a device")
     A, b, vrows = S.scenario_hrep(sc)
     o, v_nom = SCENARIO_OPTS.get(sc["name"], (dict(), 0.5))
     o = dict(o); o.update(kw)
@@ -316,10 +342,19 @@ def warm_start_many(sc, x0, xF, N, workers=None, smooth=False, device=None, **kw
         res = hybrid_astar_many(x0[:, :3], xF[:, :3], vrows, A, b, threads=workers or effective_cpus(), **o)
         return [None if r is None else path_to_warm_start(r[0], r[1], N, xF[i], v_nom=v_nom, smooth=smooth) for i, r in enumerate(res)]
     geo = dict(ego=o.pop("ego", S.EGO), L=o.pop("L", S.L_WHEELBASE), XYbounds=o.pop("XYbounds", S.XYBOUNDS)); cap = o.pop("cap", 1024)      # hybrid_astar_many's named parameters
-    s, g, paths, dirs, cnt, _ = _hybrid_astar_dense(x0[:, :3], xF[:, :3], vrows, A, b, geo["ego"], geo["L"], geo["XYbounds"], workers or effective_cpus(), cap, o)
+    if search == "device":
+        s, g, paths, dirs, cnt, _ = _hybrid_astar_dense_device(x0[:, :3], xF[:, :3], vrows, A, b, geo["ego"], geo["L"], geo["XYbounds"], cap, o, device, bucket_width)
+    else:
+        s, g, paths, dirs, cnt, _ = _hybrid_astar_dense(x0[:, :3], xF[:, :3], vrows, A, b, geo["ego"], geo["L"], geo["XYbounds"], workers or effective_cpus(), cap, o)
     Ts, xWS, uWS, ok = path_to_warm_start_many(paths, dirs, cnt, N, xF, v_nom=v_nom, smooth=smooth, device=device)
     out = [(float(Ts[i]), xWS[i], uWS[i]) if ok[i] else None for i in range(len(cnt))]
-    for i in np.flatnonzero(cnt == -1):
+    long_ = np.flatnonzero(cnt == -1)
+    if search == "device" and len(long_):      # longer than cap nodes: searched again where the caller asked for, with room for 20000 nodes; resampled by numpy
+        _, _, p2, d2, c2, _ = _hybrid_astar_dense_device(s[long_], g[long_], vrows, A, b, geo["ego"], geo["L"], geo["XYbounds"], 20000, o, device, bucket_width)
+        for j, i in enumerate(long_):
+            out[i] = None if c2[j] <= 0 else path_to_warm_start(p2[j, :c2[j]], d2[j, :c2[j]], N, xF[i], v_nom=v_nom, smooth=smooth)
+        return out
+    for i in long_:
         try:
             r = hybrid_astar(s[i], g[i], vrows, A, b, **geo, **o)
         except ValueError:

@@ -213,11 +213,11 @@ def sample_poses(sc, B, rng, goal_jitter=False):
     return x0, xF
 
 
-def plan_batch(sc, x0, xF, N, rng, planner=None, workers=None, smooth=False, device=None):
+def plan_batch(sc, x0, xF, N, rng, planner=None, workers=None, smooth=False, device=None, search="host"):
     """warm starts (the step before the path, host side) for given poses: geometric line/arc primitives for the backwards scenario, Hybrid A* (obca_amd/planner.py) for
     the parallel one, whose 6 m bay needs a multi-manoeuvre path; planner=True/False forces the choice.  A start pose for which the planner finds no path is re-drawn
     from `rng` (x0 is updated in place).  Returns Ts (B,), xWS (B,N+1,4), uWS (B,N,2).  device (with the planner): the paths are resampled on that GPU
-    (planner.path_to_warm_start_many) instead of by numpy per instance."""
+    (planner.path_to_warm_start_many) instead of by numpy per instance; search="device": the searches run there as well (planner.warm_start_many)."""
     B = len(x0)
     use_planner = (sc["name"] != "backwards") if planner is None else bool(planner)
     Ts = np.zeros(B); xWS = np.zeros((B, N + 1, 4)); uWS = np.zeros((B, N, 2))
@@ -229,7 +229,7 @@ def plan_batch(sc, x0, xF, N, rng, planner=None, workers=None, smooth=False, dev
         from . import planner as PL
         todo = list(range(B))
         while todo:
-            res = PL.warm_start_many(sc, x0[todo], xF[todo], N, workers=workers, smooth=smooth, device=device)
+            res = PL.warm_start_many(sc, x0[todo], xF[todo], N, workers=workers, smooth=smooth, device=device, search=search)
             nxt = []
             for i, r in zip(todo, res):
                 if r is None:
@@ -240,12 +240,12 @@ def plan_batch(sc, x0, xF, N, rng, planner=None, workers=None, smooth=False, dev
     return Ts, xWS, uWS
 
 
-def make_batch(sc, B, N=80, seed=20260925, goal_jitter=False, planner=None, workers=None, smooth=False, device=None):
-    """Synthetic batch: sample_poses + plan_batch from one random stream (seed); device: see plan_batch."""
+def make_batch(sc, B, N=80, seed=20260925, goal_jitter=False, planner=None, workers=None, smooth=False, device=None, search="host"):
+    """Synthetic batch: sample_poses + plan_batch from one random stream (seed); device, search: see plan_batch."""
     rng = np.random.default_rng(seed)
     A, b, vrows = scenario_hrep(sc)
     x0, xF = sample_poses(sc, B, rng, goal_jitter)
-    Ts, xWS, uWS = plan_batch(sc, x0, xF, N, rng, planner=planner, workers=workers, smooth=smooth, device=device)
+    Ts, xWS, uWS = plan_batch(sc, x0, xF, N, rng, planner=planner, workers=workers, smooth=smooth, device=device, search=search)
     return dict(x0=x0, xF=xF, Ts=Ts, xWS=xWS, uWS=uWS, A=A, b=b, vOb=vrows, N=N, L=L_WHEELBASE,
                 ego=EGO.copy(), XYbounds=XYBOUNDS.copy())
 
