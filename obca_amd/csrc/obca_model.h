@@ -541,127 +541,163 @@ OBCA_FN void obs_block(const Consts &c, const ObsIn<VM> &in, double mu_b, double
 
 // ---------------------------------------------------------------- DualMultWS: one (pose, obstacle) convex problem
 // max d = -g'mu + (A e - b)'lam  s.t. |A'lam|^2<=1, G'mu + R'A'lam = 0, lam,mu>=0   (DualMultWS.jl:52-73)
-// feasible-start primal-dual path following (sigma = 0.1) down to an average complementarity of 1e-9.
+// feasible-start primal-dual path following: bound multipliers from z = 1, sigma = 0.1, until the average complementarity and the residuals are below 1e-9 -- or
+// OB_DW_PASSES passes have run.  Most problems end far below that cap; a long thin obstacle some metres away does not (85 of the 115 344 problems of a 256-instance mixed batch, up to 1.82 m short): with |A e - b| of 10 .. 100 against z = 1
+// the iterate runs into the boundary |A'lam| = 1 long before it is dual feasible and the steps shrink to 1e-4 (a triangle 30 m long and 2 m wide, its tip 8.4 m from
+// the car, came back 9.8 cm short: feasible, far from optimal, and indistinguishable from an answer).  A problem that reaches the cap unconverged is solved once more
+// by the SAME passes -- one loop body: this function is inlined three times in two kernels -- from a start in the objective's scale, z = max(1, max |A e - b|), with
+// sigma = 0.5, up to OB_DW_PASSES2 passes (of random polygons with aspect ratios 0.01 .. 30, 0.5 .. 150 m away, one in ten goes there and needs 52 at most).  A first attempt
+// that is nearly there at its last pass (average complementarity below OB_DW_NEAR: 20 of the 248 832 problems of the benchmark batch, 2.3e-8 short at most, 1 .. 3 passes
+// more) goes on instead, to OB_DW_PASSES1 at most: a restart would cost its wavefront 25 passes.  Where the first attempt converges nothing changed, bit for bit.  The CPU checker restates the same text; tests/test_dualws_geometry_cpu.py and tests/test_gpu_dualws_geometry.py hold
+// it, the host build and the device against exact polygon geometry (tests/polygon_distance.py).
+#define OB_DW_PASSES 60
+#define OB_DW_PASSES2 300
+#define OB_DW_PASSES1 120
+#define OB_DW_NEAR 1e-6
+#if defined(__HIP_DEVICE_COMPILE__)
+#define OB_DW_KEEP_IN_LOOP(x) asm volatile("" : "+v"(x))      // an empty statement the compiler may not move: what is computed from x stays where it is written
+#else
+#define OB_DW_KEEP_IN_LOOP(x) (void)(x)
+#endif
 template <int VM>
 OBCA_FN void dualws_one(int v, const double *a1, const double *a2, const double *bj, const double g[4], double ex, double ey,
                         double cs, double sn, double *lam, double *mu, double *dout) {
-    double Q0[VM], Q1[VM], cl[VM], amax = 0;
+    double Q0[VM], Q1[VM], cl[VM];
 #pragma unroll
     for (int i = 0; i < VM; i++) {
         double x1 = i < v ? a1[i] : 0.0, x2 = i < v ? a2[i] : 0.0;
         Q0[i] = cs * x1 + sn * x2; Q1[i] = -sn * x1 + cs * x2;
         cl[i] = x1 * ex + x2 * ey - (i < v ? bj[i] : 0.0);
-        double nr = sqrt(x1 * x1 + x2 * x2); amax = fmax(amax, nr);
     }
-    double zl[VM], zm[4], zh = 1, eta0 = 0, eta1 = 0;
-#pragma unroll
-    for (int i = 0; i < VM; i++) { lam[i] = i < v ? 0.5 / (v * fmax(amax, 1e-12)) : 0.0; zl[i] = 1; }
-    {
-        double q0 = 0, q1 = 0;
-#pragma unroll
-        for (int i = 0; i < VM; i++) { q0 += Q0[i] * lam[i]; q1 += Q1[i] * lam[i]; }
-        mu[0] = 1 + fmax(0.0, -q0); mu[2] = mu[0] + q0; mu[1] = 1 + fmax(0.0, -q1); mu[3] = mu[1] + q1;
-#pragma unroll
-        for (int i = 0; i < 4; i++) zm[i] = 1;
-    }
+    double zl[VM], zm[4], zh, eta0, eta1;
     const double Em0[4] = {1, 0, -1, 0}, Em1[4] = {0, 1, 0, -1};
     const double iv5 = 1.0 / (v + 5);
-    for (int it = 0; it < 60; it++) {
-        double p1 = 0, p2 = 0;
-#pragma unroll
-        for (int i = 0; i < VM; i++) if (i < v) { p1 += a1[i] * lam[i]; p2 += a2[i] * lam[i]; }
-        double h = 1 - p1 * p1 - p2 * p2;
-        double gap = h * zh;
-#pragma unroll
-        for (int i = 0; i < VM; i++) if (i < v) gap += lam[i] * zl[i];
-#pragma unroll
-        for (int i = 0; i < 4; i++) gap += mu[i] * zm[i];
-        double mbar = gap * iv5;
-        double gh[VM], rl[VM], rm[4], rmax = 0;
+    // Two attempts as an outer loop that is never unrolled: ONE copy of the passes.  The start is formed inside it from what the passes keep in registers anyway (the
+    // rows, A e - b), behind OB_DW_KEEP_IN_LOOP: hoisted out of the loop, its two numbers would stay alive across the passes -- the 2-row kernel then loses its third
+    // wavefront per SIMD and the 8-row clearance kernel spills.  `limit` tells the attempt.
+    int limit = OB_DW_PASSES;
+    bool open = true, goon = false;      // (per lane, and kept out of `limit` and the pass counter: those stay the wavefront's)
+#pragma nounroll
+    for (;;) {
+        int vs = v; OB_DW_KEEP_IN_LOOP(vs);
+        double amax = 0, z0 = 1;
 #pragma unroll
         for (int i = 0; i < VM; i++) {
-            if (i < v) {
-                gh[i] = -2 * (p1 * a1[i] + p2 * a2[i]);
-                rl[i] = -cl[i] + Q0[i] * eta0 + Q1[i] * eta1 - zl[i] - zh * gh[i];
-                rmax = fmax(rmax, fabs(rl[i]));
-            } else { gh[i] = 0; rl[i] = 0; }
+            double x1 = i < vs ? a1[i] : 0.0, x2 = i < vs ? a2[i] : 0.0;
+            double nr = sqrt(x1 * x1 + x2 * x2); amax = fmax(amax, nr);
+            if (limit == OB_DW_PASSES2 && i < vs) z0 = fmax(z0, fabs(cl[i]));
         }
 #pragma unroll
-        for (int i = 0; i < 4; i++) { rm[i] = g[i] + Em0[i] * eta0 + Em1[i] * eta1 - zm[i]; rmax = fmax(rmax, fabs(rm[i])); }
-        if (mbar < 1e-9 && rmax < 1e-9) break;
-        double mt = 0.1 * mbar;
-        // reciprocals of the barrier variables, once per iteration (reciprocal + Newton, obca_model.h: rcp_nr); the subproblem is a chain of
-        // dependent scalar operations per lane, and an IEEE division is 11 of them
-        const double ih = rcp_nr(h);
-        double il[VM], im[4];
+        for (int i = 0; i < VM; i++) { lam[i] = i < v ? 0.5 / (vs * fmax(amax, 1e-12)) : 0.0; zl[i] = z0; }
+        {
+            double q0 = 0, q1 = 0;
 #pragma unroll
-        for (int i = 0; i < VM; i++) il[i] = i < v ? rcp_nr(lam[i]) : 0.0;
+            for (int i = 0; i < VM; i++) { q0 += Q0[i] * lam[i]; q1 += Q1[i] * lam[i]; }
+            mu[0] = 1 + fmax(0.0, -q0); mu[2] = mu[0] + q0; mu[1] = 1 + fmax(0.0, -q1); mu[3] = mu[1] + q1;
 #pragma unroll
-        for (int i = 0; i < 4; i++) im[i] = rcp_nr(mu[i]);
-        double Hl[VM * VM], bl[VM], Dm[4], iDm[4], bm[4];
-#pragma unroll
-        for (int i = 0; i < VM; i++) {
-#pragma unroll
-            for (int j = 0; j < VM; j++)
-                Hl[i * VM + j] = (i < v && j < v) ? zh * 2 * (a1[i] * a1[j] + a2[i] * a2[j]) + (zh * ih) * gh[i] * gh[j] : 0.0;
-            if (i < v) { Hl[i * VM + i] += zl[i] * il[i]; bl[i] = -(rl[i] + zl[i] - mt * il[i] + (zh - mt * ih) * gh[i]); }
-            else bl[i] = 0;
+            for (int i = 0; i < 4; i++) zm[i] = z0;
         }
+        zh = z0; eta0 = 0; eta1 = 0;
+        for (int it = 0; it < limit || (goon && it < OB_DW_PASSES1); it++) {
+            double p1 = 0, p2 = 0;
 #pragma unroll
-        for (int i = 0; i < 4; i++) { Dm[i] = zm[i] * im[i]; iDm[i] = rcp_nr(Dm[i]); bm[i] = -(rm[i] + zm[i] - mt * im[i]); }
-        if (ldl_fact<VM>(v, Hl)) break;
-        double HiQ0[VM], HiQ1[VM], Hib[VM];
+            for (int i = 0; i < VM; i++) if (i < v) { p1 += a1[i] * lam[i]; p2 += a2[i] * lam[i]; }
+            double h = 1 - p1 * p1 - p2 * p2;
+            double gap = h * zh;
 #pragma unroll
-        for (int i = 0; i < VM; i++) { HiQ0[i] = Q0[i]; HiQ1[i] = Q1[i]; Hib[i] = bl[i]; }
-        ldl_solve<VM>(v, Hl, HiQ0); ldl_solve<VM>(v, Hl, HiQ1); ldl_solve<VM>(v, Hl, Hib);
-        double S00 = 0, S01 = 0, S11 = 0, rs0 = 0, rs1 = 0;
+            for (int i = 0; i < VM; i++) if (i < v) gap += lam[i] * zl[i];
 #pragma unroll
-        for (int i = 0; i < VM; i++) if (i < v) {
-            S00 += Q0[i] * HiQ0[i]; S01 += Q0[i] * HiQ1[i]; S11 += Q1[i] * HiQ1[i];
-            rs0 += Q0[i] * Hib[i]; rs1 += Q1[i] * Hib[i];
-        }
+            for (int i = 0; i < 4; i++) gap += mu[i] * zm[i];
+            double mbar = gap * iv5;
+            if (it == OB_DW_PASSES - 1 && limit == OB_DW_PASSES && mbar < OB_DW_NEAR) goon = true;      // nearly there at its last pass: the first attempt goes on, to OB_DW_PASSES1
+            double gh[VM], rl[VM], rm[4], rmax = 0;
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-            S00 += Em0[i] * Em0[i] * iDm[i]; S01 += Em0[i] * Em1[i] * iDm[i]; S11 += Em1[i] * Em1[i] * iDm[i];
-            rs0 += Em0[i] * bm[i] * iDm[i]; rs1 += Em1[i] * bm[i] * iDm[i];
-        }
-        double Lc[3];
-        if (!chol2(S00, S01, S11, Lc)) break;
-        double de0 = rs0, de1 = rs1;
-        chol2_solve(Lc, de0, de1);
-        double dl[VM], dm[4], dzl[VM], dzm[4], ghd = 0;
+            for (int i = 0; i < VM; i++) {
+                if (i < v) {
+                    gh[i] = -2 * (p1 * a1[i] + p2 * a2[i]);
+                    rl[i] = -cl[i] + Q0[i] * eta0 + Q1[i] * eta1 - zl[i] - zh * gh[i];
+                    rmax = fmax(rmax, fabs(rl[i]));
+                } else { gh[i] = 0; rl[i] = 0; }
+            }
 #pragma unroll
-        for (int i = 0; i < VM; i++) {
-            dl[i] = i < v ? Hib[i] - HiQ0[i] * de0 - HiQ1[i] * de1 : 0.0;
-            dzl[i] = i < v ? mt * il[i] - zl[i] - zl[i] * il[i] * dl[i] : 0.0;
-            ghd += gh[i] * dl[i];
-        }
+            for (int i = 0; i < 4; i++) { rm[i] = g[i] + Em0[i] * eta0 + Em1[i] * eta1 - zm[i]; rmax = fmax(rmax, fabs(rm[i])); }
+            if (mbar < 1e-9 && rmax < 1e-9) { open = false; break; }
+            double mt = (limit == OB_DW_PASSES2 ? 0.5 : 0.1) * mbar;
+            // reciprocals of the barrier variables, once per iteration (reciprocal + Newton, obca_model.h: rcp_nr); the subproblem is a chain of
+            // dependent scalar operations per lane, and an IEEE division is 11 of them
+            const double ih = rcp_nr(h);
+            double il[VM], im[4];
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-            dm[i] = (bm[i] - Em0[i] * de0 - Em1[i] * de1) * iDm[i];
-            dzm[i] = mt * im[i] - zm[i] - zm[i] * im[i] * dm[i];
-        }
-        double dzh = mt * ih - zh - zh * ih * ghd;
-        double a = 1, tb = 0.995, cc;
+            for (int i = 0; i < VM; i++) il[i] = i < v ? rcp_nr(lam[i]) : 0.0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) im[i] = rcp_nr(mu[i]);
+            double Hl[VM * VM], bl[VM], Dm[4], iDm[4], bm[4];
+#pragma unroll
+            for (int i = 0; i < VM; i++) {
+#pragma unroll
+                for (int j = 0; j < VM; j++)
+                    Hl[i * VM + j] = (i < v && j < v) ? zh * 2 * (a1[i] * a1[j] + a2[i] * a2[j]) + (zh * ih) * gh[i] * gh[j] : 0.0;
+                if (i < v) { Hl[i * VM + i] += zl[i] * il[i]; bl[i] = -(rl[i] + zl[i] - mt * il[i] + (zh - mt * ih) * gh[i]); }
+                else bl[i] = 0;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) { Dm[i] = zm[i] * im[i]; iDm[i] = rcp_nr(Dm[i]); bm[i] = -(rm[i] + zm[i] - mt * im[i]); }
+            if (ldl_fact<VM>(v, Hl)) { open = false; break; }
+            double HiQ0[VM], HiQ1[VM], Hib[VM];
+#pragma unroll
+            for (int i = 0; i < VM; i++) { HiQ0[i] = Q0[i]; HiQ1[i] = Q1[i]; Hib[i] = bl[i]; }
+            ldl_solve<VM>(v, Hl, HiQ0); ldl_solve<VM>(v, Hl, HiQ1); ldl_solve<VM>(v, Hl, Hib);
+            double S00 = 0, S01 = 0, S11 = 0, rs0 = 0, rs1 = 0;
+#pragma unroll
+            for (int i = 0; i < VM; i++) if (i < v) {
+                S00 += Q0[i] * HiQ0[i]; S01 += Q0[i] * HiQ1[i]; S11 += Q1[i] * HiQ1[i];
+                rs0 += Q0[i] * Hib[i]; rs1 += Q1[i] * Hib[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                S00 += Em0[i] * Em0[i] * iDm[i]; S01 += Em0[i] * Em1[i] * iDm[i]; S11 += Em1[i] * Em1[i] * iDm[i];
+                rs0 += Em0[i] * bm[i] * iDm[i]; rs1 += Em1[i] * bm[i] * iDm[i];
+            }
+            double Lc[3];
+            if (!chol2(S00, S01, S11, Lc)) { open = false; break; }
+            double de0 = rs0, de1 = rs1;
+            chol2_solve(Lc, de0, de1);
+            double dl[VM], dm[4], dzl[VM], dzm[4], ghd = 0;
+#pragma unroll
+            for (int i = 0; i < VM; i++) {
+                dl[i] = i < v ? Hib[i] - HiQ0[i] * de0 - HiQ1[i] * de1 : 0.0;
+                dzl[i] = i < v ? mt * il[i] - zl[i] - zl[i] * il[i] * dl[i] : 0.0;
+                ghd += gh[i] * dl[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                dm[i] = (bm[i] - Em0[i] * de0 - Em1[i] * de1) * iDm[i];
+                dzm[i] = mt * im[i] - zm[i] - zm[i] * im[i] * dm[i];
+            }
+            double dzh = mt * ih - zh - zh * ih * ghd;
+            double a = 1, tb = 0.995, cc;
 #define OB_FTB(val, dv) { cc = (dv) < 0 ? -tb * (val) * rcp_nr(dv) : 1e300; if (cc < a) a = cc; }
 #pragma unroll
-        for (int i = 0; i < VM; i++) if (i < v) { OB_FTB(lam[i], dl[i]); OB_FTB(zl[i], dzl[i]); }
+            for (int i = 0; i < VM; i++) if (i < v) { OB_FTB(lam[i], dl[i]); OB_FTB(zl[i], dzl[i]); }
 #pragma unroll
-        for (int i = 0; i < 4; i++) { OB_FTB(mu[i], dm[i]); OB_FTB(zm[i], dzm[i]); }
-        OB_FTB(zh, dzh);
+            for (int i = 0; i < 4; i++) { OB_FTB(mu[i], dm[i]); OB_FTB(zm[i], dzm[i]); }
+            OB_FTB(zh, dzh);
 #undef OB_FTB
-        for (int bt = 0; bt < 60; bt++) {
-            double q1 = 0, q2 = 0;
+            for (int bt = 0; bt < 60; bt++) {
+                double q1 = 0, q2 = 0;
 #pragma unroll
-            for (int i = 0; i < VM; i++) if (i < v) { q1 += a1[i] * (lam[i] + a * dl[i]); q2 += a2[i] * (lam[i] + a * dl[i]); }
-            if (1 - q1 * q1 - q2 * q2 >= (1 - tb) * h) break;
-            a *= 0.7;
+                for (int i = 0; i < VM; i++) if (i < v) { q1 += a1[i] * (lam[i] + a * dl[i]); q2 += a2[i] * (lam[i] + a * dl[i]); }
+                if (1 - q1 * q1 - q2 * q2 >= (1 - tb) * h) break;
+                a *= 0.7;
+            }
+#pragma unroll
+            for (int i = 0; i < VM; i++) if (i < v) { lam[i] += a * dl[i]; zl[i] += a * dzl[i]; }
+#pragma unroll
+            for (int i = 0; i < 4; i++) { mu[i] += a * dm[i]; zm[i] += a * dzm[i]; }
+            zh += a * dzh; eta0 += a * de0; eta1 += a * de1;
         }
-#pragma unroll
-        for (int i = 0; i < VM; i++) if (i < v) { lam[i] += a * dl[i]; zl[i] += a * dzl[i]; }
-#pragma unroll
-        for (int i = 0; i < 4; i++) { mu[i] += a * dm[i]; zm[i] += a * dzm[i]; }
-        zh += a * dzh; eta0 += a * de0; eta1 += a * de1;
+        if (!open || limit == OB_DW_PASSES2) break;      // converged (or a factorisation failed: as before, the point it stands at), or this was the second attempt
+        limit = OB_DW_PASSES2; goon = false;
     }
     double dv = 0;
 #pragma unroll

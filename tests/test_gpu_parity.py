@@ -36,6 +36,8 @@ def _solve_batch(OA, bt, fixTime=0, lWS=None, nWS=None, opts=None, dist=False):
 
 
 def test_dualws_matches_oracle_and_geometry(OA, oracle):
+    """the device against the oracle on a scenario batch, and against closed-form answers on 64 single HALF-PLANES (the one shape on which the sub-problem is nearly
+    trivial; polygons, at every gap, against exact geometry: tests/test_gpu_dualws_geometry.py)"""
     N, B = 80, 64
     bt = S.make_batch(S.BACKWARDS, B, N)
     xWS = bt["xWS"]
