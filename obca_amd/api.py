@@ -57,6 +57,7 @@ def _load():
     cabi.bind(_lib, "obca_refine.h")                      # solved batches on a finer horizon: likewise
     cabi.bind(_lib, "obca_quad_subdivide.h")              # ... and solved quadcopter batches
     cabi.bind(_lib, "obca_plan_device.h")                 # the parking planner on the device
+    cabi.bind(_lib, "obca_plan_scenes.h")                 # ... in per-instance obstacle fields
     return _lib
 
 
@@ -85,6 +86,9 @@ QUAD_SUBDIVIDE_MAXFACTOR = 32      # OBCA_QUAD_SUBDIVIDE_MAXFACTOR
 PLAN_DEVICE_EXPORTS = ["obca_hybrid_configure", "obca_hybrid_astar_batch", "obca_hybrid_ms"]
 HYBRID_MAXMAP, HYBRID_MAXCELLS, HYBRID_MAXSLOTS, HYBRID_MAXNODES, HYBRID_DEFAULT_WIDTH = 35000, 6000000, 256, 1 << 20, 0.2      # the limits of include/obca_plan_device.h
 HYBRID_STATUS = {0: "no path", -1: "more nodes than cap", -2: "the start or goal pose collides", -3: "a sizing limit of the slot was hit (node pool, chunk pool)"}
+# include/obca_plan_scenes.h: the same planner, every search in the obstacle field of its own instance (scene_astar_batch, scene_ms, planner.scene_astar_many,
+# planner.scene_warm_start_many, scenarios.make_scene_batch(device=...)); slots, pools and status codes are the shared-field planner's
+SCENE_EXPORTS = ["obca_scene_astar_batch", "obca_scene_astar_ms"]
 QUAD_REFINE_STATUS = {0: "refined from the solution", 1: "interpolated from the uploaded warm start (the last solve failed, or its iterate is not finite)",
                       -1: "zero warm start (the uploaded one is not finite either)"}
 REFINE_STATUS = {0: "refined from the solution", 1: "refined from the start iterate (the last solve failed, or its iterate is not finite)", -1: "zero start (the start iterate is not finite either)"}
@@ -501,6 +505,29 @@ def hybrid_astar_batch(starts, goals, vOb, A, b, ego, L, XYbounds, opts=None, bu
     rc = _load().obca_hybrid_astar_batch(ctx._h, B, s, g, len(vOb), vOb, _in(A), _in(b), _in(ego), float(L), _in(XYbounds), o, 0 if o is None else len(o),
                                          0.0 if bucket_width is None else float(bucket_width), paths, dirs, cap, cnt, nexp, rounds)
     ctx._check(rc, "obca_hybrid_astar_batch")
+    return paths, dirs, cnt, nexp, rounds
+
+
+def scene_ms(device=0):
+    """HIP-event duration of the last per-instance search kernel (scene_astar_batch) of the context's device planner [ms]; hybrid_ms keeps the shared-field one"""
+    ctx = _ctx(device); a = C.c_float(0)
+    ctx._check(_load().obca_scene_astar_ms(ctx._h, C.byref(a)), "obca_scene_astar_ms")
+    return a.value
+
+
+def scene_astar_batch(starts, goals, vOb, A, b, ego, L, XYbounds, opts=None, bucket_width=None, cap=1024, device=0):
+    """obca_scene_astar_batch: B Hybrid A* searches on the GPU, one workgroup each, every search in the obstacle field of ITS OWN instance.  vOb, A, b: per-instance lists
+    (taken as they are) or one field (broadcast), as everywhere here (_norm_obstacles); an instance without obstacles is a free field inside XYbounds.  The rest is
+    hybrid_astar_batch's: starts, goals (B, >= 3), opts, the slots of hybrid_configure, the return value (paths (B, cap, 3), dirs (B, cap), counts (B,), expansions (B,),
+    rounds (B,)) and the counts codes (HYBRID_STATUS; -2: the pose collides with the instance's own field)."""
+    s = np.ascontiguousarray(np.asarray(starts, float)[:, :3]); g = np.ascontiguousarray(np.asarray(goals, float)[:, :3]); B = len(s); cap = int(cap)
+    nObs, vflat, Aflat, bflat = _norm_obstacles(B, vOb, A, b)
+    o = None if opts is None else np.ascontiguousarray(opts, float)
+    paths = np.zeros((B, max(cap, 0), 3)); dirs = np.zeros((B, max(cap, 0)), np.int32); cnt = np.zeros(B, np.int32); nexp = np.zeros(B, np.int32); rounds = np.zeros(B, np.int32)
+    ctx = _ctx(device)
+    rc = _load().obca_scene_astar_batch(ctx._h, B, s, g, _in(nObs, np.int32), _in(vflat, np.int32), _in(Aflat), _in(bflat), _in(ego), float(L), _in(XYbounds), o,
+                                        0 if o is None else len(o), 0.0 if bucket_width is None else float(bucket_width), paths, dirs, cap, cnt, nexp, rounds)
+    ctx._check(rc, "obca_scene_astar_batch")
     return paths, dirs, cnt, nexp, rounds
 
 

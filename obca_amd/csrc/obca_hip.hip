@@ -464,11 +464,13 @@ struct HybridBufs {
     char *slotmem = nullptr; size_t slot_bytes = 0; int nslots = 0, ncell = 0, nodes = 0, chunks = 0;
     char *io = nullptr; size_t io_bytes = 0; int lds_set = 0;
     hipEvent_t e0 = nullptr, e1 = nullptr; int have_ev = 0, timed = 0;
+    hipEvent_t s0 = nullptr, s1 = nullptr; int have_sev = 0, stimed = 0, lds_sset = 0;      // the per-instance call (obca_scene_astar_batch): events and LDS attribute of its own
     void release() {
         if (slotmem) (void)hipFree(slotmem);
         if (io) (void)hipFree(io);
         if (have_ev) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
-        slotmem = io = nullptr; slot_bytes = io_bytes = 0; nslots = have_ev = timed = 0;
+        if (have_sev) { (void)hipEventDestroy(s0); (void)hipEventDestroy(s1); }
+        slotmem = io = nullptr; slot_bytes = io_bytes = 0; nslots = have_ev = timed = have_sev = stimed = 0;
     }
 };
 }  // namespace
@@ -1780,15 +1782,20 @@ int obca_quadcopter_subdivide_batch(obca_ctx *ctx, int B, int N, int factor, con
 
 // the parking planner (obca_hybrid.h): `slots` persistent workgroups, workgroup s runs the searches s, s + slots, ... in its slot of the planner's memory.  LDS: the
 // holonomic map (nmap floats, padded to an even count), then the bucket heads and control words.
-__global__ __launch_bounds__(HY_NT) void obca_hybrid_kernel(int B, int slots, const hy::Params *__restrict__ Pp, hy::Field F, const unsigned char *__restrict__ blocked,
+// SCENES false: one field F for the batch, its blocked cells from the host (obca_hybrid_astar_batch).  SCENES true: search i runs in the field of instance i, put together
+// from the instance's record in S, and finds the blocked cells itself (obca_scene_astar_batch); F and blocked are not read.
+template <bool SCENES>
+__global__ __launch_bounds__(HY_NT) void obca_hybrid_kernel(int B, int slots, const hy::Params *__restrict__ Pp, hy::Field F, hy::Fields S, const unsigned char *__restrict__ blocked,
                                                             const double *__restrict__ inst, char *slotmem, size_t slot_bytes, double *paths, int *dirs, int *counts, int *nexp, int *rounds) {
     extern __shared__ float hy_lds[];
     const hy::Params &P = *Pp;
     if ((int)blockIdx.x >= slots) return;
     const hy::SlotMem M = hy::carve(slotmem + (size_t)blockIdx.x * slot_bytes, P.ncell, P.maxnodes, P.maxchunks);
     int *li = (int *)(hy_lds + ((P.nmap + 1) & ~1));
+    if (!SCENES) __builtin_assume(blocked != nullptr);      // (the host never launches this instantiation without the map: the search's own blocked test is not compiled into it)
     for (int i = blockIdx.x; i < B; i += slots)
-        hy::search(P, F, blocked, inst + (size_t)i * 10, M, hy_lds, li, paths + (size_t)i * P.cap * 3, dirs + (size_t)i * P.cap, counts + i, nexp + i, rounds + i);
+        hy::search(P, SCENES ? hy::field_of(S, i) : F, SCENES ? nullptr : blocked, inst + (size_t)i * 10, M, hy_lds, li, paths + (size_t)i * P.cap * 3, dirs + (size_t)i * P.cap,
+                   counts + i, nexp + i, rounds + i);
 }
 
 extern "C" {
@@ -1859,14 +1866,14 @@ int obca_hybrid_astar_batch(obca_ctx *ctx, int B, const double *starts, const do
     F.A = (const double *)(d + o_A); F.b = (const double *)(d + o_b); F.rn = (const double *)(d + o_rn); F.vert = (const double *)(d + o_vert);
     const int lds = (((P.nmap + 1) & ~1) + HY_LDS_INTS) * (int)sizeof(float);
     if (lds > h.lds_set) {
-        if (hipFuncSetAttribute((const void *)obca_hybrid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) { ctx->err = "obca_hybrid_astar_batch: hipFuncSetAttribute failed"; return -2; }
+        if (hipFuncSetAttribute((const void *)obca_hybrid_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) { ctx->err = "obca_hybrid_astar_batch: hipFuncSetAttribute failed"; return -2; }
         h.lds_set = lds;
     }
     int *dcnt = (int *)(d + o_cnt);
     bool ok = hipMemcpyAsync(d, up.data(), n_in, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
     ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess;      // (`up` is pageable and leaves scope)
     ok = ok && hipEventRecord(h.e0, ctx->stream) == hipSuccess;
-    hipLaunchKernelGGL(obca_hybrid_kernel, dim3(slots), dim3(HY_NT), lds, ctx->stream, B, slots, (const hy::Params *)d, F, (const unsigned char *)(d + o_blk), (const double *)(d + o_inst),
+    hipLaunchKernelGGL(obca_hybrid_kernel<false>, dim3(slots), dim3(HY_NT), lds, ctx->stream, B, slots, (const hy::Params *)d, F, hy::Fields(), (const unsigned char *)(d + o_blk), (const double *)(d + o_inst),
                        h.slotmem, sb, (double *)(d + o_paths), (int *)(d + o_dirs), dcnt, dcnt + B, dcnt + 2 * B);
     ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(h.e1, ctx->stream) == hipSuccess;
     std::vector<int> tail((size_t)3 * B);
@@ -1886,6 +1893,93 @@ int obca_hybrid_astar_batch(obca_ctx *ctx, int B, const double *starts, const do
 int obca_hybrid_ms(obca_ctx *ctx, float *ms) {
     if (!ctx || !ms) return -1;
     if (!ctx->hyb || !ctx->hyb->timed || hipEventElapsedTime(ms, ctx->hyb->e0, ctx->hyb->e1) != hipSuccess) { ctx->err = "obca_hybrid_ms: no search has run on this context"; return -2; }
+    return 0;
+}
+
+// ---- the same planner, every search in the obstacle field of its own instance (include/obca_plan_scenes.h): obca_hybrid_astar_batch's host side with the packed fields
+// and their records in place of the one field and its blocked map; the slots and the staging block are shared with it, the events are this call's own
+int obca_scene_astar_batch(obca_ctx *ctx, int B, const double *starts, const double *goals, const int *nOb, const int *vOb, const double *A, const double *b,
+                           const double ego[4], double L, const double XYbounds[4], const double *opts, int nopts, double bucket_width,
+                           double *paths, int *dirs, int cap, int *counts, int *expansions, int *rounds) {
+    if (!ctx) return -1;
+    if (!ctx->hyb) ctx->hyb = new HybridBufs();
+    HybridBufs &h = *ctx->hyb;
+    const int mn = h.max_nodes ? h.max_nodes : OBCA_HYBRID_MAXNODES, mc = h.max_chunks ? h.max_chunks : hy::default_chunks(mn);
+    hy::Params P; hy::HostFields W; std::vector<double> inst;
+    const std::string bad = (paths && dirs && counts) ? hy::make_scenes(B, starts, goals, nOb, vOb, A, b, ego, L, XYbounds, opts, nopts, bucket_width, cap, mn, mc, P, W, inst)
+                                                      : std::string("NULL output array");
+    if (!bad.empty()) { ctx->err = "obca_scene_astar_batch: " + bad; return -1; }
+    use_device(ctx->device);
+    if (!h.have_sev) {
+        if (hipEventCreate(&h.s0) != hipSuccess) { ctx->err = "hipEventCreate failed"; return -2; }
+        if (hipEventCreate(&h.s1) != hipSuccess) { (void)hipEventDestroy(h.s0); ctx->err = "hipEventCreate failed"; return -2; }
+        h.have_sev = 1;
+    }
+    h.stimed = 0;
+    const size_t sb = hy::slot_bytes(P.ncell, mn, mc);
+    int slots = h.slots ? h.slots : (int)std::min<size_t>(OBCA_HYBRID_MAXSLOTS, std::max<size_t>(1, OBCA_HYBRID_BUDGET / sb));
+    slots = std::min(slots, B);
+    if (!h.slotmem || h.nslots < slots || h.ncell != P.ncell || h.nodes != mn || h.chunks != mc) {
+        if (h.slotmem) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.slotmem); h.slotmem = nullptr; h.nslots = 0; }
+        if (hipMalloc((void **)&h.slotmem, sb * slots) != hipSuccess) { h.slotmem = nullptr; ctx->err = "obca_scene_astar_batch: hipMalloc of the slots failed (fewer slots or nodes: obca_hybrid_configure)"; return -2; }
+        h.slot_bytes = sb; h.nslots = slots; h.ncell = P.ncell; h.nodes = mn; h.chunks = mc;
+        bool ok = true;      // claim words and cell table: all ones; a search leaves them so
+        for (int s = 0; s < slots && ok; s++) ok = hipMemsetAsync(h.slotmem + (size_t)s * sb, 0xFF, hy::slot_init_bytes(P.ncell), ctx->stream) == hipSuccess;
+        if (!ok) { ctx->err = "obca_scene_astar_batch: hipMemsetAsync failed"; h.release(); return -2; }
+    }
+    // one block up: [ Params | inst B x 10 | A | b | rn | nrm | vert | rec (B x 4) v off voff (ints) ], one block down: [ paths | dirs | counts | expansions | rounds ]
+    auto up8 = [](size_t n) { return (n + 7) / 8 * 8; };
+    const size_t M_ = W.b.size(), nv = W.vert.size(), nob = W.v.size(), noff = W.off.size();      // (noff = nob + B)
+    const size_t o_inst = up8(sizeof(hy::Params)), o_A = o_inst + inst.size() * 8, o_b = o_A + 2 * M_ * 8, o_rn = o_b + M_ * 8, o_nrm = o_rn + M_ * 8, o_vert = o_nrm + M_ * 8,
+                 o_rec = o_vert + nv * 8, o_v = o_rec + (size_t)4 * B * 4, o_off = o_v + nob * 4, o_voff = o_off + noff * 4, n_in = up8(o_voff + noff * 4);
+    const size_t o_paths = n_in, o_dirs = o_paths + (size_t)B * cap * 24, o_cnt = o_dirs + up8((size_t)B * cap * 4), n_all = o_cnt + up8((size_t)3 * B * 4);
+    if (h.io_bytes < n_all) {
+        if (h.io) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.io); h.io = nullptr; h.io_bytes = 0; }
+        if (hipMalloc((void **)&h.io, n_all) != hipSuccess) { h.io = nullptr; ctx->err = "obca_scene_astar_batch: hipMalloc failed"; h.release(); return -2; }
+        h.io_bytes = n_all;
+    }
+    std::vector<char> up(n_in, 0);
+    memcpy(up.data(), &P, sizeof P); memcpy(up.data() + o_inst, inst.data(), inst.size() * 8);
+    if (M_) {
+        memcpy(up.data() + o_A, W.A.data(), 2 * M_ * 8); memcpy(up.data() + o_b, W.b.data(), M_ * 8); memcpy(up.data() + o_rn, W.rn.data(), M_ * 8);
+        memcpy(up.data() + o_nrm, W.nrm.data(), M_ * 8);
+    }
+    if (nv) memcpy(up.data() + o_vert, W.vert.data(), nv * 8);
+    memcpy(up.data() + o_rec, W.rec.data(), (size_t)4 * B * 4);
+    if (nob) memcpy(up.data() + o_v, W.v.data(), nob * 4);
+    memcpy(up.data() + o_off, W.off.data(), noff * 4); memcpy(up.data() + o_voff, W.voff.data(), noff * 4);
+    char *d = h.io;
+    hy::Fields S; S.rec = (const int *)(d + o_rec); S.v = (const int *)(d + o_v); S.off = (const int *)(d + o_off); S.voff = (const int *)(d + o_voff);
+    S.A = (const double *)(d + o_A); S.b = (const double *)(d + o_b); S.rn = (const double *)(d + o_rn); S.nrm = (const double *)(d + o_nrm); S.vert = (const double *)(d + o_vert);
+    const int lds = (((P.nmap + 1) & ~1) + HY_LDS_INTS) * (int)sizeof(float);
+    if (lds > h.lds_sset) {
+        if (hipFuncSetAttribute((const void *)obca_hybrid_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) { ctx->err = "obca_scene_astar_batch: hipFuncSetAttribute failed"; h.release(); return -2; }
+        h.lds_sset = lds;
+    }
+    int *dcnt = (int *)(d + o_cnt);
+    bool ok = hipMemcpyAsync(d, up.data(), n_in, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess;      // (`up` is pageable and leaves scope)
+    ok = ok && hipEventRecord(h.s0, ctx->stream) == hipSuccess;
+    if (ok) hipLaunchKernelGGL(obca_hybrid_kernel<true>, dim3(slots), dim3(HY_NT), lds, ctx->stream, B, slots, (const hy::Params *)d, hy::Field(), S, (const unsigned char *)nullptr,
+                               (const double *)(d + o_inst), h.slotmem, sb, (double *)(d + o_paths), (int *)(d + o_dirs), dcnt, dcnt + B, dcnt + 2 * B);
+    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(h.s1, ctx->stream) == hipSuccess;
+    std::vector<int> tail((size_t)3 * B);
+    ok = ok && hipMemcpyAsync(paths, d + o_paths, (size_t)B * cap * 24, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(dirs, d + o_dirs, (size_t)B * cap * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(tail.data(), dcnt, (size_t)3 * B * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess || !ok) {
+        ctx->err = "obca_scene_astar_batch: kernel or copy failed";
+        h.release();      // the slots may hold a half-finished search: the next call starts from fresh ones
+        return -2;
+    }
+    for (int i = 0; i < B; i++) { counts[i] = tail[i]; if (expansions) expansions[i] = tail[B + i]; if (rounds) rounds[i] = tail[2 * B + i]; }
+    h.stimed = 1;
+    return 0;
+}
+
+int obca_scene_astar_ms(obca_ctx *ctx, float *ms) {
+    if (!ctx || !ms) return -1;
+    if (!ctx->hyb || !ctx->hyb->stimed || hipEventElapsedTime(ms, ctx->hyb->s0, ctx->hyb->s1) != hipSuccess) { ctx->err = "obca_scene_astar_ms: no per-instance search has run on this context"; return -2; }
     return 0;
 }
 

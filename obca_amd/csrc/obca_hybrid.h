@@ -17,7 +17,11 @@
 // no libm result enters: the search itself calls none (heading as (sin, cos), rotated by per-primitive constants from the host; distances by sqrt), the Reeds-Shepp curves do.
 // No contraction of a * b + c into an fma anywhere in this file.
 // The holonomic map (2-D fp32 cost-to-go of a disc robot, per search: goals differ) is relaxed in LDS until nothing changes, as obca_plan3d.h does; the blocked cells, row
-// norms, obstacle vertices and edge weights come from the host.  Every loop is bounded: rounds by P.maxrounds, expansions by maxexp (a round whose live entries would pass it is not expanded), sweeps by the cell count, the chain walk
+// norms, obstacle vertices and edge weights come from the host.
+// Per-instance obstacle fields (include/obca_plan_scenes.h): the same search, called with the field of its own instance (field_of: a record of offsets into arrays that
+// hold the fields of the whole batch, make_fields) and without a blocked map -- it then finds the blocked cells itself while it initialises the map (cell_blocked: the
+// host's test with the row norm read from memory, so still no libm), 512 threads sharing the cells.  Nothing else of a search depends on which route called it.
+// Every loop is bounded: rounds by P.maxrounds, expansions by maxexp (a round whose live entries would pass it is not expanded), sweeps by the cell count, the chain walk
 // by the node count, wrap() by its own count.
 #pragma once
 #include <math.h>
@@ -27,6 +31,7 @@
 #include <vector>
 #include "../../include/obca_plan.h"
 #include "../../include/obca_plan_device.h"
+#include "../../include/obca_plan_scenes.h"
 
 #ifdef OBCA_EMU
 #define HY_FN static inline
@@ -63,10 +68,16 @@ struct Params {      // one per call, built on the host (make_params)
     double xmin, xmax, ymin, ymax, res, yres, step, dsub, smax, margin, gtol, ytol, crev, csw, cst, cchg, hweight, L, Rmin, RminH, bw, ego[4];
     float w1, w2;                                          // edge weights of the holonomic map: (float)(res hypot(1, 0)), (float)(res hypot(1, 1))
     double kap[HY_NSI], steer[HY_NSI], sd[HY_NSI], cd[HY_NSI];      // per steering command: curvature, angle, sin / cos of the heading change of one forward sub-step
+    double rad;                                            // radius of the disc robot of the holonomic map: 0.9 of the car's half width (or half length, if that is less)
 };
-struct Field {      // the obstacle field, shared by the batch
+struct Field {      // the obstacle field of a search: the batch's (obca_hybrid_astar_batch), or the instance's own (obca_scene_astar_batch: field_of)
     int nOb; const int *v, *off, *voff; const double *A, *b, *rn, *vert;
+    const double *nrm = nullptr;      // the row norms hypot(A0, A1) (rn = 1 / nrm): read by cell_blocked only, that is by a search without a blocked map from the host
 };
+// The fields of a batch of scenes, instance after instance in flat arrays (make_fields).  rec: four ints per instance -- where its obstacles, rows and polygon vertices
+// start, and how many obstacles it has; off and voff carry one entry more than obstacles per instance (so instance i starts at its obstacle offset + i) and count from
+// the instance's own first row / vertex.
+struct Fields { const int *rec, *v, *off, *voff; const double *A, *b, *rn, *nrm, *vert; };
 struct Node { double x, y, yaw, s, c; float g; int parent, cell, bucket, pos; signed char dir, si; };
 struct SlotMem { Node *nodes; unsigned *cell_g; int *cell_node; u64 *claim; int *touched, *far, *chunks, *chunklist; };
 struct P2 { double x, y; };
@@ -159,6 +170,30 @@ HY_FN bool collides_cs(const Params &P, const Field &w, double x, double y, doub
         if (n >= 3) {
             double area = 0; for (int i = 0; i < n; i++) { const P2 p = cur[i], q = cur[i + 1 == n ? 0 : i + 1]; area += p.x * q.y - q.x * p.y; }
             if (fabs(area) > 1e-9) return true;
+        }
+    }
+    return false;
+}
+
+// The field of instance i of a batch of scenes (the values are the same in every lane of the workgroup)
+HY_HD Field field_of(const Fields &S, int i) {
+    const int ob = S.rec[4 * i], row = S.rec[4 * i + 1], vx = S.rec[4 * i + 2];
+    Field F; F.nOb = S.rec[4 * i + 3]; F.v = S.v + ob; F.off = S.off + ob + i; F.voff = S.voff + ob + i;
+    F.A = S.A + 2 * (size_t)row; F.b = S.b + row; F.rn = S.rn + row; F.nrm = S.nrm + row; F.vert = S.vert + 2 * (size_t)vx;
+    return F;
+}
+// Can a disc of radius P.rad stand on cell (ix, iy) of the holonomic map?  disc_collides (below, the host's: obca_planner.cpp's) for one cell, statement by statement,
+// with the host's hypot(A0, A1) read from F.nrm: no libm, no contraction, the same fp64 operations in the same order -- so the same byte as the host's map.
+HY_HD bool cell_blocked(const Params &P, const Field &F, int ix, int iy) {
+    const double x = P.xmin + ix * P.res, y = P.ymin + iy * P.res, rad = P.rad;
+    for (int j = 0; j < F.nOb; j++) {
+        double worst = -1e300;
+        for (int i = 0; i < F.v[j]; i++) { const int r = F.off[j] + i; const double e = (F.A[2 * r] * x + F.A[2 * r + 1] * y - F.b[r]) / F.nrm[r]; worst = e > worst ? e : worst; }
+        if (worst < rad) {
+            if (worst <= 0) return true;
+            int cnt = 0; double d2 = 0;
+            for (int i = 0; i < F.v[j]; i++) { const int r = F.off[j] + i; const double e = (F.A[2 * r] * x + F.A[2 * r + 1] * y - F.b[r]) / F.nrm[r]; if (e > 0) { d2 += e * e; cnt++; } }
+            if (cnt <= 1 || d2 < rad * rad) return true;
         }
     }
     return false;
@@ -374,6 +409,8 @@ static float *emu_map_out = nullptr;      // the holonomic map of the last searc
 
 // ---------------------------------------------------------------- one search
 // in: start x, y, yaw, sin, cos; goal x, y, yaw, sin, cos.  hmap: P.nmap floats and li: HY_LDS_INTS ints, in LDS.  path cap x 3, dirs cap.
+// blocked: the cells of the holonomic map a disc cannot stand on, P.nmap bytes from the host -- or NULL: the search finds them itself from F (cell_blocked, needs F.nrm),
+// the threads sharing the cells as they share the relaxation.  Everything else the search knows of the obstacles it reads through F, nothing through P.
 HY_FN void search(const Params &P, const Field &F, const unsigned char *blocked, const double *in, const SlotMem &M, float *hmap, int *li,
                   double *path, int *dirs, int *count, int *nexp_out, int *rounds_out) {
     Buckets K; K.bh = li; K.bt = li + HY_W; K.bc = li + 2 * HY_W; K.ba = li + 3 * HY_W; K.bn = li + 4 * HY_W; K.ctl = li + 5 * HY_W;
@@ -389,7 +426,7 @@ HY_FN void search(const Params &P, const Field &F, const unsigned char *blocked,
     if (HY_TID0) { for (int i = 0; i < C_WORDS; i++) ctl[i] = 0; *fin = HY_NONE; }
     if (run) {
         const int gx = round_idx((goal[0] - P.xmin) / P.res, P.nx), gy = round_idx((goal[1] - P.ymin) / P.res, P.ny), gid = gy * P.nx + gx;
-        HY_FOR(c, P.nmap) hmap[c] = c == gid ? 0.f : (blocked[c] ? -1.f : HUGE_VALF);
+        HY_FOR(c, P.nmap) hmap[c] = c == gid ? 0.f : ((blocked ? blocked[c] != 0 : cell_blocked(P, F, c % P.nx, c / P.nx)) ? -1.f : HUGE_VALF);
         HY_BARRIER();
         bool settled = false;
         for (int s = 0; !settled && s < P.nmap; s++) {
@@ -600,7 +637,9 @@ HY_FN void search(const Params &P, const Field &F, const unsigned char *blocked,
 }
 
 // ================================================================ host code: the arguments, the parameter block, the obstacle field, the blocked cells
-struct HostField { std::vector<int> v, off, voff; std::vector<double> A, b, rn, vert; };
+struct HostField { std::vector<int> v, off, voff; std::vector<double> A, b, rn, vert, nrm; };
+// the fields of a batch of scenes as `Fields` reads them (make_fields)
+struct HostFields { std::vector<int> rec, v, off, voff; std::vector<double> A, b, rn, nrm, vert; };
 
 static inline bool finite_(double v) { return v - v == 0.0; }
 static inline double hmin(double a, double b) { return a < b ? a : b; }
@@ -628,6 +667,14 @@ static inline int host_clip(const P2 *in, int n, double ax, double ay, double bb
     }
     return m;
 }
+// one obstacle as a polygon (World::finish): its `rows` half-planes cut from a square of half side far_; the vertices are appended to `vert`
+static inline void host_polygon(const double *A, const double *b, int rows, double far_, std::vector<double> &vert) {
+    P2 pa[HY_CLIP] = {{far_, far_}, {-far_, far_}, {-far_, -far_}, {far_, -far_}}, pb[HY_CLIP];
+    int n = 4; P2 *cur = pa, *nxt = pb;
+    for (int i = 0; i < rows && n > 0; i++) { n = host_clip(cur, n, A[2 * i], A[2 * i + 1], b[i], nxt); P2 *t = cur; cur = nxt; nxt = t; }
+    for (int i = 0; i < n; i++) { vert.push_back(cur[i].x); vert.push_back(cur[i].y); }
+}
+static inline double host_far(const double *XYbounds) { return 1e3 + hmax(hmax(fabs(XYbounds[0]), fabs(XYbounds[1])), hmax(fabs(XYbounds[2]), fabs(XYbounds[3]))); }
 
 // NULL if the call is good (then P, W, blocked and inst -- B x 10 doubles: start and goal with sin, cos of their headings -- are filled), else what is wrong
 static inline const char *make_params(int B, const double *starts, const double *goals, int nOb, const int *vOb, const double *A, const double *b, const double *ego, double L,
@@ -676,23 +723,21 @@ static inline const char *make_params(int B, const double *starts, const double 
     W.v.assign(vOb, vOb + nOb); W.off.assign(nOb + 1, 0);
     for (int j = 0; j < nOb; j++) { if (vOb[j] < 1 || vOb[j] > OBCA_HYBRID_MAXROWS) return "need 1 .. OBCA_HYBRID_MAXROWS rows per obstacle"; W.off[j + 1] = W.off[j] + vOb[j]; }
     const int M_ = W.off[nOb];
-    W.A.assign(A, A + 2 * M_); W.b.assign(b, b + M_); W.rn.resize(M_);
+    W.A.assign(A, A + 2 * M_); W.b.assign(b, b + M_); W.rn.resize(M_); W.nrm.resize(M_);
     for (int r = 0; r < M_; r++) {
         if (!finite_(A[2 * r]) || !finite_(A[2 * r + 1]) || !finite_(b[r])) return "an obstacle row is not finite";
-        const double n = hypot(A[2 * r], A[2 * r + 1]); W.rn[r] = n > 0 ? 1.0 / n : 0.0;
+        const double n = hypot(A[2 * r], A[2 * r + 1]); W.rn[r] = n > 0 ? 1.0 / n : 0.0; W.nrm[r] = n;
     }
-    const double far_ = 1e3 + hmax(hmax(fabs(P.xmin), fabs(P.xmax)), hmax(fabs(P.ymin), fabs(P.ymax)));
+    const double far_ = host_far(XYbounds);
     W.voff.assign(nOb + 1, 0); W.vert.clear();
     for (int j = 0; j < nOb; j++) {
-        P2 pa[HY_CLIP] = {{far_, far_}, {-far_, far_}, {-far_, -far_}, {far_, -far_}}, pb[HY_CLIP];
-        int n = 4; P2 *cur = pa, *nxt = pb;
-        for (int i = 0; i < W.v[j] && n > 0; i++) { const int r = W.off[j] + i; n = host_clip(cur, n, W.A[2 * r], W.A[2 * r + 1], W.b[r], nxt); P2 *t = cur; cur = nxt; nxt = t; }
-        for (int i = 0; i < n; i++) { W.vert.push_back(cur[i].x); W.vert.push_back(cur[i].y); }
+        host_polygon(W.A.data() + 2 * (size_t)W.off[j], W.b.data() + W.off[j], W.v[j], far_, W.vert);
         W.voff[j + 1] = (int)W.vert.size() / 2;
     }
     P.nOb = nOb; P.nrows = M_; P.nvert = (int)W.vert.size() / 2;
     // the cells a disc of the car's half width cannot stand on (the holonomic map's obstacles): a property of the field, not of the goal
     const double rad = hmin(hmin(ego[1], ego[3]), 0.5 * (ego[0] + ego[2])) * 0.9;
+    P.rad = rad;
     blocked.assign((size_t)P.nmap, 0);
     for (int iy = 0; iy < P.ny; iy++) for (int ix = 0; ix < P.nx; ix++) blocked[(size_t)iy * P.nx + ix] = disc_collides(W, nOb, P.xmin + ix * P.res, P.ymin + iy * P.res, rad);
     inst.resize((size_t)B * 10);
@@ -701,6 +746,47 @@ static inline const char *make_params(int B, const double *starts, const double 
         q[0] = p[0]; q[1] = p[1]; q[2] = p[2]; q[3] = sin(p[2]); q[4] = cos(p[2]);
     }
     return nullptr;
+}
+// The fields of B instances, packed for `Fields`: nOb[i] obstacles per instance, their row counts in vOb, rows in A (x 2) and b, instance after instance.  Per instance
+// what make_params does for its one field: rows, 1 / norm, norm, the obstacles as clipped polygons; and the record of its offsets.  Empty if the fields are good, else
+// what is wrong with the FIRST instance that has something wrong.
+static inline std::string make_fields(int B, const int *nOb, const int *vOb, const double *A, const double *b, const double *XYbounds, HostFields &W) {
+    if (B < 1 || !nOb || !XYbounds) return "need B >= 1 and non-NULL nOb, XYbounds";
+    const double far_ = host_far(XYbounds);
+    W = HostFields();
+    long long ob = 0, row = 0;
+    for (int i = 0; i < B; i++) {
+        const std::string who = "instance " + std::to_string(i) + ": ";
+        if (nOb[i] < 0) return who + "a negative obstacle count";
+        if (nOb[i] > OBCA_HYBRID_MAXOB) return who + "more than OBCA_HYBRID_MAXOB obstacles";
+        if (nOb[i] > 0 && (!vOb || !A || !b)) return who + "obstacles, but vOb, A or b is NULL";
+        W.rec.push_back((int)ob); W.rec.push_back((int)row); W.rec.push_back((int)(W.vert.size() / 2)); W.rec.push_back(nOb[i]);
+        const long long row0 = row; const size_t vert0 = W.vert.size() / 2;
+        for (int j = 0; j < nOb[i]; j++) {
+            const int v = vOb[ob + j];
+            if (v < 1 || v > OBCA_HYBRID_MAXROWS) return who + "need 1 .. OBCA_HYBRID_MAXROWS rows per obstacle";
+            for (long long r = row; r < row + v; r++) {
+                if (!finite_(A[2 * r]) || !finite_(A[2 * r + 1]) || !finite_(b[r])) return who + "an obstacle row is not finite";
+                const double n = hypot(A[2 * r], A[2 * r + 1]);
+                W.A.push_back(A[2 * r]); W.A.push_back(A[2 * r + 1]); W.b.push_back(b[r]); W.rn.push_back(n > 0 ? 1.0 / n : 0.0); W.nrm.push_back(n);
+            }
+            W.v.push_back(v); W.off.push_back((int)(row - row0)); W.voff.push_back((int)(W.vert.size() / 2 - vert0));
+            host_polygon(A + 2 * row, b + row, v, far_, W.vert);
+            row += v;
+        }
+        W.off.push_back((int)(row - row0)); W.voff.push_back((int)(W.vert.size() / 2 - vert0));
+        ob += nOb[i];
+    }
+    return std::string();
+}
+// obca_scene_astar_batch's arguments: make_params for everything but the fields (P, inst; P.nOb, nrows, nvert stay zero: a search reads its field through F), then
+// make_fields.  Empty if the call is good.
+static inline std::string make_scenes(int B, const double *starts, const double *goals, const int *nOb, const int *vOb, const double *A, const double *b, const double *ego, double L,
+                                      const double *XYbounds, const double *opts_in, int nopts, double bucket_width, int cap, int maxnodes, int maxchunks,
+                                      Params &P, HostFields &W, std::vector<double> &inst) {
+    HostField none; std::vector<unsigned char> free_map;
+    if (const char *bad = make_params(B, starts, goals, 0, nullptr, nullptr, nullptr, ego, L, XYbounds, opts_in, nopts, bucket_width, cap, maxnodes, maxchunks, P, none, free_map, inst)) return bad;
+    return make_fields(B, nOb, vOb, A, b, XYbounds, W);
 }
 // Chunks of a slot by default.  A bucket takes a chunk whenever it goes from empty to not empty (at most once per round and per bucket of a window) and one per
 // HY_CE entries beyond that, so a search of R rounds and n nodes needs at most n / HY_CE + R + HY_W per window: a quarter of the nodes covers what was measured.

@@ -363,6 +363,64 @@ def warm_start_many(sc, x0, xF, N, workers=None, smooth=False, device=None, sear
     return out
 
 
+def _scene_dense(starts, goals, vOb, A, b, ego, L, XYbounds, cap, kw, device, bucket_width=None):
+    """obca_scene_astar_batch (include/obca_plan_scenes.h) with the return value of _hybrid_astar_dense: every search on the GPU, in the field of its own instance"""
+    from . import api
+    s = np.ascontiguousarray(np.asarray(starts, float)[:, :3]); g = np.ascontiguousarray(np.asarray(goals, float)[:, :3])
+    o = dict(DEFAULT_OPTS); o.update(kw)
+    opts = np.array([o[k] for k in DEFAULT_OPTS], float)
+    paths, dirs, cnt, nexp, _ = api.scene_astar_batch(s, g, vOb, A, b, ego, L, XYbounds, opts, bucket_width, cap, device)
+    return s, g, paths, dirs, cnt, nexp
+
+
+def _fields_of(vOb, A, b, idx, B):
+    """the obstacle fields of the instances idx: per-instance lists are cut, one shared field stays what it is"""
+    if isinstance(vOb, (list, tuple)) and len(vOb) == B and np.ndim(vOb[0]) >= 1:
+        return [vOb[i] for i in idx], [A[i] for i in idx], [b[i] for i in idx]
+    return vOb, A, b
+
+
+def _scene_again(s, g, vOb, A, b, ego, L, XYbounds, kw, device, bucket_width, long_):
+    """the searches whose path has more than cap nodes, once more on the device with room for 20000"""
+    v2, A2, b2 = _fields_of(vOb, A, b, long_, len(s))
+    return _scene_dense(s[long_], g[long_], v2, A2, b2, ego, L, XYbounds, 20000, kw, device, bucket_width)
+
+
+def scene_astar_many(starts, goals, vOb, A, b, ego=S.EGO, L=S.L_WHEELBASE, XYbounds=S.XYBOUNDS, device=0, bucket_width=None, cap=1024, **kw):
+    """B searches on the GPU, each in the obstacle field of its own instance (obca_scene_astar_batch; vOb, A, b: per-instance lists, or one field for all): a list of
+    (path, dir, expansions) / None -- hybrid_astar_many(device=...)'s contract: a path of more than cap nodes is searched again on the device with room for 20000; an
+    instance without a path, with a start or goal pose that collides with its own field, or whose search outgrew its slot (count -3, api.HYBRID_STATUS) is None, alone.
+    There is no host fallback."""
+    s, g, paths, dirs, cnt, nexp = _scene_dense(starts, goals, vOb, A, b, ego, L, XYbounds, cap, kw, device, bucket_width)
+    out = [(paths[i, :cnt[i]].copy(), dirs[i, :cnt[i]].copy(), int(nexp[i])) if cnt[i] > 0 else None for i in range(len(s))]
+    long_ = np.flatnonzero(cnt == -1)
+    if len(long_):
+        _, _, p2, d2, c2, n2 = _scene_again(s, g, vOb, A, b, ego, L, XYbounds, kw, device, bucket_width, long_)
+        for j, i in enumerate(long_):
+            out[i] = (p2[j, :c2[j]].copy(), d2[j, :c2[j]].copy(), int(n2[j])) if c2[j] > 0 else None
+    return out
+
+
+def scene_warm_start_many(x0, xF, N, vOb, A, b, device=0, smooth=False, v_nom=0.5, bucket_width=None, **kw):
+    """warm starts of a batch whose instances have obstacle fields of their own: scene_astar_many's searches, then path_to_warm_start_many on the same device.  Returns a
+    list of (Ts, xWS (N+1, 4), uWS (N, 2)) / None; a path of more than `cap` nodes is searched again on the device and resampled by numpy, as in
+    warm_start_many(search="device").  kw: ego, L, XYbounds, cap and the search options."""
+    o = dict(kw)
+    geo = dict(ego=o.pop("ego", S.EGO), L=o.pop("L", S.L_WHEELBASE), XYbounds=o.pop("XYbounds", S.XYBOUNDS)); cap = o.pop("cap", 1024)
+    x0 = np.asarray(x0, float); xF = np.asarray(xF, float)
+    if len(x0) == 0:
+        return []
+    s, g, paths, dirs, cnt, _ = _scene_dense(x0[:, :3], xF[:, :3], vOb, A, b, geo["ego"], geo["L"], geo["XYbounds"], cap, o, device, bucket_width)
+    Ts, xWS, uWS, ok = path_to_warm_start_many(paths, dirs, cnt, N, xF, v_nom=v_nom, L=geo["L"], smooth=smooth, device=device)
+    out = [(float(Ts[i]), xWS[i], uWS[i]) if ok[i] else None for i in range(len(cnt))]
+    long_ = np.flatnonzero(cnt == -1)
+    if len(long_):
+        _, _, p2, d2, c2, _ = _scene_again(s, g, vOb, A, b, geo["ego"], geo["L"], geo["XYbounds"], o, device, bucket_width, long_)
+        for j, i in enumerate(long_):
+            out[i] = None if c2[j] <= 0 else path_to_warm_start(p2[j, :c2[j]], d2[j, :c2[j]], N, xF[i], v_nom=v_nom, L=geo["L"], smooth=smooth)
+    return out
+
+
 # ---------------------------------------------------------------- quadcopter: 3-D grid A* (a_star_3D.jl, mainQuadcopter.jl:108-138)
 QUAD_ROOM = (10.0, 10.0, 5.0)
 

@@ -391,6 +391,69 @@ def make_mixed_batch(B, N=80, seed=20260925, max_extra=7, min_obstacles=3, rows=
     return base
 
 
+def scene_field(rng, start, boxes=(1, 3)):
+    """the obstacle field of one scene: the backwards scenario plus boxes[0] .. boxes[1] axis-parallel boxes ON THE ROAD (centre x in +-12 but not within 3 m of the
+    slot's mouth, y in 6 .. 10, half sides 0.3 .. 0.8 m), each kept only if the car at `start` stays 0.5 m clear of it (20 attempts per box).  A path through the
+    three-obstacle field may well cross them: the field has to be planned in.  Returns (rows per obstacle, A, b)."""
+    from . import planner
+    sc = BACKWARDS
+    lOb = [list(map(list, o)) for o in sc["lOb"]]; vOb = list(sc["vOb"])
+    n = int(rng.integers(boxes[0], boxes[1] + 1))
+    for _ in range(n):
+        for attempt in range(20):
+            cx = rng.uniform(-12, 12); cy = rng.uniform(6.0, 10.0); hx = rng.uniform(0.3, 0.8); hy = rng.uniform(0.3, 0.8)
+            if abs(cx) < 3.0:                                              # not in front of the slot's mouth
+                continue
+            pts = [[cx - hx, cy + hy], [cx + hx, cy + hy], [cx + hx, cy - hy], [cx - hx, cy - hy]]      # clockwise
+            A1, b1 = obst_hrep(1, [5], [pts + [pts[0]]])
+            if planner.collides(np.asarray(start, float)[:3], np.array([4]), A1, b1, margin=0.5):      # keep the start pose clear
+                continue
+            lOb.append(pts + [pts[0]]); vOb.append(5)
+            break
+    A, b = obst_hrep(len(vOb), vOb, lOb)
+    return np.asarray(vOb) - 1, A, b
+
+
+def scene_inputs(B, seed=20260925, boxes=(1, 3)):
+    """what make_scene_batch plans: the random stream, the backwards scenario's poses (all starts first) and then, instance after instance, the fields of scene_field"""
+    rng = np.random.default_rng(seed)
+    x0, xF = sample_poses(BACKWARDS, B, rng)
+    return rng, x0, xF, [scene_field(rng, x0[i], boxes) for i in range(B)]
+
+
+def make_scene_batch(B, N=80, seed=20260925, boxes=(1, 3), device=None):
+    """a batch whose instances have to be PLANNED in their own obstacle fields: the backwards scenario's poses, and per instance the field of scene_field -- boxes on the
+    road, where the plan of the three-obstacle field drives.  device=None: one planner.hybrid_astar per instance on the host, then path_to_warm_start; a device index (or
+    an api.Context): planner.scene_warm_start_many -- the searches of the whole batch on that GPU, each in its own field, and the resampling there too.  An instance
+    without a plan gets a new start pose and a new field from the same stream, as in plan_batch.  Returns make_mixed_batch's dict: vOb, A, b are per-instance lists."""
+    from . import planner as PL
+    rng, x0, xF, fields = scene_inputs(B, seed, boxes)
+    o, v_nom = PL.SCENARIO_OPTS["backwards"]
+    Ts = np.zeros(B); xWS = np.zeros((B, N + 1, 4)); uWS = np.zeros((B, N, 2))
+    todo = list(range(B))
+    while todo:
+        if device is None:
+            res = []
+            for i in todo:
+                try:
+                    r = PL.hybrid_astar(x0[i, :3], xF[i, :3], *fields[i], **o)
+                except ValueError:      # the start or goal pose collides
+                    r = None
+                res.append(None if r is None else PL.path_to_warm_start(r[0], r[1], N, xF[i], v_nom=v_nom))
+        else:
+            res = PL.scene_warm_start_many(x0[todo], xF[todo], N, [fields[i][0] for i in todo], [fields[i][1] for i in todo], [fields[i][2] for i in todo],
+                                           device=device, v_nom=v_nom, **o)
+        nxt = []
+        for i, r in zip(todo, res):
+            if r is None:
+                x0[i] = _draw_start(rng); fields[i] = scene_field(rng, x0[i], boxes); nxt.append(i)
+            else:
+                Ts[i], xWS[i], uWS[i] = r
+        todo = nxt
+    return dict(x0=x0, xF=xF, Ts=Ts, xWS=xWS, uWS=uWS, A=[f[1] for f in fields], b=[f[2] for f in fields], vOb=[f[0] for f in fields], N=N, L=L_WHEELBASE,
+                ego=EGO.copy(), XYbounds=XYBOUNDS.copy())
+
+
 def make_corridor_batch(B, N=80, seed=20260925, n_extra=(3, 7), clearance=(0.0, 0.2)):
     """config-5 style batch whose extra obstacles BIND: the backwards-parking scenario plus n_extra[0]..n_extra[1] wedges per instance that narrow the road from its two
     sides -- triangles standing on the upper wall (y = 11) or on the blocks beside the slot (y = 5), sloped rows through obstHrep -- with their tips `clearance` metres
