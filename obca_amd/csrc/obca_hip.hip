@@ -12,6 +12,8 @@
 //   obca_path_ws_*_kernel   : one wavefront per instance, the parking warm start from a planner path (obca_path_ws.h): into host-bound arrays or into a resident batch.
 //   obca_shift_kernel, obca_quad_shift_kernel : receding-horizon restarts, one workgroup per instance: the warm start of the next solve from the last solution
 //                             (parking: below; quadcopter: obca_quad_shift.h).
+// Host helpers the entry points are built from (below "host side"): EventPair, KernelStage (staging types); run_validate, launch_timed (a kernel between two events, results down);
+//   run_chunks with parking_chunks / quad_chunks (host-pointer calls over the slots); into_call (refine / subdivide into a second batch); hybrid_call (both planner entry points).
 // Memory (per instance, fp64, all in HBM; sizes for N=80, 3 obstacles / 5 rows in brackets):
 //   prob  header+rx,ry,ryaw   [495]      z, zn  primal-dual iterate and the line search's
 //   trial point (they swap) [6797 each]      d  stage part of the search direction [~650 used]
@@ -397,17 +399,6 @@ __global__ __launch_bounds__(256) void obca_gather_rows_kernel(double *dst, size
 struct obca_batch;
 struct obca_quad_batch;
 struct Slot { int device; hipStream_t stream; obca_batch *pb; obca_quad_batch *qb; int cus; };
-namespace { struct PathWsBufs; struct HybridBufs; }
-struct obca_ctx {
-    int device; hipStream_t stream;         // primary device / stream (= slots[0]): the device-resident obca_batch_* API runs here
-    std::vector<int> devices; std::vector<Slot> slots;
-    std::string err; std::string name; int cus;
-    PathWsBufs *pw = nullptr;               // staging of obca_parking_path_warm_start_batch (primary device), created by its first call
-    PathWsBufs *rf = nullptr;               // the same set for obca_parking_refine_batch
-    PathWsBufs *qsd = nullptr;              // and for obca_quadcopter_subdivide_batch
-    HybridBufs *hyb = nullptr;              // the planner's slots and staging (obca_hybrid_astar_batch), created by its first call or by obca_hybrid_configure
-};
-static std::string g_create_err;
 
 // Device work buffers never carry what a previous owner of the memory left in them:
 // every allocation is filled once, on the stream of the batch it belongs to (the
@@ -453,30 +444,55 @@ struct DevBuf {
         return e;
     }
 };
-// staging of the path warm-start calls (obca_path_ws.h): one device block and its pinned mirror, the events around the kernel
-struct PathWsBufs {
-    DevBuf dev; PinnedBuf host; hipEvent_t e0 = nullptr, e1 = nullptr; int have_ev = 0, timed = 0;
-    void release() { dev.release(); host.release(); if (have_ev) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); } have_ev = timed = 0; }
+// two events around a kernel, created by the first ensure(); `timed`: an interval has been recorded between them, elapsed() refuses before
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr; int have = 0, timed = 0;
+    int ensure(std::string &err) {
+        if (have) return 0;
+        if (hipEventCreate(&e0) != hipSuccess) { err = "hipEventCreate failed"; return -2; }
+        if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); err = "hipEventCreate failed"; return -2; }
+        have = 1;
+        return 0;
+    }
+    hipError_t begin(hipStream_t stream) { return hipEventRecord(e0, stream); }
+    hipError_t end(hipStream_t stream) { return hipEventRecord(e1, stream); }
+    bool elapsed(float *ms) const { return timed && hipEventElapsedTime(ms, e0, e1) == hipSuccess; }
+    void release() { if (have) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); } have = timed = 0; }
 };
-// the planner (obca_hybrid.h): the configuration, the slots' memory (kept while the next call fits it), the staging block of a call, the events around the kernel
+// staging of one kernel call (path warm start, refine, subdivide): a device block, its pinned mirror, the events around the kernel.  Allocates nothing until first used.
+struct KernelStage {
+    DevBuf dev; PinnedBuf host; EventPair ev;
+    void release() { dev.release(); host.release(); ev.release(); }
+};
+// the planner (obca_hybrid.h): the configuration, the slots' memory (kept while the next call fits it), the staging block of a call; per entry point (shared field, per-instance
+// fields) the events around the kernel and the LDS attribute its instantiation has been given
 struct HybridBufs {
     int slots = 0, max_nodes = 0, max_chunks = 0;      // as configured (0 = default)
     char *slotmem = nullptr; size_t slot_bytes = 0; int nslots = 0, ncell = 0, nodes = 0, chunks = 0;
-    char *io = nullptr; size_t io_bytes = 0; int lds_set = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr; int have_ev = 0, timed = 0;
-    hipEvent_t s0 = nullptr, s1 = nullptr; int have_sev = 0, stimed = 0, lds_sset = 0;      // the per-instance call (obca_scene_astar_batch): events and LDS attribute of its own
+    char *io = nullptr; size_t io_bytes = 0;
+    EventPair ev[2]; int lds_set[2] = {0, 0};      // [0]: obca_hybrid_astar_batch, [1]: obca_scene_astar_batch
     void release() {
         if (slotmem) (void)hipFree(slotmem);
         if (io) (void)hipFree(io);
-        if (have_ev) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
-        if (have_sev) { (void)hipEventDestroy(s0); (void)hipEventDestroy(s1); }
-        slotmem = io = nullptr; slot_bytes = io_bytes = 0; nslots = have_ev = timed = have_sev = stimed = 0;
+        ev[0].release(); ev[1].release();
+        slotmem = io = nullptr; slot_bytes = io_bytes = 0; nslots = 0;
     }
 };
 }  // namespace
 
+struct obca_ctx {
+    int device; hipStream_t stream;         // primary device / stream (= slots[0]): the device-resident obca_batch_* API runs here
+    std::vector<int> devices; std::vector<Slot> slots;
+    std::string err; std::string name; int cus;
+    KernelStage pw;                         // staging of obca_parking_path_warm_start_batch (primary device)
+    KernelStage rf;                         // the same set for obca_parking_refine_batch
+    KernelStage qsd;                        // and for obca_quadcopter_subdivide_batch
+    HybridBufs hyb;                         // the planner's slots and staging (obca_hybrid_astar_batch, obca_scene_astar_batch) and its configuration (obca_hybrid_configure)
+};
+static std::string g_create_err;
+
 // buffers of the validate calls of a batch: device input (row lengths; a host-pointer call's trajectory extras) and output, their pinned mirrors, the events around the kernel
-struct ValBufs { DevBuf d_in, d_out; PinnedBuf h_in, h_out; hipEvent_t e0 = nullptr, e1 = nullptr; int have_ev = 0, timed = 0; };
+struct ValBufs { DevBuf d_in, d_out; PinnedBuf h_in, h_out; EventPair ev; };
 // what a parking and a quadcopter batch have in common
 struct BatchCore {
     obca_ctx *ctx; int device; hipStream_t stream; std::string err;
@@ -495,7 +511,7 @@ struct obca_quad_batch : BatchCore {
     using BatchCore::BatchCore;
     QDevBufs d = {};
     PinnedBuf h_z;
-    PathWsBufs sd;       // obca_quad_batch_subdivide_into, this batch the destination: selection and status on the device, the events around the kernel
+    KernelStage sd;       // obca_quad_batch_subdivide_into, this batch the destination: selection and status on the device, the events around the kernel
 };
 struct obca_batch : BatchCore {
     using BatchCore::BatchCore;
@@ -509,8 +525,8 @@ struct obca_batch : BatchCore {
     hipEvent_t e2 = nullptr;      // e0 .. e1: DualMultWS, e1 .. e2: interior point
     int sliced = 0;      // slice length (passes) of the last solve if it used the two-launch schedule, else 0
     int val_rl = 0;      // the row lengths of the uploaded instances are in val.d_in (resident validate)
-    PathWsBufs pw;       // obca_batch_set_path_warm_start
-    PathWsBufs rf;       // obca_batch_refine_into, this batch the destination: selection and status on the device, the events around the kernel
+    KernelStage pw;       // obca_batch_set_path_warm_start
+    KernelStage rf;       // obca_batch_refine_into, this batch the destination: selection and status on the device, the events around the kernel
     std::vector<int> vmx;                                   // per instance: most rows of one of its obstacles (a refined selection takes its own row class along)
 };
 
@@ -528,17 +544,10 @@ static int core_sync(BatchCore *bt, const char *what) {
     if (hipStreamSynchronize(bt->stream) != hipSuccess) { bt->ctx->err = what; return -2; }
     return 0;
 }
-static int core_elapsed_ms(BatchCore *bt, bool recorded, hipEvent_t from, hipEvent_t to, float *ms, const char *what) {
-    if (!recorded || hipEventElapsedTime(ms, from, to) != hipSuccess) { bt->ctx->err = what; return -2; }
+// every *_ms entry point of an event pair: refuses with `what` until the pair has timed a call
+static int core_elapsed_ms(obca_ctx *ctx, const EventPair &ev, float *ms, const char *what) {
+    if (!ev.elapsed(ms)) { ctx->err = what; return -2; }
     return 0;
-}
-static int core_validate_ms(BatchCore *bt, float *ms, const char *what) {
-    if (!bt || !ms) return -1;
-    return core_elapsed_ms(bt, bt->val.timed != 0, bt->val.e0, bt->val.e1, ms, what);
-}
-static int core_clearance_ms(BatchCore *bt, float *ms, const char *what) {
-    if (!bt || !ms) return -1;
-    return core_elapsed_ms(bt, bt->clr.timed != 0, bt->clr.e0, bt->clr.e1, ms, what);
 }
 static int core_scratch_bytes(const BatchCore *bt, long long *bytes) { if (!bt || !bytes) return -1; *bytes = bt->bytes; return 0; }
 #ifdef OBCA_PROFILE      /* the per-phase clocks exist in the profiling build only (libobca_hip_prof.so, tools/phase_profile.py): not an entry point of the product */
@@ -553,8 +562,7 @@ static int core_phase_cycles(BatchCore *bt, const double *prof, double *out /* B
 static void core_release(BatchCore *bt) {
     for (ValBufs *pv : {&bt->val, &bt->clr}) {
         ValBufs &v = *pv;
-        v.d_in.release(); v.d_out.release(); v.h_in.release(); v.h_out.release();
-        if (v.have_ev) { (void)hipEventDestroy(v.e0); (void)hipEventDestroy(v.e1); }
+        v.d_in.release(); v.d_out.release(); v.h_in.release(); v.h_out.release(); v.ev.release();
     }
     bt->h_prob.release(); bt->h_info.release();
     (void)hipEventDestroy(bt->e0); (void)hipEventDestroy(bt->e1);
@@ -641,10 +649,8 @@ int obca_destroy(obca_ctx *c) {
         if (s.qb) obca_quad_batch_destroy(s.qb);
         if (s.stream) { use_device(s.device); (void)hipStreamDestroy(s.stream); }
     }
-    if (c->pw) { use_device(c->device); c->pw->release(); delete c->pw; }
-    if (c->rf) { use_device(c->device); c->rf->release(); delete c->rf; }
-    if (c->qsd) { use_device(c->device); c->qsd->release(); delete c->qsd; }
-    if (c->hyb) { use_device(c->device); c->hyb->release(); delete c->hyb; }
+    use_device(c->device);
+    c->pw.release(); c->rf.release(); c->qsd.release(); c->hyb.release();
     delete c; return 0;
 }
 const char *obca_last_error(const obca_ctx *c) { return c ? c->err.c_str() : g_create_err.c_str(); }
@@ -922,11 +928,7 @@ static int batch_download_range(obca_batch *bt, const ParkOut &o, int lo) {
 
 // ---- a-posteriori validation (obca_validate.h)
 static int val_reserve(std::string &err, ValBufs &v, size_t in_doubles, size_t out_doubles, hipStream_t stream) {
-    if (!v.have_ev) {
-        if (hipEventCreate(&v.e0) != hipSuccess) { err = "hipEventCreate failed"; return -2; }
-        if (hipEventCreate(&v.e1) != hipSuccess) { (void)hipEventDestroy(v.e0); err = "hipEventCreate failed"; return -2; }
-        v.have_ev = 1;
-    }
+    if (int rc = v.ev.ensure(err)) return rc;
     if (v.d_in.reserve(in_doubles, stream) != hipSuccess) { err = "hipMalloc(validate input) failed"; return -2; }
     if (v.d_out.reserve(out_doubles, stream) != hipSuccess) { err = "hipMalloc(validate output) failed"; return -2; }
     if (v.h_in.reserve(err, in_doubles) || v.h_out.reserve(err, out_doubles)) return -2;
@@ -944,11 +946,11 @@ static int run_validate(BatchCore *bt, ValBufs &v, size_t s_in, bool upload, siz
         for (int i = 0; i < B; i++) pack(i, v.h_in + (size_t)i * s_in);
         HIPCHK(bt, hipMemcpyAsync(v.d_in, v.h_in, (size_t)B * s_in * sizeof(double), hipMemcpyHostToDevice, bt->stream));
     }
-    HIPCHK(bt, hipEventRecord(v.e0, bt->stream));
+    HIPCHK(bt, v.ev.begin(bt->stream));
     launch();
     HIPCHK(bt, hipGetLastError());
-    HIPCHK(bt, hipEventRecord(v.e1, bt->stream));
-    v.timed = 1;
+    HIPCHK(bt, v.ev.end(bt->stream));
+    v.ev.timed = 1;
     HIPCHK(bt, hipMemcpyAsync(v.h_out, v.d_out, (size_t)B * s_out * sizeof(double), hipMemcpyDeviceToHost, bt->stream));
     HIPCHK(bt, hipStreamSynchronize(bt->stream));
     for (int i = 0; i < B; i++) unpack(i, (const double *)v.h_out + (size_t)i * s_out);
@@ -1055,22 +1057,30 @@ static int slot_batch(obca_ctx *ctx, Slot &s, BT *&cached, int (*destroy)(BT *),
     return cached ? 0 : batch_create_on(ctx, s.device, s.stream, cap, N, &cached, err);
 }
 
-static int parking_call(obca_ctx *ctx, int dist, int dualws_only, int B, int N, ParkIn &in, const obca_opts *opts, const ParkOut &out) {
-    if (!ctx) return -1;
-    if (B < 1 || N < 0 || N > OBCA_NMAX) { ctx->err = "need B>=1, 0<=N<=OBCA_NMAX"; return -1; }
-    if (!in.Ts || !in.ego || !in.XYb || !in.nOb || !in.vOb || !in.A || !in.b || !in.rx || !in.ry || !in.ryaw) { ctx->err = "NULL argument"; return -1; }
-    if (!dualws_only && N < 2) { ctx->err = "the NLP needs a horizon N>=2"; return -1; }
-    if (int rc = park_prefix(ctx->err, B, in.nOb, in.vOb, in)) return rc;
+// a parking host-pointer call over the slots: per chunk the slot's cached batch -> upload of the chunk's instances -> op(batch, lo) -> the batch's error text if one of them failed
+template <typename Op>
+static int parking_chunks(obca_ctx *ctx, int dist, int B, int N, const ParkIn &in, Op &&op /* int(obca_batch *, int lo) */) {
     const int chunk = pick_chunk(ctx, B, 4);
     return run_chunks(ctx, B, chunk, [&](Slot &s, int lo, int n, std::string &err) -> int {
         int rc = slot_batch(ctx, s, s.pb, obca_batch_destroy, std::min(chunk, B), std::min(chunk, B), N, err);
         if (rc) return rc;
         obca_batch *bt = s.pb; bt->dist = dist ? 1 : 0;
         rc = batch_upload_range(bt, in, lo, n);
-        if (!rc) rc = batch_solve(bt, opts, dualws_only);
-        if (!rc) rc = batch_download_range(bt, out, lo);
+        if (!rc) rc = op(bt, lo);
         if (rc) err = bt->err;
         return rc;
+    });
+}
+
+static int parking_call(obca_ctx *ctx, int dist, int dualws_only, int B, int N, ParkIn &in, const obca_opts *opts, const ParkOut &out) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 0 || N > OBCA_NMAX) { ctx->err = "need B>=1, 0<=N<=OBCA_NMAX"; return -1; }
+    if (!in.Ts || !in.ego || !in.XYb || !in.nOb || !in.vOb || !in.A || !in.b || !in.rx || !in.ry || !in.ryaw) { ctx->err = "NULL argument"; return -1; }
+    if (!dualws_only && N < 2) { ctx->err = "the NLP needs a horizon N>=2"; return -1; }
+    if (int rc = park_prefix(ctx->err, B, in.nOb, in.vOb, in)) return rc;
+    return parking_chunks(ctx, dist, B, N, in, [&](obca_batch *bt, int lo) -> int {
+        const int rc = batch_solve(bt, opts, dualws_only);
+        return rc ? rc : batch_download_range(bt, out, lo);
     });
 }
 
@@ -1133,8 +1143,8 @@ int obca_batch_last_schedule(const obca_batch *bt, int *ipm_launches, int *slice
 }
 int obca_batch_kernel_ms(obca_batch *bt, float *ipm_ms, float *dualws_ms) {
     if (!bt) return -1;
-    float a = 0, b = 0; const char *what = "obca_batch_kernel_ms: events not ready";
-    if (core_elapsed_ms(bt, true, bt->e0, bt->e1, &a, what) || core_elapsed_ms(bt, true, bt->e1, bt->e2, &b, what)) return -2;
+    float a = 0, b = 0;
+    if (hipEventElapsedTime(&a, bt->e0, bt->e1) != hipSuccess || hipEventElapsedTime(&b, bt->e1, bt->e2) != hipSuccess) { bt->ctx->err = "obca_batch_kernel_ms: events not ready"; return -2; }
     if (dualws_ms) *dualws_ms = a; if (ipm_ms) *ipm_ms = b;
     return 0;
 }
@@ -1152,7 +1162,7 @@ int obca_batch_validate(obca_batch *bt, double tol, int *ok, int *ref_ok, double
     if (bt->N < 1) { bt->ctx->err = "obca_batch_validate: needs a horizon N>=1"; return -1; }
     return fin(bt, batch_validate_range(bt, nullptr, nullptr, tol > 0 ? tol : PV_REF_TOL, 0, ok, ref_ok, viol));
 }
-int obca_batch_validate_ms(obca_batch *bt, float *ms) { return core_validate_ms(bt, ms, "obca_batch_validate_ms: no validate call has run on this batch"); }
+int obca_batch_validate_ms(obca_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->val.ev, ms, "obca_batch_validate_ms: no validate call has run on this batch") : -1; }
 int obca_parking_constraints_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const double XYb[4], int fixTime,
                                    const double *x0, const double *xF, const int *nOb, const int *vOb, const double *A, const double *b, int dist,
                                    const double *x, const double *u, const double *timeScale, const double *l, const double *n, const double *sl,
@@ -1164,16 +1174,7 @@ int obca_parking_constraints_batch(obca_ctx *ctx, int B, int N, const double *Ts
     ParkIn in = {Ts, L, ego, XYb, fixTime, x0, xF, nOb, vOb, A, b, zero.data(), zero.data(), zero.data(), x, u, l, n, {}, {}};
     if (int rc = park_prefix(ctx->err, B, nOb, vOb, in)) return rc;
     const double tl = tol > 0 ? tol : PV_REF_TOL;
-    const int chunk = pick_chunk(ctx, B, 4);
-    return run_chunks(ctx, B, chunk, [&](Slot &s, int lo, int cnt, std::string &err) -> int {
-        int rc = slot_batch(ctx, s, s.pb, obca_batch_destroy, std::min(chunk, B), std::min(chunk, B), N, err);
-        if (rc) return rc;
-        obca_batch *bt = s.pb; bt->dist = dist ? 1 : 0;
-        rc = batch_upload_range(bt, in, lo, cnt);
-        if (!rc) rc = batch_validate_range(bt, timeScale, sl, tl, lo, ok, ref_ok, viol);
-        if (rc) err = bt->err;
-        return rc;
-    });
+    return parking_chunks(ctx, dist, B, N, in, [&](obca_batch *bt, int lo) { return batch_validate_range(bt, timeScale, sl, tl, lo, ok, ref_ok, viol); });
 }
 
 int obca_batch_clearance(obca_batch *bt, int substeps, double need, double *out) {
@@ -1184,7 +1185,7 @@ int obca_batch_clearance(obca_batch *bt, int substeps, double need, double *out)
     if (bt->N < 1) { bt->ctx->err = "obca_batch_clearance: needs a horizon N>=1"; return -1; }
     return fin(bt, batch_clearance_range(bt, false, nullptr, substeps, need, 0, out));
 }
-int obca_batch_clearance_ms(obca_batch *bt, float *ms) { return core_clearance_ms(bt, ms, "obca_batch_clearance_ms: no clearance call has run on this batch"); }
+int obca_batch_clearance_ms(obca_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->clr.ev, ms, "obca_batch_clearance_ms: no clearance call has run on this batch") : -1; }
 int obca_parking_clearance_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const int *nOb, const int *vOb, const double *A, const double *b,
                                  const double *x, const double *u, const double *timeScale, int substeps, double need, double *out) {
     if (!ctx) return -1;
@@ -1195,16 +1196,7 @@ int obca_parking_clearance_batch(obca_ctx *ctx, int B, int N, const double *Ts, 
     const double XYb[4] = {0, 0, 0, 0};
     ParkIn in = {Ts, L, ego, XYb, 0, nullptr, nullptr, nOb, vOb, A, b, zero.data(), zero.data(), zero.data(), x, u, nullptr, nullptr, {}, {}};
     if (int rc = park_prefix(ctx->err, B, nOb, vOb, in)) return rc;
-    const int chunk = pick_chunk(ctx, B, 4);
-    return run_chunks(ctx, B, chunk, [&](Slot &s, int lo, int cnt, std::string &err) -> int {
-        int rc = slot_batch(ctx, s, s.pb, obca_batch_destroy, std::min(chunk, B), std::min(chunk, B), N, err);
-        if (rc) return rc;
-        obca_batch *bt = s.pb; bt->dist = 0;
-        rc = batch_upload_range(bt, in, lo, cnt);
-        if (!rc) rc = batch_clearance_range(bt, true, timeScale, substeps, need, lo, out);
-        if (rc) err = bt->err;
-        return rc;
-    });
+    return parking_chunks(ctx, 0, B, N, in, [&](obca_batch *bt, int lo) { return batch_clearance_range(bt, true, timeScale, substeps, need, lo, out); });
 }
 
 int obca_parking_signed_dist_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const double XYb[4],
@@ -1243,21 +1235,31 @@ int obca_dualmult_ws_batch(obca_ctx *ctx, int B, int N, const double ego[4], con
 
 }  // extern "C"
 
+// ---- one kernel between the events of `ev`, then the copies of `down` to the host, then the stream is synchronised: the launch of every call that stages through a KernelStage
+// and of the planner.  `ok`: what the caller queued before (its upload) went through -- nothing is launched behind a failed copy; `entry` names the entry point in the error.
+struct Down { void *dst; const void *src; size_t bytes; };
+template <typename Launch>
+static int launch_timed(std::string &err, const char *entry, hipStream_t stream, EventPair &ev, bool ok, Launch &&launch, std::initializer_list<Down> down) {
+    ok = ok && ev.begin(stream) == hipSuccess;
+    if (ok) launch();
+    ok = ok && hipGetLastError() == hipSuccess && ev.end(stream) == hipSuccess;
+    for (const Down &c : down) ok = ok && hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, stream) == hipSuccess;
+    if (hipStreamSynchronize(stream) != hipSuccess || !ok) { err = std::string(entry) + ": kernel or copy failed"; return -2; }
+    ev.timed = 1;
+    return 0;
+}
+
 // ---- warm starts from planner paths (obca_path_ws.h, include/obca_path_ws.h)
 // What both calls send up, packed on the host into the pinned mirror so that ONE contiguous transfer carries it and only the rows below the longest usable count of the
 // call cross the bus: doubles [ paths B x rows x 3 | xF 4 x B (host-pointer call) ], then ints [ dirs B x rows | counts B ]; behind them, device only, [ status B ] and
 // `out_doubles` of output.  Device pointers in `d`.
 struct PathWsDev { const double *paths, *xF; const int *dirs, *counts; int *status; double *out; int rows; };
-static int path_ws_stage(std::string &err, PathWsBufs &w, hipStream_t stream, int B, const double *paths, const int *dirs, const int *counts, int cap, const double *xF,
+static int path_ws_stage(std::string &err, KernelStage &w, hipStream_t stream, int B, const double *paths, const int *dirs, const int *counts, int cap, const double *xF,
                          size_t out_doubles, PathWsDev &d) {
     int rows = 0;
     for (int i = 0; i < B; i++) if (!pw::path_ws_count_status(counts[i], cap)) rows = std::max(rows, counts[i]);
     const size_t np = (size_t)B * rows * 3, nd = np + (xF ? (size_t)B * 4 : 0), ni = (size_t)B * rows + B, up = nd + (ni + 1) / 2, st = (ni + B + 1) / 2;
-    if (!w.have_ev) {
-        if (hipEventCreate(&w.e0) != hipSuccess) { err = "hipEventCreate failed"; return -2; }
-        if (hipEventCreate(&w.e1) != hipSuccess) { (void)hipEventDestroy(w.e0); err = "hipEventCreate failed"; return -2; }
-        w.have_ev = 1;
-    }
+    if (int rc = w.ev.ensure(err)) return rc;
     if (w.dev.reserve(nd + st + out_doubles, stream) != hipSuccess) { err = "hipMalloc(path warm start) failed"; return -2; }
     if (w.host.reserve(err, up)) return -2;
     double *h = w.host; int *hi = (int *)(h + nd);
@@ -1285,22 +1287,13 @@ int obca_parking_path_warm_start_batch(obca_ctx *ctx, int B, int N, const double
         ctx->err = std::string("obca_parking_path_warm_start_batch: ") + bad; return -1;
     }
     use_device(ctx->device);
-    if (!ctx->pw) ctx->pw = new PathWsBufs();
-    PathWsBufs &w = *ctx->pw;
     const size_t nx = (size_t)B * 4 * (N + 1), nu = (size_t)B * 2 * N;
     PathWsDev d;
-    if (int rc = path_ws_stage(ctx->err, w, ctx->stream, B, paths, dirs, counts, cap, xF, (size_t)B + nx + nu, d)) return rc;
+    if (int rc = path_ws_stage(ctx->err, ctx->pw, ctx->stream, B, paths, dirs, counts, cap, xF, (size_t)B + nx + nu, d)) return rc;
     double *dTs = d.out, *dx = d.out + B, *du = d.out + B + nx;
-    bool ok = hipEventRecord(w.e0, ctx->stream) == hipSuccess;
-    hipLaunchKernelGGL(obca_path_ws_host_kernel, dim3(B), dim3(OB_NT), 0, ctx->stream, B, N, d.paths, d.dirs, d.counts, d.rows, cap, d.xF, v_nom, L, a_max, dTs, dx, du, d.status);
-    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(w.e1, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(Ts, dTs, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(xWS, dx, nx * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(uWS, du, nu * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(status, d.status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess || !ok) { ctx->err = "obca_parking_path_warm_start_batch: kernel or copy failed"; return -2; }
-    w.timed = 1;
-    return 0;
+    return launch_timed(ctx->err, "obca_parking_path_warm_start_batch", ctx->stream, ctx->pw.ev, true, [&] {
+        hipLaunchKernelGGL(obca_path_ws_host_kernel, dim3(B), dim3(OB_NT), 0, ctx->stream, B, N, d.paths, d.dirs, d.counts, d.rows, cap, d.xF, v_nom, L, a_max, dTs, dx, du, d.status);
+    }, {{Ts, dTs, (size_t)B * sizeof(double)}, {xWS, dx, nx * sizeof(double)}, {uWS, du, nu * sizeof(double)}, {status, d.status, (size_t)B * sizeof(int)}});
 }
 
 int obca_batch_set_path_warm_start(obca_batch *bt, const double *paths, const int *dirs, const int *counts, int cap, int use_xF, double v_nom, double a_max, int *status) {
@@ -1311,87 +1304,82 @@ int obca_batch_set_path_warm_start(obca_batch *bt, const double *paths, const in
         ctx->err = std::string("obca_batch_set_path_warm_start: ") + bad; return -1;
     }
     use_device(bt->device);
-    PathWsBufs &w = bt->pw;
     PathWsDev d;
-    if (int rc = path_ws_stage(bt->err, w, bt->stream, bt->B, paths, dirs, counts, cap, nullptr, 0, d)) return fin(bt, rc);
+    if (int rc = path_ws_stage(bt->err, bt->pw, bt->stream, bt->B, paths, dirs, counts, cap, nullptr, 0, d)) return fin(bt, rc);
     // from here on the record and the start iterate may be rewritten, whatever becomes of the call: d.z no longer answers the problem, and the start's multipliers
     // count as cleared -- the next solve runs DualMultWS
     bt->solved = 0; bt->have_duals = 0;
-    bool ok = hipEventRecord(w.e0, bt->stream) == hipSuccess;
-    hipLaunchKernelGGL(obca_path_ws_batch_kernel, dim3(bt->B), dim3(OB_NT), 0, bt->stream, bt->B, bt->N, d.paths, d.dirs, d.counts, d.rows, cap, use_xF ? 1 : 0, v_nom, a_max, bt->d, d.status);
-    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(w.e1, bt->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(status, d.status, (size_t)bt->B * sizeof(int), hipMemcpyDeviceToHost, bt->stream) == hipSuccess;
-    if (hipStreamSynchronize(bt->stream) != hipSuccess || !ok) { ctx->err = "obca_batch_set_path_warm_start: kernel or copy failed"; return -2; }
-    w.timed = 1;
-    return 0;
+    return launch_timed(ctx->err, "obca_batch_set_path_warm_start", bt->stream, bt->pw.ev, true, [&] {
+        hipLaunchKernelGGL(obca_path_ws_batch_kernel, dim3(bt->B), dim3(OB_NT), 0, bt->stream, bt->B, bt->N, d.paths, d.dirs, d.counts, d.rows, cap, use_xF ? 1 : 0, v_nom, a_max, bt->d, d.status);
+    }, {{status, d.status, (size_t)bt->B * sizeof(int)}});
 }
 
 int obca_batch_path_ws_ms(obca_batch *bt, float *ms) {
-    if (!bt || !ms) return -1;
-    return core_elapsed_ms(bt, bt->pw.timed != 0, bt->pw.e0, bt->pw.e1, ms, "obca_batch_path_ws_ms: no path warm start has run on this batch");
+    return bt && ms ? core_elapsed_ms(bt->ctx, bt->pw.ev, ms, "obca_batch_path_ws_ms: no path warm start has run on this batch") : -1;
 }
 
 }  // extern "C"
 
 // ---- solved batches on a finer horizon (obca_refine.h, include/obca_refine.h)
-static int refine_events(std::string &err, PathWsBufs &w) {
-    if (w.have_ev) return 0;
-    if (hipEventCreate(&w.e0) != hipSuccess) { err = "hipEventCreate failed"; return -2; }
-    if (hipEventCreate(&w.e1) != hipSuccess) { (void)hipEventDestroy(w.e0); err = "hipEventCreate failed"; return -2; }
-    w.have_ev = 1;
-    return 0;
+// What obca_batch_refine_into and obca_quad_batch_subdivide_into share: a selection of a solved batch, rewritten by a kernel into a second batch of the context.  Checks the two
+// batches and the selection (`unsolved`: the family's text for a source without a solution, `bad_args`: what the family's check of (n, N, factor, ...) said), runs prepare()
+// -- the host side of the destination --, stages the selection in `w` (dst->rf or dst->sd) as ints [ sel cap | status cap ], runs launch(sel, status) on the destination's
+// stream and brings the status words back.  The destination counts as not uploaded until the kernel has written every record.
+template <typename BT, typename Prepare, typename Launch>
+static int into_call(const char *entry, BT *dst, BT *src, KernelStage &w, int factor, const char *unsolved, const char *bad_args, const int *sel, int n, int *status,
+                     Prepare &&prepare /* int() */, Launch &&launch /* (const int *sel, int *status): device pointers */) {
+    obca_ctx *ctx = dst->ctx;
+    const char *bad = nullptr;
+    if (!status) bad = "NULL argument";
+    else if (dst == src || dst->ctx != src->ctx || dst->stream != src->stream) bad = "source and destination must be two batches of one context";
+    else if (!src->uploaded || !src->solved) bad = unsolved;
+    else if (bad_args) bad = bad_args;
+    else if (dst->N != factor * src->N) bad = "the destination's horizon must be factor * the source's";
+    else if (n > dst->cap) bad = "more instances than the destination was created for";
+    for (int j = 0; !bad && sel && j < n; j++) if (sel[j] < 0 || sel[j] >= src->B) bad = "an index outside 0 .. B - 1 of the source";
+    if (!bad && !sel && n > src->B) bad = "an index outside 0 .. B - 1 of the source";
+    if (bad) { ctx->err = std::string(entry) + ": " + bad; return -1; }
+    use_device(dst->device);
+    if (int rc = prepare()) return fin(dst, rc);
+    if (int rc = w.ev.ensure(dst->err)) return fin(dst, rc);
+    if (w.dev.reserve((size_t)dst->cap + 1, dst->stream) != hipSuccess) { ctx->err = std::string(entry) + ": hipMalloc failed"; return -2; }
+    if (w.host.reserve(dst->err, ((size_t)dst->cap + 1) / 2 + 1)) return fin(dst, -2);
+    int *hs = (int *)w.host.p, *dsel = (int *)w.dev.p, *dst_st = dsel + dst->cap;
+    dst->uploaded = 0;      // until the kernel has written every record (and, for a parking batch, every row)
+    for (int j = 0; j < n; j++) hs[j] = sel ? sel[j] : j;
+    const bool up = hipMemcpyAsync(dsel, hs, (size_t)n * sizeof(int), hipMemcpyHostToDevice, dst->stream) == hipSuccess;
+    const int rc = launch_timed(ctx->err, entry, dst->stream, w.ev, up, [&] { launch((const int *)dsel, dst_st); }, {{status, dst_st, (size_t)n * sizeof(int)}});
+    if (!rc) dst->uploaded = 1;
+    return rc;
 }
 
 extern "C" {
 
 int obca_batch_refine_into(obca_batch *dst, obca_batch *src, int factor, int duals, const int *sel, int n, int *status) {
     if (!dst || !src) return -1;
-    obca_ctx *ctx = dst->ctx;
-    const char *bad = nullptr;
-    if (!status) bad = "NULL argument";
-    else if (dst == src || dst->ctx != src->ctx || dst->stream != src->stream) bad = "source and destination must be two batches of one context";
-    else if (!src->uploaded || !src->solved) bad = "nothing has been solved on the source since its last upload, shift or path warm start";
-    else if ((bad = rfn::refine_check_args(n, src->N, factor, duals)) != nullptr) {}
-    else if (dst->N != factor * src->N) bad = "the destination's horizon must be factor * the source's";
-    else if (n > dst->cap) bad = "more instances than the destination was created for";
-    for (int j = 0; !bad && sel && j < n; j++) if (sel[j] < 0 || sel[j] >= src->B) bad = "an index outside 0 .. B - 1 of the source";
-    if (!bad && !sel && n > src->B) bad = "an index outside 0 .. B - 1 of the source";
-    if (bad) { ctx->err = std::string("obca_batch_refine_into: ") + bad; return -1; }
-    // the host records of the selection, in its order: the packed outputs of a later download follow the running sums, lambda goes back through the source's row lengths
-    dst->B = n; dst->solved = 0; dst->val_rl = 0;
-    dst->nOb.assign(n, 0); dst->M.assign(n, 0); dst->obOff.assign(n + 1, 0); dst->rowOff.assign(n + 1, 0); dst->vmx.assign(n, 0); dst->rowLen.clear();
-    int nObMax = 0, MMax = 0; dst->vmax = 0;
-    for (int j = 0; j < n; j++) {
-        const int i = sel ? sel[j] : j;
-        dst->nOb[j] = src->nOb[i]; dst->M[j] = src->M[i]; dst->vmx[j] = src->vmx[i];
-        dst->obOff[j + 1] = dst->obOff[j] + dst->nOb[j]; dst->rowOff[j + 1] = dst->rowOff[j] + dst->M[j];
-        const double *rl = src->rowLen.data() + (src->rowOff[i] - src->rowOff[0]);
-        dst->rowLen.insert(dst->rowLen.end(), rl, rl + src->M[i]);
-        nObMax = std::max(nObMax, dst->nOb[j]); MMax = std::max(MMax, dst->M[j]); dst->vmax = std::max(dst->vmax, dst->vmx[j]);
-    }
-    dst->dist = src->dist; dst->fixTime = src->fixTime; dst->have_duals = duals;
-    use_device(dst->device);
-    if (int rc = batch_reserve_shape(dst, nObMax, MMax)) return fin(dst, rc);
-    PathWsBufs &w = dst->rf;
-    if (int rc = refine_events(dst->err, w)) return fin(dst, rc);
-    if (w.dev.reserve((size_t)dst->cap + 1, dst->stream) != hipSuccess) { ctx->err = "obca_batch_refine_into: hipMalloc failed"; return -2; }      // ints: [ sel cap | status cap ]
-    if (w.host.reserve(dst->err, ((size_t)dst->cap + 1) / 2 + 1)) return fin(dst, -2);
-    int *hs = (int *)w.host.p, *dsel = (int *)w.dev.p, *dst_st = dsel + dst->cap;
-    dst->uploaded = 0;      // until the kernel has written every record and every row
-    for (int j = 0; j < n; j++) hs[j] = sel ? sel[j] : j;
-    bool ok = hipMemcpyAsync(dsel, hs, (size_t)n * sizeof(int), hipMemcpyHostToDevice, dst->stream) == hipSuccess;
-    ok = ok && hipEventRecord(w.e0, dst->stream) == hipSuccess;
-    hipLaunchKernelGGL(obca_refine_batch_kernel, dim3(n), dim3(OB_NT), 0, dst->stream, n, src->N, factor, duals, (const int *)dsel, src->d, dst->d, dst_st);
-    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(w.e1, dst->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(status, dst_st, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, dst->stream) == hipSuccess;
-    if (hipStreamSynchronize(dst->stream) != hipSuccess || !ok) { ctx->err = "obca_batch_refine_into: kernel or copy failed"; return -2; }
-    w.timed = 1; dst->uploaded = 1;
-    return 0;
+    return into_call("obca_batch_refine_into", dst, src, dst->rf, factor, "nothing has been solved on the source since its last upload, shift or path warm start",
+                     rfn::refine_check_args(n, src->N, factor, duals), sel, n, status, [&] {
+        // the host records of the selection, in its order: the packed outputs of a later download follow the running sums, lambda goes back through the source's row lengths
+        dst->B = n; dst->solved = 0; dst->val_rl = 0;
+        dst->nOb.assign(n, 0); dst->M.assign(n, 0); dst->obOff.assign(n + 1, 0); dst->rowOff.assign(n + 1, 0); dst->vmx.assign(n, 0); dst->rowLen.clear();
+        int nObMax = 0, MMax = 0; dst->vmax = 0;
+        for (int j = 0; j < n; j++) {
+            const int i = sel ? sel[j] : j;
+            dst->nOb[j] = src->nOb[i]; dst->M[j] = src->M[i]; dst->vmx[j] = src->vmx[i];
+            dst->obOff[j + 1] = dst->obOff[j] + dst->nOb[j]; dst->rowOff[j + 1] = dst->rowOff[j] + dst->M[j];
+            const double *rl = src->rowLen.data() + (src->rowOff[i] - src->rowOff[0]);
+            dst->rowLen.insert(dst->rowLen.end(), rl, rl + src->M[i]);
+            nObMax = std::max(nObMax, dst->nOb[j]); MMax = std::max(MMax, dst->M[j]); dst->vmax = std::max(dst->vmax, dst->vmx[j]);
+        }
+        dst->dist = src->dist; dst->fixTime = src->fixTime; dst->have_duals = duals;
+        return batch_reserve_shape(dst, nObMax, MMax);
+    }, [&](const int *dsel, int *dstatus) {
+        hipLaunchKernelGGL(obca_refine_batch_kernel, dim3(n), dim3(OB_NT), 0, dst->stream, n, src->N, factor, duals, dsel, src->d, dst->d, dstatus);
+    });
 }
 
 int obca_batch_refine_ms(obca_batch *dst, float *ms) {
-    if (!dst || !ms) return -1;
-    return core_elapsed_ms(dst, dst->rf.timed != 0, dst->rf.e0, dst->rf.e1, ms, "obca_batch_refine_ms: no refine call has written into this batch");
+    return dst && ms ? core_elapsed_ms(dst->ctx, dst->rf.ev, ms, "obca_batch_refine_ms: no refine call has written into this batch") : -1;
 }
 
 int obca_parking_refine_batch(obca_ctx *ctx, int B, int N, int factor, const double *Ts, double L, const double *x, const double *u, const double *timeScale,
@@ -1401,9 +1389,8 @@ int obca_parking_refine_batch(obca_ctx *ctx, int B, int N, int factor, const dou
     if (!bad && !(Ts && x && u && Ts_f && x_f && u_f)) bad = "NULL argument";
     if (bad) { ctx->err = std::string("obca_parking_refine_batch: ") + bad; return -1; }
     use_device(ctx->device);
-    if (!ctx->rf) ctx->rf = new PathWsBufs();
-    PathWsBufs &w = *ctx->rf;
-    if (int rc = refine_events(ctx->err, w)) return rc;
+    KernelStage &w = ctx->rf;
+    if (int rc = w.ev.ensure(ctx->err)) return rc;
     const size_t Nf = (size_t)N * factor, nx = (size_t)B * 4 * (N + 1), nu = (size_t)B * 2 * N, nt = timeScale ? (size_t)B * (N + 1) : 0, nin = B + nx + nu + nt;
     const size_t nxf = (size_t)B * 4 * (Nf + 1), nuf = (size_t)B * 2 * Nf;
     if (w.dev.reserve(nin + B + nxf + nuf, ctx->stream) != hipSuccess) { ctx->err = "obca_parking_refine_batch: hipMalloc failed"; return -2; }
@@ -1412,17 +1399,11 @@ int obca_parking_refine_batch(obca_ctx *ctx, int B, int N, int factor, const dou
     memcpy(h, Ts, sizeof(double) * B); memcpy(h + B, x, sizeof(double) * nx); memcpy(h + B + nx, u, sizeof(double) * nu);
     if (nt) memcpy(h + B + nx + nu, timeScale, sizeof(double) * nt);
     double *dTsf = d + nin, *dxf = dTsf + B, *duf = dxf + nxf;
-    bool ok = hipMemcpyAsync(d, h, nin * sizeof(double), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-    ok = ok && hipEventRecord(w.e0, ctx->stream) == hipSuccess;
-    hipLaunchKernelGGL(obca_refine_host_kernel, dim3(B), dim3(OB_NT), 0, ctx->stream, B, N, factor, (const double *)d, L, (const double *)(d + B), (const double *)(d + B + nx),
-                       (const double *)(nt ? d + B + nx + nu : nullptr), dTsf, dxf, duf);
-    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(w.e1, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(Ts_f, dTsf, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(x_f, dxf, nxf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(u_f, duf, nuf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess || !ok) { ctx->err = "obca_parking_refine_batch: kernel or copy failed"; return -2; }
-    w.timed = 1;
-    return 0;
+    const bool up = hipMemcpyAsync(d, h, nin * sizeof(double), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    return launch_timed(ctx->err, "obca_parking_refine_batch", ctx->stream, w.ev, up, [&] {
+        hipLaunchKernelGGL(obca_refine_host_kernel, dim3(B), dim3(OB_NT), 0, ctx->stream, B, N, factor, (const double *)d, L, (const double *)(d + B), (const double *)(d + B + nx),
+                           (const double *)(nt ? d + B + nx + nu : nullptr), dTsf, dxf, duf);
+    }, {{Ts_f, dTsf, (size_t)B * sizeof(double)}, {x_f, dxf, nxf * sizeof(double)}, {u_f, duf, nuf * sizeof(double)}});
 }
 
 }  // extern "C"
@@ -1586,20 +1567,27 @@ static int quad_clearance_range(obca_quad_batch *bt, const double *ts, int S, do
 }
 // instances (one wavefront each) resident per CU, as OBCA_RESIDENT_PER_CU for the parking kernel: what pick_chunk sizes a quadcopter chunk by
 static const int QUAD_RESIDENT_PER_CU = (QNT == 64 ? 4 : 2) * OBCA_QUAD_WAVES_PER_EU;
-static int quadcopter_call(obca_ctx *ctx, int B, int N, const QuadIn &in, const obca_opts *opts, const QuadOut &out) {
-    if (!ctx) return -1;
-    if (B < 1 || N < 2 || N > OBCA_QUAD_NMAX) { ctx->err = "need B>=1, 2<=N<=OBCA_QUAD_NMAX"; return -1; }
-    if (!in.Ts || !in.x0 || !in.xF || !in.ob || !in.xWS || !in.timeWS) { ctx->err = "NULL argument"; return -1; }
+// parking_chunks for the quadcopter; the slot's cached batch only has to hold the chunk at hand
+template <typename Op>
+static int quad_chunks(obca_ctx *ctx, int B, int N, const QuadIn &in, Op &&op /* int(obca_quad_batch *, int lo) */) {
     const int chunk = pick_chunk(ctx, B, QUAD_RESIDENT_PER_CU);
     return run_chunks(ctx, B, chunk, [&](Slot &s, int lo, int n, std::string &err) -> int {
         int rc = slot_batch(ctx, s, s.qb, obca_quad_batch_destroy, n, std::min(chunk, B), N, err);
         if (rc) return rc;
         obca_quad_batch *bt = s.qb;
         rc = quad_upload_range(bt, in, lo, n);
-        if (!rc) rc = quad_solve(bt, opts);
-        if (!rc) rc = quad_download_range(bt, out, lo);
+        if (!rc) rc = op(bt, lo);
         if (rc) err = bt->err;
         return rc;
+    });
+}
+static int quadcopter_call(obca_ctx *ctx, int B, int N, const QuadIn &in, const obca_opts *opts, const QuadOut &out) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 2 || N > OBCA_QUAD_NMAX) { ctx->err = "need B>=1, 2<=N<=OBCA_QUAD_NMAX"; return -1; }
+    if (!in.Ts || !in.x0 || !in.xF || !in.ob || !in.xWS || !in.timeWS) { ctx->err = "NULL argument"; return -1; }
+    return quad_chunks(ctx, B, N, in, [&](obca_quad_batch *bt, int lo) -> int {
+        const int rc = quad_solve(bt, opts);
+        return rc ? rc : quad_download_range(bt, out, lo);
     });
 }
 extern "C" {
@@ -1631,7 +1619,8 @@ int obca_quad_batch_shift_warm_start(obca_quad_batch *bt, int shift, const doubl
 int obca_quad_batch_sync(obca_quad_batch *bt) { return core_sync(bt, "obca_quad_batch_sync: hipStreamSynchronize failed"); }
 int obca_quad_batch_kernel_ms(obca_quad_batch *bt, float *ipm_ms) {
     if (!bt || !ipm_ms) return -1;
-    return core_elapsed_ms(bt, true, bt->e0, bt->e1, ipm_ms, "obca_quad_batch_kernel_ms: events not ready");
+    if (hipEventElapsedTime(ipm_ms, bt->e0, bt->e1) != hipSuccess) { bt->ctx->err = "obca_quad_batch_kernel_ms: events not ready"; return -2; }
+    return 0;
 }
 int obca_quad_batch_validate(obca_quad_batch *bt, double tol, int *ok, double *viol) {
     if (!bt) return -1;
@@ -1639,7 +1628,7 @@ int obca_quad_batch_validate(obca_quad_batch *bt, double tol, int *ok, double *v
     if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_quad_batch_validate: nothing has been solved since the last upload"; return -1; }
     return fin(bt, quad_validate_range(bt, nullptr, nullptr, nullptr, nullptr, tol > 0 ? tol : 1e-3, 0, ok, viol));
 }
-int obca_quad_batch_validate_ms(obca_quad_batch *bt, float *ms) { return core_validate_ms(bt, ms, "obca_quad_batch_validate_ms: no validate call has run on this batch"); }
+int obca_quad_batch_validate_ms(obca_quad_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->val.ev, ms, "obca_quad_batch_validate_ms: no validate call has run on this batch") : -1; }
 int obca_quadcopter_constr_satisfaction_batch(obca_ctx *ctx, int B, int N, const double *Ts, double R, const double *x0, const double *xF, const double *ob,
                                               const double *x, const double *u, const double *timeScale, const double *lambda, double tol, int *ok, double *viol) {
     if (!ctx) return -1;
@@ -1648,16 +1637,7 @@ int obca_quadcopter_constr_satisfaction_batch(obca_ctx *ctx, int B, int N, const
     const std::vector<double> one((size_t)B, 1.0);                 // timeWS of a solve: no check reads it
     const QuadIn in = {Ts, R, x0, xF, ob, x, one.data(), 0, 0};
     const double tl = tol > 0 ? tol : 1e-3;
-    const int chunk = pick_chunk(ctx, B, QUAD_RESIDENT_PER_CU);
-    return run_chunks(ctx, B, chunk, [&](Slot &s, int lo, int cnt, std::string &err) -> int {
-        int rc = slot_batch(ctx, s, s.qb, obca_quad_batch_destroy, cnt, std::min(chunk, B), N, err);
-        if (rc) return rc;
-        obca_quad_batch *bt = s.qb;
-        rc = quad_upload_range(bt, in, lo, cnt);
-        if (!rc) rc = quad_validate_range(bt, x, u, timeScale, lambda, tl, lo, ok, viol);
-        if (rc) err = bt->err;
-        return rc;
-    });
+    return quad_chunks(ctx, B, N, in, [&](obca_quad_batch *bt, int lo) { return quad_validate_range(bt, x, u, timeScale, lambda, tl, lo, ok, viol); });
 }
 int obca_quad_batch_clearance(obca_quad_batch *bt, int substeps, double need, double *out) {
     if (!bt) return -1;
@@ -1666,7 +1646,7 @@ int obca_quad_batch_clearance(obca_quad_batch *bt, int substeps, double need, do
     if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_quad_batch_clearance: nothing has been solved since the last upload or shift"; return -1; }
     return fin(bt, quad_clearance_range(bt, nullptr, substeps, need, 0, out));
 }
-int obca_quad_batch_clearance_ms(obca_quad_batch *bt, float *ms) { return core_clearance_ms(bt, ms, "obca_quad_batch_clearance_ms: no clearance call has run on this batch"); }
+int obca_quad_batch_clearance_ms(obca_quad_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->clr.ev, ms, "obca_quad_batch_clearance_ms: no clearance call has run on this batch") : -1; }
 int obca_quadcopter_clearance_batch(obca_ctx *ctx, int B, int N, const double *Ts, double R, const double *ob, const double *x, const double *timeScale, int substeps, double need, double *out) {
     if (!ctx) return -1;
     if (B < 1 || N < 2 || N > OBCA_QUAD_NMAX) { ctx->err = "obca_quadcopter_clearance_batch: need B>=1, 2<=N<=OBCA_QUAD_NMAX"; return -1; }
@@ -1674,16 +1654,7 @@ int obca_quadcopter_clearance_batch(obca_ctx *ctx, int B, int N, const double *T
     if (const char *bad = clr::clearance_check_args(substeps, need)) { ctx->err = std::string("obca_quadcopter_clearance_batch: ") + bad; return -1; }
     const std::vector<double> zero((size_t)B * QX, 0.0), one((size_t)B, 1.0);      // start, goal and timeWS of a solve: the check reads none of them
     const QuadIn in = {Ts, R, zero.data(), zero.data(), ob, x, one.data(), 0, 0};
-    const int chunk = pick_chunk(ctx, B, QUAD_RESIDENT_PER_CU);
-    return run_chunks(ctx, B, chunk, [&](Slot &s, int lo, int cnt, std::string &err) -> int {
-        int rc = slot_batch(ctx, s, s.qb, obca_quad_batch_destroy, cnt, std::min(chunk, B), N, err);
-        if (rc) return rc;
-        obca_quad_batch *bt = s.qb;
-        rc = quad_upload_range(bt, in, lo, cnt);
-        if (!rc) rc = quad_clearance_range(bt, timeScale, substeps, need, lo, out);
-        if (rc) err = bt->err;
-        return rc;
-    });
+    return quad_chunks(ctx, B, N, in, [&](obca_quad_batch *bt, int lo) { return quad_clearance_range(bt, timeScale, substeps, need, lo, out); });
 }
 int obca_quad_batch_download(obca_quad_batch *bt, double *xp, double *up, double *ts, int *exitflag, double *lp, double *slp, double *info) {
     if (!bt) return -1;
@@ -1711,39 +1682,15 @@ int obca_quadcopter_dist_batch(obca_ctx *ctx, int B, int N, const double *Ts, do
 /* ---- solved quadcopter batches on a finer horizon (obca_quad_subdivide.h, include/obca_quad_subdivide.h) */
 int obca_quad_batch_subdivide_into(obca_quad_batch *dst, obca_quad_batch *src, int factor, double margin, const int *sel, int n, int *status) {
     if (!dst || !src) return -1;
-    obca_ctx *ctx = dst->ctx;
-    const char *bad = nullptr;
-    if (!status) bad = "NULL argument";
-    else if (dst == src || dst->ctx != src->ctx || dst->stream != src->stream) bad = "source and destination must be two batches of one context";
-    else if (!src->uploaded || !src->solved) bad = "nothing has been solved on the source since its last upload or shift";
-    else if ((bad = qsd::subdivide_check_args(n, src->N, factor, margin)) != nullptr) {}
-    else if (dst->N != factor * src->N) bad = "the destination's horizon must be factor * the source's";
-    else if (n > dst->cap) bad = "more instances than the destination was created for";
-    for (int j = 0; !bad && sel && j < n; j++) if (sel[j] < 0 || sel[j] >= src->B) bad = "an index outside 0 .. B - 1 of the source";
-    if (!bad && !sel && n > src->B) bad = "an index outside 0 .. B - 1 of the source";
-    if (bad) { ctx->err = std::string("obca_quad_batch_subdivide_into: ") + bad; return -1; }
-    use_device(dst->device);
-    PathWsBufs &w = dst->sd;
-    if (int rc = refine_events(dst->err, w)) return fin(dst, rc);
-    if (w.dev.reserve((size_t)dst->cap + 1, dst->stream) != hipSuccess) { ctx->err = "obca_quad_batch_subdivide_into: hipMalloc failed"; return -2; }      // ints: [ sel cap | status cap ]
-    if (w.host.reserve(dst->err, ((size_t)dst->cap + 1) / 2 + 1)) return fin(dst, -2);
-    int *hs = (int *)w.host.p, *dsel = (int *)w.dev.p, *dst_st = dsel + dst->cap;
-    dst->B = n; dst->solved = 0;
-    dst->uploaded = 0;      // until the kernel has written every record
-    for (int j = 0; j < n; j++) hs[j] = sel ? sel[j] : j;
-    bool ok = hipMemcpyAsync(dsel, hs, (size_t)n * sizeof(int), hipMemcpyHostToDevice, dst->stream) == hipSuccess;
-    ok = ok && hipEventRecord(w.e0, dst->stream) == hipSuccess;
-    hipLaunchKernelGGL(obca_quad_subdivide_batch_kernel, dim3(n), dim3(QNT), 0, dst->stream, n, src->N, factor, margin, (const int *)dsel, src->d, dst->d, dst_st);
-    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(w.e1, dst->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(status, dst_st, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, dst->stream) == hipSuccess;
-    if (hipStreamSynchronize(dst->stream) != hipSuccess || !ok) { ctx->err = "obca_quad_batch_subdivide_into: kernel or copy failed"; return -2; }
-    w.timed = 1; dst->uploaded = 1;
-    return 0;
+    return into_call("obca_quad_batch_subdivide_into", dst, src, dst->sd, factor, "nothing has been solved on the source since its last upload or shift",
+                     qsd::subdivide_check_args(n, src->N, factor, margin), sel, n, status, [&] { dst->B = n; dst->solved = 0; return 0; },
+                     [&](const int *dsel, int *dstatus) {
+        hipLaunchKernelGGL(obca_quad_subdivide_batch_kernel, dim3(n), dim3(QNT), 0, dst->stream, n, src->N, factor, margin, dsel, src->d, dst->d, dstatus);
+    });
 }
 
 int obca_quad_batch_subdivide_ms(obca_quad_batch *dst, float *ms) {
-    if (!dst || !ms) return -1;
-    return core_elapsed_ms(dst, dst->sd.timed != 0, dst->sd.e0, dst->sd.e1, ms, "obca_quad_batch_subdivide_ms: no subdivide call has written into this batch");
+    return dst && ms ? core_elapsed_ms(dst->ctx, dst->sd.ev, ms, "obca_quad_batch_subdivide_ms: no subdivide call has written into this batch") : -1;
 }
 
 int obca_quadcopter_subdivide_batch(obca_ctx *ctx, int B, int N, int factor, const double *Ts, const double *x, const double *timeScale, double *Ts_f, double *x_f) {
@@ -1752,9 +1699,8 @@ int obca_quadcopter_subdivide_batch(obca_ctx *ctx, int B, int N, int factor, con
     if (!bad && !(Ts && x && Ts_f && x_f)) bad = "NULL argument";
     if (bad) { ctx->err = std::string("obca_quadcopter_subdivide_batch: ") + bad; return -1; }
     use_device(ctx->device);
-    if (!ctx->qsd) ctx->qsd = new PathWsBufs();
-    PathWsBufs &w = *ctx->qsd;
-    if (int rc = refine_events(ctx->err, w)) return rc;
+    KernelStage &w = ctx->qsd;
+    if (int rc = w.ev.ensure(ctx->err)) return rc;
     const size_t Nf = (size_t)N * factor, nx = (size_t)B * QX * (N + 1), nt = timeScale ? (size_t)B * (N + 1) : 0, nin = B + nx + nt, nxf = (size_t)B * QX * (Nf + 1);
     if (w.dev.reserve(nin + B + nxf, ctx->stream) != hipSuccess) { ctx->err = "obca_quadcopter_subdivide_batch: hipMalloc failed"; return -2; }
     if (w.host.reserve(ctx->err, nin)) return -2;
@@ -1762,15 +1708,10 @@ int obca_quadcopter_subdivide_batch(obca_ctx *ctx, int B, int N, int factor, con
     memcpy(h, Ts, sizeof(double) * B); memcpy(h + B, x, sizeof(double) * nx);
     if (nt) memcpy(h + B + nx, timeScale, sizeof(double) * nt);
     double *dTsf = d + nin, *dxf = dTsf + B;
-    bool ok = hipMemcpyAsync(d, h, nin * sizeof(double), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-    ok = ok && hipEventRecord(w.e0, ctx->stream) == hipSuccess;
-    hipLaunchKernelGGL(obca_quad_subdivide_host_kernel, dim3(B), dim3(QNT), 0, ctx->stream, B, N, factor, (const double *)d, (const double *)(d + B), (const double *)(nt ? d + B + nx : nullptr), dTsf, dxf);
-    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(w.e1, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(Ts_f, dTsf, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(x_f, dxf, nxf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess || !ok) { ctx->err = "obca_quadcopter_subdivide_batch: kernel or copy failed"; return -2; }
-    w.timed = 1;
-    return 0;
+    const bool up = hipMemcpyAsync(d, h, nin * sizeof(double), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    return launch_timed(ctx->err, "obca_quadcopter_subdivide_batch", ctx->stream, w.ev, up, [&] {
+        hipLaunchKernelGGL(obca_quad_subdivide_host_kernel, dim3(B), dim3(QNT), 0, ctx->stream, B, N, factor, (const double *)d, (const double *)(d + B), (const double *)(nt ? d + B + nx : nullptr), dTsf, dxf);
+    }, {{Ts_f, dTsf, (size_t)B * sizeof(double)}, {x_f, dxf, nxf * sizeof(double)}});
 }
 
 }  // extern "C"
@@ -1798,190 +1739,145 @@ __global__ __launch_bounds__(HY_NT) void obca_hybrid_kernel(int B, int slots, co
                    counts + i, nexp + i, rounds + i);
 }
 
-extern "C" {
-
-// ---- the parking planner on the device (obca_hybrid.h, include/obca_plan_device.h)
+// ---- the parking planner on the device (obca_hybrid.h, include/obca_plan_device.h) and the same planner with every search in the obstacle field of its own instance
+// (include/obca_plan_scenes.h).  The two entry points share the slots and the staging block; each has its own events and its own instantiation of the kernel.
 #define OBCA_HYBRID_BUDGET ((size_t)16 << 30)      // bytes the slots take by default
-int obca_hybrid_configure(obca_ctx *ctx, int slots, int max_nodes, int max_chunks) {
+static inline size_t up8(size_t n) { return (n + 7) / 8 * 8; }
+// What both entry points do around their own validation and packing.  One block travels up: [ Params | inst B x 10 | the entry's field data ].  make(mn, mc, P, inst, up, o_fld)
+// checks the arguments (a text refuses the call), fills P and inst and sizes `up` to hold its field data from byte o_fld on; bind(d, F, S) then builds the device-side Field
+// (shared field; it returns the blocked map) or Fields (per-instance fields) over that data at `d` on the device.  One block comes down: [ paths | dirs | counts | expansions | rounds ].
+// `kernel` is the entry's instantiation of obca_hybrid_kernel, `own` its index (0: shared field, 1: per-instance fields) to the events and the LDS attribute of its own.
+// A failed device call behind the slots' allocation releases the planner's memory: the slots may hold a half-finished search, the next call starts from fresh ones.
+template <typename Make, typename Bind>
+static int hybrid_call(obca_ctx *ctx, const char *entry, int own, decltype(&obca_hybrid_kernel<false>) kernel, int B, double *paths, int *dirs, int cap, int *counts, int *expansions, int *rounds, Make &&make, Bind &&bind) {
     if (!ctx) return -1;
-    if (slots < 0 || slots > OBCA_HYBRID_MAXSLOTS || max_nodes < 0 || max_nodes > OBCA_HYBRID_MAXNODES || max_chunks < 0 || max_chunks > (1 << 24)) {
-        ctx->err = "obca_hybrid_configure: need 0 <= slots <= OBCA_HYBRID_MAXSLOTS, 0 <= max_nodes <= OBCA_HYBRID_MAXNODES, 0 <= max_chunks <= 2^24"; return -1;
-    }
-    if (!ctx->hyb) ctx->hyb = new HybridBufs();
-    ctx->hyb->slots = slots; ctx->hyb->max_nodes = max_nodes; ctx->hyb->max_chunks = max_chunks;
-    return 0;
-}
-
-int obca_hybrid_astar_batch(obca_ctx *ctx, int B, const double *starts, const double *goals, int nOb, const int *vOb, const double *A, const double *b,
-                            const double ego[4], double L, const double XYbounds[4], const double *opts, int nopts, double bucket_width,
-                            double *paths, int *dirs, int cap, int *counts, int *expansions, int *rounds) {
-    if (!ctx) return -1;
-    if (!ctx->hyb) ctx->hyb = new HybridBufs();
-    HybridBufs &h = *ctx->hyb;
+    HybridBufs &h = ctx->hyb; EventPair &ev = h.ev[own];
     const int mn = h.max_nodes ? h.max_nodes : OBCA_HYBRID_MAXNODES, mc = h.max_chunks ? h.max_chunks : hy::default_chunks(mn);
-    hy::Params P; hy::HostField W; std::vector<unsigned char> blocked; std::vector<double> inst;
-    const char *bad = (paths && dirs && counts) ? hy::make_params(B, starts, goals, nOb, vOb, A, b, ego, L, XYbounds, opts, nopts, bucket_width, cap, mn, mc, P, W, blocked, inst)
-                                                : "NULL output array";
-    if (bad) { ctx->err = std::string("obca_hybrid_astar_batch: ") + bad; return -1; }
+    hy::Params P; std::vector<double> inst; std::vector<char> up;
+    const size_t o_inst = up8(sizeof(hy::Params)), o_fld = o_inst + (size_t)std::max(B, 0) * 10 * 8;
+    const std::string bad = (paths && dirs && counts) ? make(mn, mc, P, inst, up, o_fld) : std::string("NULL output array");
+    if (!bad.empty()) { ctx->err = std::string(entry) + ": " + bad; return -1; }
+    auto fail = [&](const char *what) { ctx->err = std::string(entry) + ": " + what; h.release(); return -2; };
     use_device(ctx->device);
-    if (!h.have_ev) {
-        if (hipEventCreate(&h.e0) != hipSuccess) { ctx->err = "hipEventCreate failed"; return -2; }
-        if (hipEventCreate(&h.e1) != hipSuccess) { (void)hipEventDestroy(h.e0); ctx->err = "hipEventCreate failed"; return -2; }
-        h.have_ev = 1;
-    }
-    h.timed = 0;
+    if (int rc = ev.ensure(ctx->err)) return rc;
+    ev.timed = 0;
     // the slots: as many as configured, else what the budget holds, never more than searches
     const size_t sb = hy::slot_bytes(P.ncell, mn, mc);
     int slots = h.slots ? h.slots : (int)std::min<size_t>(OBCA_HYBRID_MAXSLOTS, std::max<size_t>(1, OBCA_HYBRID_BUDGET / sb));
     slots = std::min(slots, B);
     if (!h.slotmem || h.nslots < slots || h.ncell != P.ncell || h.nodes != mn || h.chunks != mc) {
         if (h.slotmem) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.slotmem); h.slotmem = nullptr; h.nslots = 0; }
-        if (hipMalloc((void **)&h.slotmem, sb * slots) != hipSuccess) { h.slotmem = nullptr; ctx->err = "obca_hybrid_astar_batch: hipMalloc of the slots failed (fewer slots or nodes: obca_hybrid_configure)"; return -2; }
+        if (hipMalloc((void **)&h.slotmem, sb * slots) != hipSuccess) { h.slotmem = nullptr; ctx->err = std::string(entry) + ": hipMalloc of the slots failed (fewer slots or nodes: obca_hybrid_configure)"; return -2; }
         h.slot_bytes = sb; h.nslots = slots; h.ncell = P.ncell; h.nodes = mn; h.chunks = mc;
         bool ok = true;      // claim words and cell table: all ones; a search leaves them so
         for (int s = 0; s < slots && ok; s++) ok = hipMemsetAsync(h.slotmem + (size_t)s * sb, 0xFF, hy::slot_init_bytes(P.ncell), ctx->stream) == hipSuccess;
-        if (!ok) { ctx->err = "obca_hybrid_astar_batch: hipMemsetAsync failed"; return -2; }
+        if (!ok) return fail("hipMemsetAsync failed");
     }
-    // one block up: [ Params | inst B x 10 | A | b | rn | vert | v off voff (ints) | blocked (bytes) ], one block down: [ paths | dirs | counts | expansions | rounds ]
-    auto up8 = [](size_t n) { return (n + 7) / 8 * 8; };
-    const size_t M_ = W.b.size(), nv = W.vert.size();
-    const size_t o_inst = up8(sizeof(hy::Params)), o_A = o_inst + inst.size() * 8, o_b = o_A + 2 * M_ * 8, o_rn = o_b + M_ * 8, o_vert = o_rn + M_ * 8, o_int = o_vert + nv * 8,
-                 o_blk = o_int + up8((size_t)(3 * nOb + 2) * 4), n_in = up8(o_blk + blocked.size());
-    const size_t o_paths = n_in, o_dirs = o_paths + (size_t)B * cap * 24, o_cnt = o_dirs + up8((size_t)B * cap * 4), n_all = o_cnt + up8((size_t)3 * B * 4);
+    const size_t n_in = up.size(), o_paths = n_in, o_dirs = o_paths + (size_t)B * cap * 24, o_cnt = o_dirs + up8((size_t)B * cap * 4), n_all = o_cnt + up8((size_t)3 * B * 4);
     if (h.io_bytes < n_all) {
         if (h.io) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.io); h.io = nullptr; h.io_bytes = 0; }
-        if (hipMalloc((void **)&h.io, n_all) != hipSuccess) { h.io = nullptr; ctx->err = "obca_hybrid_astar_batch: hipMalloc failed"; return -2; }
+        if (hipMalloc((void **)&h.io, n_all) != hipSuccess) { h.io = nullptr; return fail("hipMalloc failed"); }
         h.io_bytes = n_all;
     }
-    std::vector<char> up(n_in, 0);
     memcpy(up.data(), &P, sizeof P); memcpy(up.data() + o_inst, inst.data(), inst.size() * 8);
-    if (M_) { memcpy(up.data() + o_A, W.A.data(), 2 * M_ * 8); memcpy(up.data() + o_b, W.b.data(), M_ * 8); memcpy(up.data() + o_rn, W.rn.data(), M_ * 8); }
-    if (nv) memcpy(up.data() + o_vert, W.vert.data(), nv * 8);
-    int *ip = (int *)(up.data() + o_int);
-    for (int j = 0; j < nOb; j++) ip[j] = W.v[j];
-    for (int j = 0; j <= nOb; j++) { ip[nOb + j] = W.off[j]; ip[2 * nOb + 1 + j] = W.voff[j]; }
-    memcpy(up.data() + o_blk, blocked.data(), blocked.size());
     char *d = h.io;
-    hy::Field F; F.nOb = nOb; F.v = (const int *)(d + o_int); F.off = F.v + nOb; F.voff = F.off + nOb + 1;
-    F.A = (const double *)(d + o_A); F.b = (const double *)(d + o_b); F.rn = (const double *)(d + o_rn); F.vert = (const double *)(d + o_vert);
+    hy::Field F = hy::Field(); hy::Fields S = hy::Fields();
+    const unsigned char *blocked = bind(d + o_fld, F, S);
     const int lds = (((P.nmap + 1) & ~1) + HY_LDS_INTS) * (int)sizeof(float);
-    if (lds > h.lds_set) {
-        if (hipFuncSetAttribute((const void *)obca_hybrid_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) { ctx->err = "obca_hybrid_astar_batch: hipFuncSetAttribute failed"; return -2; }
-        h.lds_set = lds;
+    if (lds > h.lds_set[own]) {
+        if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return fail("hipFuncSetAttribute failed");
+        h.lds_set[own] = lds;
     }
     int *dcnt = (int *)(d + o_cnt);
-    bool ok = hipMemcpyAsync(d, up.data(), n_in, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-    ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess;      // (`up` is pageable and leaves scope)
-    ok = ok && hipEventRecord(h.e0, ctx->stream) == hipSuccess;
-    hipLaunchKernelGGL(obca_hybrid_kernel<false>, dim3(slots), dim3(HY_NT), lds, ctx->stream, B, slots, (const hy::Params *)d, F, hy::Fields(), (const unsigned char *)(d + o_blk), (const double *)(d + o_inst),
-                       h.slotmem, sb, (double *)(d + o_paths), (int *)(d + o_dirs), dcnt, dcnt + B, dcnt + 2 * B);
-    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(h.e1, ctx->stream) == hipSuccess;
-    std::vector<int> tail((size_t)3 * B);
-    ok = ok && hipMemcpyAsync(paths, d + o_paths, (size_t)B * cap * 24, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(dirs, d + o_dirs, (size_t)B * cap * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(tail.data(), dcnt, (size_t)3 * B * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess || !ok) {
-        ctx->err = "obca_hybrid_astar_batch: kernel or copy failed";
-        h.release();      // the slots may hold a half-finished search: the next call starts from fresh ones
-        return -2;
-    }
+    int *tail = (int *)up.data();      // once `up` has travelled, its head (Params and inst: more than 3 B ints) takes the three count arrays on the way back
+    const bool sent =hipMemcpyAsync(d, up.data(), n_in, hipMemcpyHostToDevice, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;      // (`up` is pageable)
+    const int rc = launch_timed(ctx->err, entry, ctx->stream, ev, sent, [&] {
+        hipLaunchKernelGGL(kernel, dim3(slots), dim3(HY_NT), lds, ctx->stream, B, slots, (const hy::Params *)d, F, S, blocked, (const double *)(d + o_inst),
+                           h.slotmem, sb, (double *)(d + o_paths), (int *)(d + o_dirs), dcnt, dcnt + B, dcnt + 2 * B);
+    }, {{paths, d + o_paths, (size_t)B * cap * 24}, {dirs, d + o_dirs, (size_t)B * cap * 4}, {tail, dcnt, (size_t)3 * B * 4}});
+    if (rc) { h.release(); return rc; }
     for (int i = 0; i < B; i++) { counts[i] = tail[i]; if (expansions) expansions[i] = tail[B + i]; if (rounds) rounds[i] = tail[2 * B + i]; }
-    h.timed = 1;
     return 0;
+}
+
+extern "C" {
+
+int obca_hybrid_configure(obca_ctx *ctx, int slots, int max_nodes, int max_chunks) {
+    if (!ctx) return -1;
+    if (slots < 0 || slots > OBCA_HYBRID_MAXSLOTS || max_nodes < 0 || max_nodes > OBCA_HYBRID_MAXNODES || max_chunks < 0 || max_chunks > (1 << 24)) {
+        ctx->err = "obca_hybrid_configure: need 0 <= slots <= OBCA_HYBRID_MAXSLOTS, 0 <= max_nodes <= OBCA_HYBRID_MAXNODES, 0 <= max_chunks <= 2^24"; return -1;
+    }
+    ctx->hyb.slots = slots; ctx->hyb.max_nodes = max_nodes; ctx->hyb.max_chunks = max_chunks;
+    return 0;
+}
+
+// one field for the batch; its blocked cells come from the host.  Field data: [ A | b | rn | vert | v off voff (ints) | blocked (bytes) ]
+int obca_hybrid_astar_batch(obca_ctx *ctx, int B, const double *starts, const double *goals, int nOb, const int *vOb, const double *A, const double *b,
+                            const double ego[4], double L, const double XYbounds[4], const double *opts, int nopts, double bucket_width,
+                            double *paths, int *dirs, int cap, int *counts, int *expansions, int *rounds) {
+    hy::HostField W; std::vector<unsigned char> blocked;
+    size_t M_ = 0, o_int = 0, o_blk = 0;
+    return hybrid_call(ctx, "obca_hybrid_astar_batch", 0, obca_hybrid_kernel<false>, B, paths, dirs, cap, counts, expansions, rounds,
+                              [&](int mn, int mc, hy::Params &P, std::vector<double> &inst, std::vector<char> &up, size_t o_fld) -> std::string {
+        if (const char *bad = hy::make_params(B, starts, goals, nOb, vOb, A, b, ego, L, XYbounds, opts, nopts, bucket_width, cap, mn, mc, P, W, blocked, inst)) return bad;
+        M_ = W.b.size();
+        const size_t nv = W.vert.size();
+        o_int = (4 * M_ + nv) * 8; o_blk = o_int + up8((size_t)(3 * nOb + 2) * 4);
+        up.assign(o_fld + up8(o_blk + blocked.size()), 0);
+        char *u = up.data() + o_fld;
+        if (M_) { memcpy(u, W.A.data(), 2 * M_ * 8); memcpy(u + 2 * M_ * 8, W.b.data(), M_ * 8); memcpy(u + 3 * M_ * 8, W.rn.data(), M_ * 8); }
+        if (nv) memcpy(u + 4 * M_ * 8, W.vert.data(), nv * 8);
+        int *ip = (int *)(u + o_int);
+        for (int j = 0; j < nOb; j++) ip[j] = W.v[j];
+        for (int j = 0; j <= nOb; j++) { ip[nOb + j] = W.off[j]; ip[2 * nOb + 1 + j] = W.voff[j]; }
+        memcpy(u + o_blk, blocked.data(), blocked.size());
+        return std::string();
+    }, [&](const char *d, hy::Field &F, hy::Fields &) {
+        F.nOb = nOb; F.v = (const int *)(d + o_int); F.off = F.v + nOb; F.voff = F.off + nOb + 1;
+        F.A = (const double *)d; F.b = F.A + 2 * M_; F.rn = F.b + M_; F.vert = F.rn + M_;
+        return (const unsigned char *)(d + o_blk);
+    });
 }
 
 int obca_hybrid_ms(obca_ctx *ctx, float *ms) {
-    if (!ctx || !ms) return -1;
-    if (!ctx->hyb || !ctx->hyb->timed || hipEventElapsedTime(ms, ctx->hyb->e0, ctx->hyb->e1) != hipSuccess) { ctx->err = "obca_hybrid_ms: no search has run on this context"; return -2; }
-    return 0;
+    return ctx && ms ? core_elapsed_ms(ctx, ctx->hyb.ev[0], ms, "obca_hybrid_ms: no search has run on this context") : -1;
 }
 
-// ---- the same planner, every search in the obstacle field of its own instance (include/obca_plan_scenes.h): obca_hybrid_astar_batch's host side with the packed fields
-// and their records in place of the one field and its blocked map; the slots and the staging block are shared with it, the events are this call's own
+// every search in the field of its own instance, put together on the device from the instance's record; the search finds the blocked cells itself.
+// Field data: [ A | b | rn | nrm | vert | rec (B x 4) v off voff (ints) ]
 int obca_scene_astar_batch(obca_ctx *ctx, int B, const double *starts, const double *goals, const int *nOb, const int *vOb, const double *A, const double *b,
                            const double ego[4], double L, const double XYbounds[4], const double *opts, int nopts, double bucket_width,
                            double *paths, int *dirs, int cap, int *counts, int *expansions, int *rounds) {
-    if (!ctx) return -1;
-    if (!ctx->hyb) ctx->hyb = new HybridBufs();
-    HybridBufs &h = *ctx->hyb;
-    const int mn = h.max_nodes ? h.max_nodes : OBCA_HYBRID_MAXNODES, mc = h.max_chunks ? h.max_chunks : hy::default_chunks(mn);
-    hy::Params P; hy::HostFields W; std::vector<double> inst;
-    const std::string bad = (paths && dirs && counts) ? hy::make_scenes(B, starts, goals, nOb, vOb, A, b, ego, L, XYbounds, opts, nopts, bucket_width, cap, mn, mc, P, W, inst)
-                                                      : std::string("NULL output array");
-    if (!bad.empty()) { ctx->err = "obca_scene_astar_batch: " + bad; return -1; }
-    use_device(ctx->device);
-    if (!h.have_sev) {
-        if (hipEventCreate(&h.s0) != hipSuccess) { ctx->err = "hipEventCreate failed"; return -2; }
-        if (hipEventCreate(&h.s1) != hipSuccess) { (void)hipEventDestroy(h.s0); ctx->err = "hipEventCreate failed"; return -2; }
-        h.have_sev = 1;
-    }
-    h.stimed = 0;
-    const size_t sb = hy::slot_bytes(P.ncell, mn, mc);
-    int slots = h.slots ? h.slots : (int)std::min<size_t>(OBCA_HYBRID_MAXSLOTS, std::max<size_t>(1, OBCA_HYBRID_BUDGET / sb));
-    slots = std::min(slots, B);
-    if (!h.slotmem || h.nslots < slots || h.ncell != P.ncell || h.nodes != mn || h.chunks != mc) {
-        if (h.slotmem) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.slotmem); h.slotmem = nullptr; h.nslots = 0; }
-        if (hipMalloc((void **)&h.slotmem, sb * slots) != hipSuccess) { h.slotmem = nullptr; ctx->err = "obca_scene_astar_batch: hipMalloc of the slots failed (fewer slots or nodes: obca_hybrid_configure)"; return -2; }
-        h.slot_bytes = sb; h.nslots = slots; h.ncell = P.ncell; h.nodes = mn; h.chunks = mc;
-        bool ok = true;      // claim words and cell table: all ones; a search leaves them so
-        for (int s = 0; s < slots && ok; s++) ok = hipMemsetAsync(h.slotmem + (size_t)s * sb, 0xFF, hy::slot_init_bytes(P.ncell), ctx->stream) == hipSuccess;
-        if (!ok) { ctx->err = "obca_scene_astar_batch: hipMemsetAsync failed"; h.release(); return -2; }
-    }
-    // one block up: [ Params | inst B x 10 | A | b | rn | nrm | vert | rec (B x 4) v off voff (ints) ], one block down: [ paths | dirs | counts | expansions | rounds ]
-    auto up8 = [](size_t n) { return (n + 7) / 8 * 8; };
-    const size_t M_ = W.b.size(), nv = W.vert.size(), nob = W.v.size(), noff = W.off.size();      // (noff = nob + B)
-    const size_t o_inst = up8(sizeof(hy::Params)), o_A = o_inst + inst.size() * 8, o_b = o_A + 2 * M_ * 8, o_rn = o_b + M_ * 8, o_nrm = o_rn + M_ * 8, o_vert = o_nrm + M_ * 8,
-                 o_rec = o_vert + nv * 8, o_v = o_rec + (size_t)4 * B * 4, o_off = o_v + nob * 4, o_voff = o_off + noff * 4, n_in = up8(o_voff + noff * 4);
-    const size_t o_paths = n_in, o_dirs = o_paths + (size_t)B * cap * 24, o_cnt = o_dirs + up8((size_t)B * cap * 4), n_all = o_cnt + up8((size_t)3 * B * 4);
-    if (h.io_bytes < n_all) {
-        if (h.io) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.io); h.io = nullptr; h.io_bytes = 0; }
-        if (hipMalloc((void **)&h.io, n_all) != hipSuccess) { h.io = nullptr; ctx->err = "obca_scene_astar_batch: hipMalloc failed"; h.release(); return -2; }
-        h.io_bytes = n_all;
-    }
-    std::vector<char> up(n_in, 0);
-    memcpy(up.data(), &P, sizeof P); memcpy(up.data() + o_inst, inst.data(), inst.size() * 8);
-    if (M_) {
-        memcpy(up.data() + o_A, W.A.data(), 2 * M_ * 8); memcpy(up.data() + o_b, W.b.data(), M_ * 8); memcpy(up.data() + o_rn, W.rn.data(), M_ * 8);
-        memcpy(up.data() + o_nrm, W.nrm.data(), M_ * 8);
-    }
-    if (nv) memcpy(up.data() + o_vert, W.vert.data(), nv * 8);
-    memcpy(up.data() + o_rec, W.rec.data(), (size_t)4 * B * 4);
-    if (nob) memcpy(up.data() + o_v, W.v.data(), nob * 4);
-    memcpy(up.data() + o_off, W.off.data(), noff * 4); memcpy(up.data() + o_voff, W.voff.data(), noff * 4);
-    char *d = h.io;
-    hy::Fields S; S.rec = (const int *)(d + o_rec); S.v = (const int *)(d + o_v); S.off = (const int *)(d + o_off); S.voff = (const int *)(d + o_voff);
-    S.A = (const double *)(d + o_A); S.b = (const double *)(d + o_b); S.rn = (const double *)(d + o_rn); S.nrm = (const double *)(d + o_nrm); S.vert = (const double *)(d + o_vert);
-    const int lds = (((P.nmap + 1) & ~1) + HY_LDS_INTS) * (int)sizeof(float);
-    if (lds > h.lds_sset) {
-        if (hipFuncSetAttribute((const void *)obca_hybrid_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) { ctx->err = "obca_scene_astar_batch: hipFuncSetAttribute failed"; h.release(); return -2; }
-        h.lds_sset = lds;
-    }
-    int *dcnt = (int *)(d + o_cnt);
-    bool ok = hipMemcpyAsync(d, up.data(), n_in, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-    ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess;      // (`up` is pageable and leaves scope)
-    ok = ok && hipEventRecord(h.s0, ctx->stream) == hipSuccess;
-    if (ok) hipLaunchKernelGGL(obca_hybrid_kernel<true>, dim3(slots), dim3(HY_NT), lds, ctx->stream, B, slots, (const hy::Params *)d, hy::Field(), S, (const unsigned char *)nullptr,
-                               (const double *)(d + o_inst), h.slotmem, sb, (double *)(d + o_paths), (int *)(d + o_dirs), dcnt, dcnt + B, dcnt + 2 * B);
-    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(h.s1, ctx->stream) == hipSuccess;
-    std::vector<int> tail((size_t)3 * B);
-    ok = ok && hipMemcpyAsync(paths, d + o_paths, (size_t)B * cap * 24, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(dirs, d + o_dirs, (size_t)B * cap * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(tail.data(), dcnt, (size_t)3 * B * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess || !ok) {
-        ctx->err = "obca_scene_astar_batch: kernel or copy failed";
-        h.release();      // the slots may hold a half-finished search: the next call starts from fresh ones
-        return -2;
-    }
-    for (int i = 0; i < B; i++) { counts[i] = tail[i]; if (expansions) expansions[i] = tail[B + i]; if (rounds) rounds[i] = tail[2 * B + i]; }
-    h.stimed = 1;
-    return 0;
+    hy::HostFields W;
+    size_t M_ = 0, o_rec = 0;
+    return hybrid_call(ctx, "obca_scene_astar_batch", 1, obca_hybrid_kernel<true>, B, paths, dirs, cap, counts, expansions, rounds,
+                             [&](int mn, int mc, hy::Params &P, std::vector<double> &inst, std::vector<char> &up, size_t o_fld) -> std::string {
+        const std::string bad = hy::make_scenes(B, starts, goals, nOb, vOb, A, b, ego, L, XYbounds, opts, nopts, bucket_width, cap, mn, mc, P, W, inst);
+        if (!bad.empty()) return bad;
+        M_ = W.b.size();
+        const size_t nv = W.vert.size(), nob = W.v.size(), noff = W.off.size();      // (noff = nob + B)
+        o_rec = (5 * M_ + nv) * 8;
+        up.assign(o_fld + up8(o_rec + ((size_t)4 * B + nob + 2 * noff) * 4), 0);
+        char *u = up.data() + o_fld;
+        if (M_) {
+            memcpy(u, W.A.data(), 2 * M_ * 8); memcpy(u + 2 * M_ * 8, W.b.data(), M_ * 8); memcpy(u + 3 * M_ * 8, W.rn.data(), M_ * 8);
+            memcpy(u + 4 * M_ * 8, W.nrm.data(), M_ * 8);
+        }
+        if (nv) memcpy(u + 5 * M_ * 8, W.vert.data(), nv * 8);
+        int *ip = (int *)(u + o_rec);
+        memcpy(ip, W.rec.data(), (size_t)4 * B * 4);
+        if (nob) memcpy(ip + 4 * B, W.v.data(), nob * 4);
+        memcpy(ip + 4 * B + nob, W.off.data(), noff * 4); memcpy(ip + 4 * B + nob + noff, W.voff.data(), noff * 4);
+        return bad;
+    }, [&](const char *d, hy::Field &, hy::Fields &S) {
+        S.rec = (const int *)(d + o_rec); S.v = S.rec + 4 * B; S.off = S.v + W.v.size(); S.voff = S.off + W.off.size();
+        S.A = (const double *)d; S.b = S.A + 2 * M_; S.rn = S.b + M_; S.nrm = S.rn + M_; S.vert = S.nrm + M_;
+        return (const unsigned char *)nullptr;
+    });
 }
 
 int obca_scene_astar_ms(obca_ctx *ctx, float *ms) {
-    if (!ctx || !ms) return -1;
-    if (!ctx->hyb || !ctx->hyb->stimed || hipEventElapsedTime(ms, ctx->hyb->s0, ctx->hyb->s1) != hipSuccess) { ctx->err = "obca_scene_astar_ms: no per-instance search has run on this context"; return -2; }
-    return 0;
+    return ctx && ms ? core_elapsed_ms(ctx, ctx->hyb.ev[1], ms, "obca_scene_astar_ms: no per-instance search has run on this context") : -1;
 }
-
 
 }  // extern "C"
