@@ -58,6 +58,8 @@ def _load():
     cabi.bind(_lib, "obca_quad_subdivide.h")              # ... and solved quadcopter batches
     cabi.bind(_lib, "obca_plan_device.h")                 # the parking planner on the device
     cabi.bind(_lib, "obca_plan_scenes.h")                 # ... in per-instance obstacle fields
+    cabi.bind(_lib, "obca_plan_resident.h")               # ... from the records of an uploaded batch
+    cabi.bind(_lib, "obca_plan_resident_check.h")         # ... and the diagnostic that hands out what its packing kernel wrote
     return _lib
 
 
@@ -89,6 +91,9 @@ HYBRID_STATUS = {0: "no path", -1: "more nodes than cap", -2: "the start or goal
 # include/obca_plan_scenes.h: the same planner, every search in the obstacle field of its own instance (scene_astar_batch, scene_ms, planner.scene_astar_many,
 # planner.scene_warm_start_many, scenarios.make_scene_batch(device=...)); slots, pools and status codes are the shared-field planner's
 SCENE_EXPORTS = ["obca_scene_astar_batch", "obca_scene_astar_ms"]
+# include/obca_plan_resident.h: the same search from what an uploaded batch holds, its paths straight into the batch's warm start (Batch.plan_warm_start, plan_ms, plan_paths)
+PLAN_RESIDENT_EXPORTS = ["obca_batch_plan_warm_start", "obca_batch_plan_ms", "obca_batch_plan_download"]
+PLAN_RESIDENT_CHECK_EXPORTS = ["obca_batch_packed_block"]      # include/obca_plan_resident_check.h: a diagnostic (Batch.plan_block)
 QUAD_REFINE_STATUS = {0: "refined from the solution", 1: "interpolated from the uploaded warm start (the last solve failed, or its iterate is not finite)",
                       -1: "zero warm start (the uploaded one is not finite either)"}
 REFINE_STATUS = {0: "refined from the solution", 1: "refined from the start iterate (the last solve failed, or its iterate is not finite)", -1: "zero start (the start iterate is not finite either)"}
@@ -404,6 +409,47 @@ class Batch(_DeviceBatch):
         a = C.c_float(0)
         self._call("path_ws_ms", C.byref(a))
         return a.value
+
+    def plan_warm_start(self, bucket_width=None, cap=1024, v_nom=0.5, smooth=False, use_xF=True, **planner_options):
+        """The resident route (obca_batch_plan_warm_start): every instance of the uploaded batch is planned ON THE DEVICE in its own obstacle field -- put together there
+        from the record the upload left: x0, xF, the unit rows, the uploaded ego, L and XYbounds -- by scene_astar_batch's search, and set_path_warm_start's kernel writes
+        the warm start from the paths where they lie.  No path, no field and no pose crosses the bus.  planner_options: the search options by name, as
+        planner.scene_astar_many takes them (planner.DEFAULT_OPTS); bucket_width, cap: scene_astar_batch's (cap <= PATH_WS_MAXNODES); v_nom, smooth, use_xF:
+        set_path_warm_start's.  Returns (counts, status, expansions, rounds), (B,) int32 each: counts as scene_astar_batch (HYBRID_STATUS), status as set_path_warm_start
+        (PATH_WS_STATUS; an instance with a negative one keeps what was uploaded)."""
+        from . import planner
+        o = dict(planner.DEFAULT_OPTS); o.update(planner_options)
+        opts = np.array([o[k] for k in planner.DEFAULT_OPTS], float)
+        cnt, st, nexp, rounds = (np.zeros(self.B, np.int32) for _ in range(4))
+        self._call("plan_warm_start", opts, len(opts), 0.0 if bucket_width is None else float(bucket_width), int(cap), bool(use_xF), float(v_nom), 0.3 if smooth else 0.0,
+                   cnt, st, nexp, rounds)
+        return cnt, st, nexp, rounds
+
+    def plan_ms(self):
+        """HIP-event durations (pack, search, ws) of the three kernels of the last plan_warm_start [ms]"""
+        a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
+        self._call("plan_ms", C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value, c.value
+
+    def plan_paths(self):
+        """What the last plan_warm_start planned, for plots and tests: (paths (B, cap, 3), dirs (B, cap), inst (B, 10) -- the instance records the packing kernel wrote:
+        start x, y, yaw, sin, cos, goal x, y, yaw, sin, cos).  They lie in the context's planner staging: an ObcaError once another planner call of the context has run."""
+        cap = _load().obca_batch_plan_download(self._h, None, None, 0, None)      # (no array: the call answers with the last plan's cap, whoever made the plan)
+        if cap < 2:
+            self.ctx._check(cap, "obca_batch_plan_download")
+        paths = np.zeros((self.B, cap, 3)); dirs = np.zeros((self.B, cap), np.int32); inst = np.zeros((self.B, 10))
+        self._call("plan_download", paths, dirs, cap, inst)
+        return paths, dirs, inst
+
+    def plan_block(self):
+        """DIAGNOSTIC (obca_batch_packed_block): what the packing kernel of the last plan_warm_start wrote on the device, as the search read it -- (block, dims): the bytes of
+        the packed block (layout: obca_amd/csrc/obca_plan_resident.h) and dict(B, nObMax, MMax, slot_allocs, io_allocs), the last two counting how often the context's planner
+        has allocated its slots and its staging block so far."""
+        d = np.zeros(6, np.int32)
+        self._call("packed_block", None, 0, d)
+        block = np.zeros(int(d[3]))
+        self._call("packed_block", block, len(block), d)
+        return block.view(np.uint8), dict(B=int(d[0]), nObMax=int(d[1]), MMax=int(d[2]), slot_allocs=int(d[4]), io_allocs=int(d[5]))
 
     def shift_warm_start(self, shift, x0_new=None):
         """receding-horizon restart: the next solve starts from the last solution advanced by `shift` stages (kept on the device)."""

@@ -10,10 +10,11 @@
 //   obca_refine_*_kernel    : one wavefront per destination instance, a solved parking instance on a finer horizon (obca_refine.h): into a second resident batch or host-bound arrays.
 //   obca_quad_subdivide_*_kernel : the same for a solved quadcopter instance (obca_quad_subdivide.h): it rewrites a problem record.
 //   obca_path_ws_*_kernel   : one wavefront per instance, the parking warm start from a planner path (obca_path_ws.h): into host-bound arrays or into a resident batch.
+//   obca_plan_pack_kernel   : one wavefront per instance, the planner's obstacle field and poses from the problem record of a resident batch (obca_plan_resident.h).
 //   obca_shift_kernel, obca_quad_shift_kernel : receding-horizon restarts, one workgroup per instance: the warm start of the next solve from the last solution
 //                             (parking: below; quadcopter: obca_quad_shift.h).
 // Host helpers the entry points are built from (below "host side"): EventPair, KernelStage (staging types); run_validate, launch_timed (a kernel between two events, results down);
-//   run_chunks with parking_chunks / quad_chunks (host-pointer calls over the slots); into_call (refine / subdivide into a second batch); hybrid_call (both planner entry points).
+//   run_chunks with parking_chunks / quad_chunks (host-pointer calls over the slots); into_call (refine / subdivide into a second batch); hybrid_call (both planner entry points) over hybrid_reserve / hybrid_launch (shared with the resident route).
 // Memory (per instance, fp64, all in HBM; sizes for N=80, 3 obstacles / 5 rows in brackets):
 //   prob  header+rx,ry,ryaw   [495]      z, zn  primal-dual iterate and the line search's
 //   trial point (they swap) [6797 each]      d  stage part of the search direction [~650 used]
@@ -470,13 +471,21 @@ struct HybridBufs {
     int slots = 0, max_nodes = 0, max_chunks = 0;      // as configured (0 = default)
     char *slotmem = nullptr; size_t slot_bytes = 0; int nslots = 0, ncell = 0, nodes = 0, chunks = 0;
     char *io = nullptr; size_t io_bytes = 0;
-    EventPair ev[2]; int lds_set[2] = {0, 0};      // [0]: obca_hybrid_astar_batch, [1]: obca_scene_astar_batch
+    EventPair ev[2]; int lds_set[2] = {0, 0};      // [0]: obca_hybrid_astar_batch, [1]: obca_scene_astar_batch (obca_batch_plan_warm_start launches [1]'s kernel between events of its batch)
+    unsigned long long serial = 0;                 // counts the calls that have taken the staging block: what a call left in it is there while the number stands
+    int slot_allocs = 0, io_allocs = 0;            // how often the slots / the staging block have been allocated (obca_batch_packed_block reports them: a call that fits reuses both)
     void release() {
         if (slotmem) (void)hipFree(slotmem);
         if (io) (void)hipFree(io);
         ev[0].release(); ev[1].release();
-        slotmem = io = nullptr; slot_bytes = io_bytes = 0; nslots = 0;
+        slotmem = io = nullptr; slot_bytes = io_bytes = 0; nslots = 0; serial++;
     }
+};
+// obca_batch_plan_warm_start on a batch (include/obca_plan_resident.h): the events around its three kernels -- packing, search, warm start -- and where the call left its
+// instance records and paths in the planner's staging block (`serial`: HybridBufs' when the call took the block; 0: no call yet)
+struct PlanRun {
+    EventPair ev[3]; unsigned long long serial = 0; int cap = 0, B = 0, nObMax = 0, MMax = 0; size_t o_inst = 0, o_paths = 0, o_dirs = 0;      // nObMax, MMax: the strides of the packed block at o_inst
+    void release() { for (EventPair &e : ev) e.release(); serial = 0; }
 };
 }  // namespace
 
@@ -528,6 +537,10 @@ struct obca_batch : BatchCore {
     KernelStage pw;       // obca_batch_set_path_warm_start
     KernelStage rf;       // obca_batch_refine_into, this batch the destination: selection and status on the device, the events around the kernel
     std::vector<int> vmx;                                   // per instance: most rows of one of its obstacles (a refined selection takes its own row class along)
+    // ego, L and XYbounds as obca_batch_upload was given them (the record holds what the solve derives from them): the planner's parameter block is made from these
+    // (obca_batch_plan_warm_start).  have_geo: an upload has set them -- a batch that obca_batch_refine_into filled has none
+    double ego[4] = {0, 0, 0, 0}, XYb[4] = {0, 0, 0, 0}, L = 0; int have_geo = 0;
+    PlanRun plan;         // obca_batch_plan_warm_start
 };
 
 #define HIPCHK(bt, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (bt)->err = std::string(#call) + ": " + hipGetErrorString(e_); return -2; } } while (0)
@@ -801,6 +814,8 @@ static int batch_upload_range(obca_batch *bt, const ParkIn &in, int lo, int n) {
         }
     }
     bt->have_duals = duals ? 1 : 0; bt->fixTime = in.fixTime ? 1 : 0;
+    for (int q = 0; q < 4; q++) { bt->ego[q] = ego[q]; bt->XYb[q] = XYb[q]; }
+    bt->L = in.L; bt->have_geo = 1;
     HIPCHK(bt, hipMemcpyAsync(d.prob, bt->h_prob, (size_t)n * d.s_prob * sizeof(double), hipMemcpyHostToDevice, bt->stream));
     HIPCHK(bt, hipMemcpyAsync(bt->stage, bt->h_zin, (size_t)n * W * sizeof(double), hipMemcpyHostToDevice, bt->stream));
     hipLaunchKernelGGL(obca_scatter_rows_kernel, dim3(n, (unsigned)((d.s_z + 1023) / 1024)), dim3(256), 0, bt->stream, d.z0, d.s_z, (const double *)bt->stage, W, d.s_z);
@@ -1093,7 +1108,7 @@ int obca_batch_create(obca_ctx *ctx, int B, int N, obca_batch **out) {
 int obca_batch_destroy(obca_batch *bt) {
     if (!bt) return -1;
     use_device(bt->device);
-    free_dev(bt); core_release(bt); (void)hipEventDestroy(bt->e2); bt->h_zin.release(); bt->h_zout.release(); bt->pw.release(); bt->rf.release();
+    free_dev(bt); core_release(bt); (void)hipEventDestroy(bt->e2); bt->h_zin.release(); bt->h_zout.release(); bt->pw.release(); bt->rf.release(); bt->plan.release();
     delete bt; return 0;
 }
 #ifdef OBCA_PROFILE
@@ -1371,7 +1386,7 @@ int obca_batch_refine_into(obca_batch *dst, obca_batch *src, int factor, int dua
             dst->rowLen.insert(dst->rowLen.end(), rl, rl + src->M[i]);
             nObMax = std::max(nObMax, dst->nOb[j]); MMax = std::max(MMax, dst->M[j]); dst->vmax = std::max(dst->vmax, dst->vmx[j]);
         }
-        dst->dist = src->dist; dst->fixTime = src->fixTime; dst->have_duals = duals;
+        dst->dist = src->dist; dst->fixTime = src->fixTime; dst->have_duals = duals; dst->have_geo = 0;
         return batch_reserve_shape(dst, nObMax, MMax);
     }, [&](const int *dsel, int *dstatus) {
         hipLaunchKernelGGL(obca_refine_batch_kernel, dim3(n), dim3(OB_NT), 0, dst->stream, n, src->N, factor, duals, dsel, src->d, dst->d, dstatus);
@@ -1720,6 +1735,10 @@ int obca_quadcopter_subdivide_batch(obca_ctx *ctx, int B, int N, int factor, con
    include to the end of the translation unit, and no other kernel may be compiled under that. */
 #include "obca_hybrid.h"
 #include "../../include/obca_plan_device.h"
+// the resident route's packing (its kernel is defined in the header): behind the planner's text, whose names it uses and under whose contraction rule it is compiled
+#include "obca_plan_resident.h"
+#include "../../include/obca_plan_resident.h"
+#include "../../include/obca_plan_resident_check.h"
 
 // the parking planner (obca_hybrid.h): `slots` persistent workgroups, workgroup s runs the searches s, s + slots, ... in its slot of the planner's memory.  LDS: the
 // holonomic map (nmap floats, padded to an even count), then the bucket heads and control words.
@@ -1743,6 +1762,55 @@ __global__ __launch_bounds__(HY_NT) void obca_hybrid_kernel(int B, int slots, co
 // (include/obca_plan_scenes.h).  The two entry points share the slots and the staging block; each has its own events and its own instantiation of the kernel.
 #define OBCA_HYBRID_BUDGET ((size_t)16 << 30)      // bytes the slots take by default
 static inline size_t up8(size_t n) { return (n + 7) / 8 * 8; }
+// The device side of a call of B searches with the parameter block P, shared by the host-pointer entry points (hybrid_call) and the resident route
+// (obca_batch_plan_warm_start): the slots, the staging block [ n_in bytes of input: Params | inst B x 10 | field data | paths | dirs | counts expansions rounds ] and the LDS
+// attribute of `kernel` (`own`: its index).  The context's device is selected.  hybrid_launch then launches the kernel over that block.
+struct HybridRun {
+    int B, cap, slots, lds; size_t sb, o_inst, o_paths, o_dirs, o_cnt; char *d;
+    int *counts() const { return (int *)(d + o_cnt); }
+};
+static int hybrid_reserve(obca_ctx *ctx, const char *entry, int own, decltype(&obca_hybrid_kernel<false>) kernel, int B, int cap, const hy::Params &P, int mn, int mc, size_t n_in, HybridRun &r) {
+    HybridBufs &h = ctx->hyb;
+    auto fail = [&](const char *what) { ctx->err = std::string(entry) + ": " + what; h.release(); return -2; };
+    // the slots: as many as configured, else what the budget holds, never more than searches
+    const size_t sb = hy::slot_bytes(P.ncell, mn, mc);
+    int slots = h.slots ? h.slots : (int)std::min<size_t>(OBCA_HYBRID_MAXSLOTS, std::max<size_t>(1, OBCA_HYBRID_BUDGET / sb));
+    slots = std::min(slots, B);
+    if (!h.slotmem || h.nslots < slots || h.ncell != P.ncell || h.nodes != mn || h.chunks != mc) {
+        if (h.slotmem) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.slotmem); h.slotmem = nullptr; h.nslots = 0; }
+        if (hipMalloc((void **)&h.slotmem, sb * slots) != hipSuccess) { h.slotmem = nullptr; ctx->err = std::string(entry) + ": hipMalloc of the slots failed (fewer slots or nodes: obca_hybrid_configure)"; return -2; }
+        h.slot_bytes = sb; h.nslots = slots; h.ncell = P.ncell; h.nodes = mn; h.chunks = mc; h.slot_allocs++;
+        bool ok = true;      // claim words and cell table: all ones; a search leaves them so
+        for (int s = 0; s < slots && ok; s++) ok = hipMemsetAsync(h.slotmem + (size_t)s * sb, 0xFF, hy::slot_init_bytes(P.ncell), ctx->stream) == hipSuccess;
+        if (!ok) return fail("hipMemsetAsync failed");
+    }
+    r.B = B; r.cap = cap; r.slots = slots; r.sb = sb;
+    r.o_inst = up8(sizeof(hy::Params));
+    r.o_paths = n_in; r.o_dirs = r.o_paths + (size_t)B * cap * 24; r.o_cnt = r.o_dirs + up8((size_t)B * cap * 4);
+    const size_t n_all = r.o_cnt + up8((size_t)3 * B * 4);
+    h.serial++;      // whatever an earlier call left in the block is gone from here on
+    if (h.io_bytes < n_all) {
+        if (h.io) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.io); h.io = nullptr; h.io_bytes = 0; }
+        if (hipMalloc((void **)&h.io, n_all) != hipSuccess) { h.io = nullptr; return fail("hipMalloc failed"); }
+        h.io_bytes = n_all; h.io_allocs++;
+    }
+    r.d = h.io;
+    r.lds = (((P.nmap + 1) & ~1) + HY_LDS_INTS) * (int)sizeof(float);
+    if (r.lds > h.lds_set[own]) {
+        if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, r.lds) != hipSuccess) return fail("hipFuncSetAttribute failed");
+        h.lds_set[own] = r.lds;
+    }
+    return 0;
+}
+static void hybrid_launch(obca_ctx *ctx, decltype(&obca_hybrid_kernel<false>) kernel, const HybridRun &r, const hy::Field &F, const hy::Fields &S, const unsigned char *blocked) {
+    int *dcnt = r.counts();
+    hipLaunchKernelGGL(kernel, dim3(r.slots), dim3(HY_NT), r.lds, ctx->stream, r.B, r.slots, (const hy::Params *)r.d, F, S, blocked, (const double *)(r.d + r.o_inst),
+                       ctx->hyb.slotmem, r.sb, (double *)(r.d + r.o_paths), (int *)(r.d + r.o_dirs), dcnt, dcnt + r.B, dcnt + 2 * r.B);
+}
+static inline void hybrid_sizes(const obca_ctx *ctx, int &mn, int &mc) {
+    mn = ctx->hyb.max_nodes ? ctx->hyb.max_nodes : OBCA_HYBRID_MAXNODES; mc = ctx->hyb.max_chunks ? ctx->hyb.max_chunks : hy::default_chunks(mn);
+}
+
 // What both entry points do around their own validation and packing.  One block travels up: [ Params | inst B x 10 | the entry's field data ].  make(mn, mc, P, inst, up, o_fld)
 // checks the arguments (a text refuses the call), fills P and inst and sizes `up` to hold its field data from byte o_fld on; bind(d, F, S) then builds the device-side Field
 // (shared field; it returns the blocked map) or Fields (per-instance fields) over that data at `d` on the device.  One block comes down: [ paths | dirs | counts | expansions | rounds ].
@@ -1752,49 +1820,25 @@ template <typename Make, typename Bind>
 static int hybrid_call(obca_ctx *ctx, const char *entry, int own, decltype(&obca_hybrid_kernel<false>) kernel, int B, double *paths, int *dirs, int cap, int *counts, int *expansions, int *rounds, Make &&make, Bind &&bind) {
     if (!ctx) return -1;
     HybridBufs &h = ctx->hyb; EventPair &ev = h.ev[own];
-    const int mn = h.max_nodes ? h.max_nodes : OBCA_HYBRID_MAXNODES, mc = h.max_chunks ? h.max_chunks : hy::default_chunks(mn);
+    int mn, mc; hybrid_sizes(ctx, mn, mc);
     hy::Params P; std::vector<double> inst; std::vector<char> up;
     const size_t o_inst = up8(sizeof(hy::Params)), o_fld = o_inst + (size_t)std::max(B, 0) * 10 * 8;
     const std::string bad = (paths && dirs && counts) ? make(mn, mc, P, inst, up, o_fld) : std::string("NULL output array");
     if (!bad.empty()) { ctx->err = std::string(entry) + ": " + bad; return -1; }
-    auto fail = [&](const char *what) { ctx->err = std::string(entry) + ": " + what; h.release(); return -2; };
     use_device(ctx->device);
     if (int rc = ev.ensure(ctx->err)) return rc;
     ev.timed = 0;
-    // the slots: as many as configured, else what the budget holds, never more than searches
-    const size_t sb = hy::slot_bytes(P.ncell, mn, mc);
-    int slots = h.slots ? h.slots : (int)std::min<size_t>(OBCA_HYBRID_MAXSLOTS, std::max<size_t>(1, OBCA_HYBRID_BUDGET / sb));
-    slots = std::min(slots, B);
-    if (!h.slotmem || h.nslots < slots || h.ncell != P.ncell || h.nodes != mn || h.chunks != mc) {
-        if (h.slotmem) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.slotmem); h.slotmem = nullptr; h.nslots = 0; }
-        if (hipMalloc((void **)&h.slotmem, sb * slots) != hipSuccess) { h.slotmem = nullptr; ctx->err = std::string(entry) + ": hipMalloc of the slots failed (fewer slots or nodes: obca_hybrid_configure)"; return -2; }
-        h.slot_bytes = sb; h.nslots = slots; h.ncell = P.ncell; h.nodes = mn; h.chunks = mc;
-        bool ok = true;      // claim words and cell table: all ones; a search leaves them so
-        for (int s = 0; s < slots && ok; s++) ok = hipMemsetAsync(h.slotmem + (size_t)s * sb, 0xFF, hy::slot_init_bytes(P.ncell), ctx->stream) == hipSuccess;
-        if (!ok) return fail("hipMemsetAsync failed");
-    }
-    const size_t n_in = up.size(), o_paths = n_in, o_dirs = o_paths + (size_t)B * cap * 24, o_cnt = o_dirs + up8((size_t)B * cap * 4), n_all = o_cnt + up8((size_t)3 * B * 4);
-    if (h.io_bytes < n_all) {
-        if (h.io) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.io); h.io = nullptr; h.io_bytes = 0; }
-        if (hipMalloc((void **)&h.io, n_all) != hipSuccess) { h.io = nullptr; return fail("hipMalloc failed"); }
-        h.io_bytes = n_all;
-    }
+    const size_t n_in = up.size();
+    HybridRun r;
+    if (int rc = hybrid_reserve(ctx, entry, own, kernel, B, cap, P, mn, mc, n_in, r)) return rc;
     memcpy(up.data(), &P, sizeof P); memcpy(up.data() + o_inst, inst.data(), inst.size() * 8);
-    char *d = h.io;
+    char *d = r.d;
     hy::Field F = hy::Field(); hy::Fields S = hy::Fields();
     const unsigned char *blocked = bind(d + o_fld, F, S);
-    const int lds = (((P.nmap + 1) & ~1) + HY_LDS_INTS) * (int)sizeof(float);
-    if (lds > h.lds_set[own]) {
-        if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return fail("hipFuncSetAttribute failed");
-        h.lds_set[own] = lds;
-    }
-    int *dcnt = (int *)(d + o_cnt);
     int *tail = (int *)up.data();      // once `up` has travelled, its head (Params and inst: more than 3 B ints) takes the three count arrays on the way back
-    const bool sent =hipMemcpyAsync(d, up.data(), n_in, hipMemcpyHostToDevice, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;      // (`up` is pageable)
-    const int rc = launch_timed(ctx->err, entry, ctx->stream, ev, sent, [&] {
-        hipLaunchKernelGGL(kernel, dim3(slots), dim3(HY_NT), lds, ctx->stream, B, slots, (const hy::Params *)d, F, S, blocked, (const double *)(d + o_inst),
-                           h.slotmem, sb, (double *)(d + o_paths), (int *)(d + o_dirs), dcnt, dcnt + B, dcnt + 2 * B);
-    }, {{paths, d + o_paths, (size_t)B * cap * 24}, {dirs, d + o_dirs, (size_t)B * cap * 4}, {tail, dcnt, (size_t)3 * B * 4}});
+    const bool sent = hipMemcpyAsync(d, up.data(), n_in, hipMemcpyHostToDevice, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;      // (`up` is pageable)
+    const int rc = launch_timed(ctx->err, entry, ctx->stream, ev, sent, [&] { hybrid_launch(ctx, kernel, r, F, S, blocked); },
+                                {{paths, d + r.o_paths, (size_t)B * cap * 24}, {dirs, d + r.o_dirs, (size_t)B * cap * 4}, {tail, r.counts(), (size_t)3 * B * 4}});
     if (rc) { h.release(); return rc; }
     for (int i = 0; i < B; i++) { counts[i] = tail[i]; if (expansions) expansions[i] = tail[B + i]; if (rounds) rounds[i] = tail[2 * B + i]; }
     return 0;
@@ -1878,6 +1922,96 @@ int obca_scene_astar_batch(obca_ctx *ctx, int B, const double *starts, const dou
 
 int obca_scene_astar_ms(obca_ctx *ctx, float *ms) {
     return ctx && ms ? core_elapsed_ms(ctx, ctx->hyb.ev[1], ms, "obca_scene_astar_ms: no per-instance search has run on this context") : -1;
+}
+
+// ---- the resident route (obca_plan_resident.h, include/obca_plan_resident.h): packing -> the per-instance search -> the warm start, all three reading and writing device
+// memory, on the batch's stream (the context's: the batch is one of the primary device).  The staging block's input part holds [ Params | inst | the packed fields
+// (plr::Layout) | status B ]: only Params travels up, only counts, expansions, rounds and status come down.
+int obca_batch_plan_warm_start(obca_batch *bt, const double *opts, int nopts, double bucket_width, int cap, int use_xF, double v_nom, double a_max,
+                               int *counts, int *status, int *expansions, int *rounds) {
+    if (!bt) return -1;
+    obca_ctx *ctx = bt->ctx;
+    const char *entry = "obca_batch_plan_warm_start";
+    auto refuse = [&](const std::string &what) { ctx->err = std::string(entry) + ": " + what; return -1; };
+    if (!counts || !status) return refuse("NULL counts or status");
+    if (cap < 2 || cap > OBCA_PATH_WS_MAXNODES) return refuse("need 2 <= cap <= OBCA_PATH_WS_MAXNODES");
+    if (!bt->uploaded || !bt->have_geo) return refuse("nothing uploaded by obca_batch_upload (a batch that obca_batch_refine_into filled starts from a solution)");
+    if (bt->device != ctx->device || bt->stream != ctx->stream) return refuse("the batch is not one of its context's primary device");
+    if (const char *bad = pw::path_ws_check_args(bt->B, bt->N, cap, v_nom, 1.0, a_max, true)) return refuse(bad);
+    const int B = bt->B;
+    if ((double)B * bt->nObMax * PLR_NV > 2e9 || (double)B * bt->MMax > 2e9) return refuse("the batch is too large for the planner's 32-bit offsets");
+    // the parameter block: make_params with no field and no poses of the caller's (one pose at the origin: P depends on neither), as make_scenes calls it
+    int mn, mc; hybrid_sizes(ctx, mn, mc);
+    hy::Params P; hy::HostField none; std::vector<unsigned char> free_map; std::vector<double> pose;
+    const double origin[3] = {0.0, 0.0, 0.0};
+    if (const char *bad = hy::make_params(1, origin, origin, 0, nullptr, nullptr, nullptr, bt->ego, bt->L, bt->XYb, opts, nopts, bucket_width, cap, mn, mc, P, none, free_map, pose)) return refuse(bad);
+    use_device(bt->device);
+    PlanRun &pr = bt->plan;
+    for (EventPair &e : pr.ev) { if (int rc = e.ensure(ctx->err)) return rc; e.timed = 0; }
+    pr.serial = 0;
+    const plr::Layout lay = plr::layout(B, bt->nObMax, bt->MMax);
+    const size_t o_st = up8(sizeof(hy::Params)) + lay.bytes;
+    HybridRun r;
+    if (int rc = hybrid_reserve(ctx, entry, 1, obca_hybrid_kernel<true>, B, cap, P, mn, mc, o_st + up8((size_t)B * 4), r)) return rc;
+    const plr::Block blk = plr::block_at(r.d + r.o_inst, lay);      // (inst first: where hybrid_launch points the search's instance records)
+    int *dst = (int *)(r.d + o_st);
+    const double far_ = hy::host_far(bt->XYb);
+    // from here on the record and the start iterate may be rewritten, whatever becomes of the call (obca_batch_set_path_warm_start)
+    bt->solved = 0; bt->have_duals = 0;
+    static_assert(sizeof P == 1288, "tools/plan_resident_rate.py records this size as what the call sends up");
+    const bool sent = hipMemcpyAsync(r.d, &P, sizeof P, hipMemcpyHostToDevice, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;      // (P is pageable)
+    std::vector<int> down((size_t)4 * B);
+    int rc = launch_timed(ctx->err, entry, ctx->stream, pr.ev[0], sent, [&] {
+        hipLaunchKernelGGL(plr::obca_plan_pack_kernel, dim3(B), dim3(PLR_NT), 0, ctx->stream, B, bt->nObMax, bt->MMax, far_, (const double *)bt->d.prob, bt->d.s_prob, blk);
+    }, {});
+    if (!rc) rc = launch_timed(ctx->err, entry, ctx->stream, pr.ev[1], true, [&] { hybrid_launch(ctx, obca_hybrid_kernel<true>, r, hy::Field(), plr::fields_of(blk), nullptr); }, {});
+    if (!rc) rc = launch_timed(ctx->err, entry, ctx->stream, pr.ev[2], true, [&] {
+        hipLaunchKernelGGL(obca_path_ws_batch_kernel, dim3(B), dim3(OB_NT), 0, ctx->stream, B, bt->N, (const double *)(r.d + r.o_paths), (const int *)(r.d + r.o_dirs), (const int *)r.counts(),
+                           cap, cap, use_xF ? 1 : 0, v_nom, a_max, bt->d, dst);
+    }, {{down.data(), r.counts(), (size_t)3 * B * sizeof(int)}, {down.data() + (size_t)3 * B, dst, (size_t)B * sizeof(int)}});
+    if (rc) { ctx->hyb.release(); return rc; }
+    for (int i = 0; i < B; i++) { counts[i] = down[i]; if (expansions) expansions[i] = down[B + i]; if (rounds) rounds[i] = down[2 * B + i]; status[i] = down[(size_t)3 * B + i]; }
+    pr.serial = ctx->hyb.serial; pr.cap = cap; pr.B = B; pr.nObMax = bt->nObMax; pr.MMax = bt->MMax; pr.o_inst = r.o_inst; pr.o_paths = r.o_paths; pr.o_dirs = r.o_dirs;
+    return 0;
+}
+
+int obca_batch_plan_ms(obca_batch *bt, float *pack_ms, float *search_ms, float *ws_ms) {
+    if (!bt || !pack_ms || !search_ms || !ws_ms) return -1;
+    float *out[3] = {pack_ms, search_ms, ws_ms};
+    for (int k = 0; k < 3; k++) if (int rc = core_elapsed_ms(bt->ctx, bt->plan.ev[k], out[k], "obca_batch_plan_ms: no plan call has run on this batch")) return rc;
+    return 0;
+}
+
+int obca_batch_plan_download(obca_batch *bt, double *paths, int *dirs, int cap, double *inst) {
+    if (!bt) return -1;
+    obca_ctx *ctx = bt->ctx; const PlanRun &pr = bt->plan; const HybridBufs &h = ctx->hyb;
+    if (!pr.serial || pr.serial != h.serial || !h.io) { ctx->err = "obca_batch_plan_download: no plan of this batch is in the planner's staging block (none has run, or a later planner call of the context took it)"; return -1; }
+    if (!paths && !dirs && !inst) return pr.cap;      // the query: how many rows the arrays of a download need
+    if (cap != pr.cap) { ctx->err = "obca_batch_plan_download: cap is not the last call's"; return -1; }
+    use_device(bt->device);
+    const size_t B = pr.B;
+    bool ok = true;
+    if (paths) ok = ok && hipMemcpyAsync(paths, h.io + pr.o_paths, B * cap * 24, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    if (dirs) ok = ok && hipMemcpyAsync(dirs, h.io + pr.o_dirs, B * cap * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    if (inst) ok = ok && hipMemcpyAsync(inst, h.io + pr.o_inst, B * 80, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess || !ok) { ctx->err = "obca_batch_plan_download: copy failed"; return -2; }
+    return 0;
+}
+
+// the diagnostic of include/obca_plan_resident_check.h: the block the packing kernel of the last obca_batch_plan_warm_start wrote, as it lies on the device
+int obca_batch_packed_block(obca_batch *bt, double *block, int ndoubles, int *dims) {
+    if (!bt) return -1;
+    obca_ctx *ctx = bt->ctx; const PlanRun &pr = bt->plan; const HybridBufs &h = ctx->hyb;
+    if (!dims) { ctx->err = "obca_batch_packed_block: NULL dims"; return -1; }
+    if (!pr.serial || pr.serial != h.serial || !h.io) { ctx->err = "obca_batch_packed_block: no plan of this batch is in the planner's staging block (none has run, or a later planner call of the context took it)"; return -1; }
+    const size_t need = plr::layout(pr.B, pr.nObMax, pr.MMax).bytes / 8;
+    if (need > 2000000000u) { ctx->err = "obca_batch_packed_block: the block is too large for this call"; return -1; }
+    dims[0] = pr.B; dims[1] = pr.nObMax; dims[2] = pr.MMax; dims[3] = (int)need; dims[4] = h.slot_allocs; dims[5] = h.io_allocs;
+    if (!block) return 0;
+    if ((size_t)std::max(ndoubles, 0) < need) { ctx->err = "obca_batch_packed_block: the array is shorter than dims[3] doubles"; return -1; }
+    use_device(bt->device);
+    if (hipMemcpyAsync(block, h.io + pr.o_inst, need * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "obca_batch_packed_block: copy failed"; return -2; }
+    return 0;
 }
 
 }  // extern "C"
