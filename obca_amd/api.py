@@ -19,7 +19,7 @@ import numbers
 import os
 import time
 import numpy as np
-from . import buildflags, cabi
+from . import buildflags, cabi, planner
 from .cabi import Opts      # `typedef struct obca_opts` of include/obca_hip.h, read from the header
 from .validate import VIOL_NAMES, QUAD_VIOL_NAMES, DMIN, CLR_OUT
 
@@ -60,6 +60,7 @@ def _load():
     cabi.bind(_lib, "obca_plan_scenes.h")                 # ... in per-instance obstacle fields
     cabi.bind(_lib, "obca_plan_resident.h")               # ... from the records of an uploaded batch
     cabi.bind(_lib, "obca_plan_resident_check.h")         # ... and the diagnostic that hands out what its packing kernel wrote
+    cabi.bind(_lib, "obca_quad_plan_resident.h")          # the quadcopter's grid planner from the records of an uploaded batch
     return _lib
 
 
@@ -94,6 +95,12 @@ SCENE_EXPORTS = ["obca_scene_astar_batch", "obca_scene_astar_ms"]
 # include/obca_plan_resident.h: the same search from what an uploaded batch holds, its paths straight into the batch's warm start (Batch.plan_warm_start, plan_ms, plan_paths)
 PLAN_RESIDENT_EXPORTS = ["obca_batch_plan_warm_start", "obca_batch_plan_ms", "obca_batch_plan_download"]
 PLAN_RESIDENT_CHECK_EXPORTS = ["obca_batch_packed_block"]      # include/obca_plan_resident_check.h: a diagnostic (Batch.plan_block)
+# include/obca_quad_plan_resident.h: the quadcopter's 3-D grid search from what an uploaded batch holds, its resampled path straight into the batch's warm start
+# (QuadBatch.plan_warm_start, plan_ms, plan_paths), and the read-back of the start a batch will solve from (QuadBatch.warm_start)
+QUAD_PLAN_RESIDENT_EXPORTS = ["obca_quad_batch_grid_plan_warm_start", "obca_quad_batch_grid_plan_ms", "obca_quad_batch_grid_plan_download", "obca_quad_batch_start_download"]
+QUAD_PLAN_SKIPPED = -4      # OBCA_QUAD_PLAN_SKIPPED
+QUAD_PLAN_STATUS = {0: "no path", -1: "more way-points than cap", -2: "the start or goal point is blocked, or a coordinate of the record is not finite",
+                    -3: "the relaxation hit its sweep bound", -4: "not selected"}
 QUAD_REFINE_STATUS = {0: "refined from the solution", 1: "interpolated from the uploaded warm start (the last solve failed, or its iterate is not finite)",
                       -1: "zero warm start (the uploaded one is not finite either)"}
 REFINE_STATUS = {0: "refined from the solution", 1: "refined from the start iterate (the last solve failed, or its iterate is not finite)", -1: "zero start (the start iterate is not finite either)"}
@@ -779,6 +786,49 @@ class QuadBatch(_DeviceBatch):
         timeWS = the last t, closed-form duals --, from x0_new (B,12; the measured state; None: stage `shift` of the solution) towards xF_new (B,12; a moving goal; None: unchanged).
         An instance whose last solve failed keeps its uploaded warm start.  Solve with quad_warm_restart_opts()."""
         self._call("shift_warm_start", int(shift), *(_in(np.reshape(a, (self.B, 12))) if a is not None else None for a in (x0_new, xF_new)))
+
+    def plan_warm_start(self, clear=0.4, room=planner.QUAD_ROOM, res=0.25, cap=planner.PLAN3D_WS_CAP, select=None, timeWS=None):
+        """The resident route (obca_quad_batch_grid_plan_warm_start): the instances `select` (an index array without duplicates or a boolean mask over the batch; None: all)
+        are planned ON THE DEVICE from the x0, xF and boxes the upload left there -- planner.quad_warm_start_many's search, one workgroup per instance, the defaults
+        (planner.QUAD_ROOM, planner.PLAN3D_WS_CAP) its own -- and the path, resampled at N + 1 uniform arc lengths, becomes the instance's warm start (rows 3-11 zero).
+        timeWS: None (every instance keeps its time scale) or one number > 0 for the planned instances.  Returns (counts, sweeps), (B,) int32 each: counts as
+        planner.plan3d_paths (QUAD_PLAN_STATUS: >= 2 way-points, 0, -1, -2, -3) and -4 for an instance that was not selected; an instance with a count below 2 keeps
+        its uploaded record to the last bit.  The batch counts as unsolved afterwards."""
+        if select is None:
+            sel, n = None, 0
+        else:
+            sel = np.asarray(select)
+            sel = np.flatnonzero(sel).astype(np.int32) if sel.dtype == bool else np.ascontiguousarray(sel, np.int32).ravel()
+            n = int(sel.size)
+            if n < 1:
+                raise ObcaError("plan_warm_start: the selection is empty")
+        cnt = np.zeros(self.B, np.int32); sw = np.zeros(self.B, np.int32)
+        self._call("grid_plan_warm_start", float(clear), np.ascontiguousarray(room, float), float(res), int(cap), sel, n,
+                   None if timeWS is None else np.array([timeWS], float), cnt, sw)
+        return cnt, sw
+
+    def plan_ms(self):
+        """HIP-event duration of the last plan_warm_start's kernel [ms]"""
+        a = C.c_float(0)
+        self._call("grid_plan_ms", C.byref(a))
+        return a.value
+
+    def plan_paths(self):
+        """The way-points of the last plan_warm_start, for plots and tests: (B, cap, 3) -- start point, grid nodes, goal point; the rows behind an instance's count, and all
+        rows of an instance the call skipped, are zero."""
+        cap = _load().obca_quad_batch_grid_plan_download(self._h, None, 0)      # (no array: the call answers with the last plan's cap)
+        if cap < 2:
+            self.ctx._check(cap, "obca_quad_batch_grid_plan_download")
+        paths = np.zeros((self.B, cap, 3))
+        self._call("grid_plan_download", paths, cap)
+        return paths
+
+    def warm_start(self):
+        """The start the next solve begins from, read from the records on the device (obca_quad_batch_start_download): (xWS (B, N+1, 12), timeWS (B,)).  Works on every
+        uploaded batch: after upload, plan_warm_start, shift_warm_start, and on the batch refine() returned."""
+        xws = np.zeros((self.B, self.N + 1, 12)); tws = np.zeros(self.B)
+        self._call("start_download", xws, tws)
+        return xws, tws
 
     def kernel_ms(self):
         a = C.c_float(0)

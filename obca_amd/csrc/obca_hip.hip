@@ -11,6 +11,8 @@
 //   obca_quad_subdivide_*_kernel : the same for a solved quadcopter instance (obca_quad_subdivide.h): it rewrites a problem record.
 //   obca_path_ws_*_kernel   : one wavefront per instance, the parking warm start from a planner path (obca_path_ws.h): into host-bound arrays or into a resident batch.
 //   obca_plan_pack_kernel   : one wavefront per instance, the planner's obstacle field and poses from the problem record of a resident batch (obca_plan_resident.h).
+//   obca_quad_plan_resident_kernel : one workgroup per selected instance, the quadcopter's 3-D grid search from the problem record of a resident batch, the resampled path
+//                             written into the record's warm start (obca_quad_plan_resident.h over obca_plan3d.h).
 //   obca_shift_kernel, obca_quad_shift_kernel : receding-horizon restarts, one workgroup per instance: the warm start of the next solve from the last solution
 //                             (parking: below; quadcopter: obca_quad_shift.h).
 // Host helpers the entry points are built from (below "host side"): EventPair, KernelStage (staging types); run_validate, launch_timed (a kernel between two events, results down);
@@ -497,6 +499,7 @@ struct obca_ctx {
     KernelStage rf;                         // the same set for obca_parking_refine_batch
     KernelStage qsd;                        // and for obca_quadcopter_subdivide_batch
     HybridBufs hyb;                         // the planner's slots and staging (obca_hybrid_astar_batch, obca_scene_astar_batch) and its configuration (obca_hybrid_configure)
+    int gp_lds = 0;                         // the dynamic LDS obca_quad_plan_resident_kernel has been given on the primary device (obca_quad_batch_grid_plan_warm_start)
 };
 static std::string g_create_err;
 
@@ -521,6 +524,8 @@ struct obca_quad_batch : BatchCore {
     QDevBufs d = {};
     PinnedBuf h_z;
     KernelStage sd;       // obca_quad_batch_subdivide_into, this batch the destination: selection and status on the device, the events around the kernel
+    KernelStage gp;       // obca_quad_batch_grid_plan_warm_start: selection, counts and sweeps on the device, the events around the kernel
+    DevBuf gp_paths; int gp_cap = 0;      // ... and its way-points, B x gp_cap x 3, allocated at the first call and kept with the batch (gp_cap: the last call's cap, 0 before)
 };
 struct obca_batch : BatchCore {
     using BatchCore::BatchCore;
@@ -1516,7 +1521,7 @@ int obca_quad_batch_create(obca_ctx *ctx, int B, int N, obca_quad_batch **out) {
 int obca_quad_batch_destroy(obca_quad_batch *bt) {
     if (!bt) return -1;
     use_device(bt->device);
-    free_dev(bt); core_release(bt); bt->h_z.release(); bt->sd.release();
+    free_dev(bt); core_release(bt); bt->h_z.release(); bt->sd.release(); bt->gp.release(); bt->gp_paths.release();
     delete bt; return 0;
 }
 #ifdef OBCA_PROFILE
@@ -1739,6 +1744,9 @@ int obca_quadcopter_subdivide_batch(obca_ctx *ctx, int B, int N, int factor, con
 #include "obca_plan_resident.h"
 #include "../../include/obca_plan_resident.h"
 #include "../../include/obca_plan_resident_check.h"
+// the quadcopter's resident route (its kernel is defined in the header, over obca_plan3d.h): here because obca_plan3d.h switches contraction off at file scope too
+#include "obca_quad_plan_resident.h"
+#include "../../include/obca_quad_plan_resident.h"
 
 // the parking planner (obca_hybrid.h): `slots` persistent workgroups, workgroup s runs the searches s, s + slots, ... in its slot of the planner's memory.  LDS: the
 // holonomic map (nmap floats, padded to an even count), then the bucket heads and control words.
@@ -2011,6 +2019,87 @@ int obca_batch_packed_block(obca_batch *bt, double *block, int ndoubles, int *di
     if ((size_t)std::max(ndoubles, 0) < need) { ctx->err = "obca_batch_packed_block: the array is shorter than dims[3] doubles"; return -1; }
     use_device(bt->device);
     if (hipMemcpyAsync(block, h.io + pr.o_inst, need * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "obca_batch_packed_block: copy failed"; return -2; }
+    return 0;
+}
+
+// ---- the quadcopter's resident route (obca_quad_plan_resident.h, include/obca_quad_plan_resident.h): the grid search from the records of an uploaded batch, on the batch's
+// stream.  The stage holds ints [ sel n | counts B | sweeps B ]: the selection, -4 in every count and 0 in every sweep go up in one copy, the kernel overwrites the words of
+// the instances it plans, counts and sweeps come down.
+int obca_quad_batch_grid_plan_warm_start(obca_quad_batch *bt, double clear, const double room[3], double res, int cap, const int *sel, int n, const double *timeWS, int *counts, int *sweeps) {
+    if (!bt) return -1;
+    obca_ctx *ctx = bt->ctx;
+    const char *entry = "obca_quad_batch_grid_plan_warm_start";
+    auto refuse = [&](const std::string &what) { ctx->err = std::string(entry) + ": " + what; return -1; };
+    const int B = bt->B;
+    int dims[3];
+    if (const char *bad = qpr::check_args(B, bt->N, clear, room, res, cap, sel, n, timeWS, counts, dims)) return refuse(bad);
+    if (!bt->uploaded) return refuse("nothing uploaded");
+    if (bt->device != ctx->device || bt->stream != ctx->stream) return refuse("the batch is not one of its context's primary device");
+    if (!sel) n = B;
+    use_device(bt->device);
+    KernelStage &w = bt->gp;
+    if (int rc = w.ev.ensure(bt->err)) return fin(bt, rc);
+    const size_t nints = (size_t)n + 2 * (size_t)B, npath = (size_t)B * cap * 3;
+    if (w.dev.reserve((nints + 1) / 2, bt->stream) != hipSuccess || bt->gp_paths.reserve(npath, bt->stream) != hipSuccess) { ctx->err = std::string(entry) + ": hipMalloc failed"; return -2; }
+    if (w.host.reserve(bt->err, (nints + 1) / 2)) return fin(bt, -2);
+    const int ncell = dims[0] * dims[1] * dims[2], lds = (ncell + 4) * (int)sizeof(float);
+    if (lds > ctx->gp_lds) {
+        if (hipFuncSetAttribute((const void *)qpr::obca_quad_plan_resident_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) { ctx->err = std::string(entry) + ": hipFuncSetAttribute failed"; return -2; }
+        ctx->gp_lds = lds;
+    }
+    int *hs = (int *)w.host.p, *dsel = (int *)w.dev.p, *dcnt = dsel + n, *dsw = dcnt + B;
+    for (int j = 0; j < n; j++) hs[j] = sel ? sel[j] : j;
+    for (int i = 0; i < B; i++) { hs[n + i] = OBCA_QUAD_PLAN_SKIPPED; hs[n + B + i] = 0; }
+    // from here on the records may be rewritten, whatever becomes of the call: the batch counts as unsolved, as after an upload
+    bt->solved = 0; bt->gp_cap = 0;
+    const bool up = hipMemcpyAsync(dsel, hs, nints * sizeof(int), hipMemcpyHostToDevice, bt->stream) == hipSuccess &&
+                    hipMemsetAsync(bt->gp_paths.p, 0, npath * sizeof(double), bt->stream) == hipSuccess;      // (the rows of a skipped instance read as zeros)
+    const QDevBufs &d = bt->d;
+    const int rc = launch_timed(ctx->err, entry, bt->stream, w.ev, up, [&] {
+        hipLaunchKernelGGL(qpr::obca_quad_plan_resident_kernel, dim3(n), dim3(PL3_NT), lds, bt->stream, (const int *)dsel, n, B, bt->N, d.prob, d.s_prob, clear, room[0], room[1], room[2], res,
+                           dims[0], dims[1], dims[2], bt->gp_paths.p, cap, dcnt, dsw, timeWS ? 1 : 0, timeWS ? *timeWS : 0.0);
+    }, {{hs + n, dcnt, (size_t)2 * B * sizeof(int)}});
+    if (rc) return rc;
+    memcpy(counts, hs + n, (size_t)B * sizeof(int));
+    if (sweeps) memcpy(sweeps, hs + n + B, (size_t)B * sizeof(int));
+    bt->gp_cap = cap;
+    return 0;
+}
+
+int obca_quad_batch_grid_plan_ms(obca_quad_batch *bt, float *ms) {
+    return bt && ms ? core_elapsed_ms(bt->ctx, bt->gp.ev, ms, "obca_quad_batch_grid_plan_ms: no plan call has run on this batch") : -1;
+}
+
+int obca_quad_batch_grid_plan_download(obca_quad_batch *bt, double *paths, int cap) {
+    if (!bt) return -1;
+    obca_ctx *ctx = bt->ctx;
+    if (bt->gp_cap < 2) { ctx->err = "obca_quad_batch_grid_plan_download: no plan call has run on this batch"; return -1; }
+    if (!paths) return bt->gp_cap;      // the query: how many rows per instance the array of a download needs
+    if (cap != bt->gp_cap) { ctx->err = "obca_quad_batch_grid_plan_download: cap is not the last call's"; return -1; }
+    use_device(bt->device);
+    if (hipMemcpyAsync(paths, bt->gp_paths.p, (size_t)bt->B * cap * 3 * sizeof(double), hipMemcpyDeviceToHost, bt->stream) != hipSuccess || hipStreamSynchronize(bt->stream) != hipSuccess) {
+        ctx->err = "obca_quad_batch_grid_plan_download: copy failed"; return -2;
+    }
+    return 0;
+}
+
+int obca_quad_batch_start_download(obca_quad_batch *bt, double *xWS, double *timeWS) {
+    if (!bt) return -1;
+    obca_ctx *ctx = bt->ctx;
+    if (!xWS && !timeWS) { ctx->err = "obca_quad_batch_start_download: NULL arguments"; return -1; }
+    if (!bt->uploaded) { ctx->err = "obca_quad_batch_start_download: nothing uploaded"; return -1; }
+    const QDevBufs &d = bt->d; const size_t B = bt->B, nws = (size_t)QX * (bt->N + 1);
+    use_device(bt->device);
+    // through the pinned problem staging of the batch (an upload refills it, the shift uses it as scratch the same way): the records as they lie
+    if (bt->h_prob.reserve(bt->err, (size_t)bt->cap * d.s_prob)) return fin(bt, -2);
+    if (hipMemcpyAsync(bt->h_prob, d.prob, B * d.s_prob * sizeof(double), hipMemcpyDeviceToHost, bt->stream) != hipSuccess || hipStreamSynchronize(bt->stream) != hipSuccess) {
+        ctx->err = "obca_quad_batch_start_download: copy failed"; return -2;
+    }
+    for (size_t i = 0; i < B; i++) {
+        const double *p = bt->h_prob + i * d.s_prob;
+        if (xWS) memcpy(xWS + i * nws, p + QPH_SIZE, nws * sizeof(double));
+        if (timeWS) timeWS[i] = p[QPH_TWS];
+    }
     return 0;
 }
 

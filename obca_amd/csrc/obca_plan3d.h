@@ -163,12 +163,12 @@ static int emu_reverse = 0;      // the host build visits the nodes of a sweep i
 #define PL3_BARRIER() __syncthreads()
 #endif
 
-// in: the instance's record (start, goal, boxes); lds: 4 control words (three vote words, the instance's count), then the field (G.ncell floats).
+// start, goal: 3 doubles each; boxes: 6 G.nBox doubles (obca_quad_plan_resident.h reads the three where a problem record holds them); lds: 4 control words (three vote
+// words, the instance's count), then the field (G.ncell floats).  The instance's count stays in the fourth control word for the caller.
 // path: cap x 3; count, sweeps: this instance's; N > 0 and xws != NULL: also the warm start, (N + 1) x 12.
-PL3_FN void plan_instance(const double *in, Grid G, float *lds, double *path, int cap, int *count, int *sweeps, int N, double *xws) {
+PL3_FN void plan_instance(const double *start, const double *goal, const double *boxes, Grid G, float *lds, double *path, int cap, int *count, int *sweeps, int N, double *xws) {
     int *ctl = (int *)lds; float *g = lds + 4;
-    const double *start = in, *goal = in + 3;
-    G.boxes = in + 6;
+    G.boxes = boxes;
     float w[4]; w[0] = 0.f; w[1] = edge_w(G.res, 1); w[2] = edge_w(G.res, 2); w[3] = edge_w(G.res, 3);
     int status = 1, nsweep = 0;
     if (blocked(G, start[0], start[1], start[2]) || blocked(G, goal[0], goal[1], goal[2])) status = -2;      // (every thread decides the same from the same numbers)
@@ -247,6 +247,10 @@ PL3_FN void plan_instance(const double *in, Grid G, float *lds, double *path, in
         }
     }
 #undef PL3_FOR_NODES
+}
+// in: the instance's record (start, goal, boxes) in one piece
+PL3_FN void plan_instance(const double *in, Grid G, float *lds, double *path, int cap, int *count, int *sweeps, int N, double *xws) {
+    plan_instance(in, in + 3, in + 6, G, lds, path, cap, count, sweeps, N, xws);
 }
 
 }  // namespace pl3
