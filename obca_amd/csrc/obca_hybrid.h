@@ -20,7 +20,10 @@
 // norms, obstacle vertices and edge weights come from the host.
 // Per-instance obstacle fields (include/obca_plan_scenes.h): the same search, called with the field of its own instance (field_of: a record of offsets into arrays that
 // hold the fields of the whole batch, make_fields) and without a blocked map -- it then finds the blocked cells itself while it initialises the map (cell_blocked: the
-// host's test with the row norm read from memory, so still no libm), 512 threads sharing the cells.  Nothing else of a search depends on which route called it.
+// disc test the host's map comes from, the row norm read from memory, so still no libm), 512 threads sharing the cells.  Nothing else of a search depends on which route
+// called it.
+// The collision test, the disc test, the polygons and the Reeds-Shepp curves are obca_plan_geom.h's: ONE text, which the host search (obca_planner.cpp) compiles too.  The
+// search loop, the holonomic map (relaxed here, a Dijkstra there), the primitives' integration and wrap() are each search's own.
 // Every loop is bounded: rounds by P.maxrounds, expansions by maxexp (a round whose live entries would pass it is not expanded), sweeps by the cell count, the chain walk
 // by the node count, wrap() by its own count.
 #pragma once
@@ -33,29 +36,25 @@
 #include "../../include/obca_plan_device.h"
 #include "../../include/obca_plan_scenes.h"
 
-#ifdef OBCA_EMU
-#define HY_FN static inline
-#define HY_HD static inline
-#else
-#define HY_FN __device__ __forceinline__
-#define HY_HD __host__ __device__ static inline
+#ifndef OBCA_EMU
 // A file-scope pragma lasts to the end of the translation unit (the target knows no float_control push / pop): obca_hip.hip includes this header LAST, behind every
 // other definition, so nothing but the planner is compiled under it.
 #pragma clang fp contract(off)
 #endif
+#include "obca_plan_geom.h"      // behind the pragma: the geometry and the Reeds-Shepp curves this search shares with the host search (HY_FN, HY_HD, HY_PI come with them)
 #ifndef HY_NT
 #define HY_NT 512      // threads per workgroup = per search: 8 waves, two per SIMD (256 VGPRs each: the collision test clips polygons in registers)
 #endif
 
 namespace obca {
 namespace hy {
+using namespace geom;
 
 #define HY_W OBCA_HYBRID_WINDOW
 #define HY_CH OBCA_HYBRID_CHUNK
 #define HY_CE (OBCA_HYBRID_CHUNK - 1)              // entries of a chunk (word 0 is the link)
 #define HY_NSI (2 * OBCA_HYBRID_MAXSTEER + 1)
 #define HY_CLIP (4 + OBCA_HYBRID_MAXROWS + 1)      // every half-plane adds at most one vertex to a convex polygon
-#define HY_PI 3.14159265358979323846
 #define HY_NONE 0xFFFFFFFFFFFFFFFFull
 typedef unsigned long long u64;
 
@@ -70,17 +69,14 @@ struct Params {      // one per call, built on the host (make_params)
     double kap[HY_NSI], steer[HY_NSI], sd[HY_NSI], cd[HY_NSI];      // per steering command: curvature, angle, sin / cos of the heading change of one forward sub-step
     double rad;                                            // radius of the disc robot of the holonomic map: 0.9 of the car's half width (or half length, if that is less)
 };
-struct Field {      // the obstacle field of a search: the batch's (obca_hybrid_astar_batch), or the instance's own (obca_scene_astar_batch: field_of)
-    int nOb; const int *v, *off, *voff; const double *A, *b, *rn, *vert;
-    const double *nrm = nullptr;      // the row norms hypot(A0, A1) (rn = 1 / nrm): read by cell_blocked only, that is by a search without a blocked map from the host
-};
+struct Field : geom::Field {};      // the obstacle field of a search: the batch's (obca_hybrid_astar_batch), or the instance's own (obca_scene_astar_batch: field_of); under
+                                    // the name the kernel's argument always had, so the kernels keep their symbols
 // The fields of a batch of scenes, instance after instance in flat arrays (make_fields).  rec: four ints per instance -- where its obstacles, rows and polygon vertices
 // start, and how many obstacles it has; off and voff carry one entry more than obstacles per instance (so instance i starts at its obstacle offset + i) and count from
 // the instance's own first row / vertex.
 struct Fields { const int *rec, *v, *off, *voff; const double *A, *b, *rn, *nrm, *vert; };
 struct Node { double x, y, yaw, s, c; float g; int parent, cell, bucket, pos; signed char dir, si; };
 struct SlotMem { Node *nodes; unsigned *cell_g; int *cell_node; u64 *claim; int *touched, *far, *chunks, *chunklist; };
-struct P2 { double x, y; };
 struct Pose { double x, y, yaw, s, c; };
 
 // ---------------------------------------------------------------- atomics, loops
@@ -114,66 +110,17 @@ HY_FN void astore64(u64 *p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, 
 #endif
 
 HY_FN unsigned fbits(float f) { unsigned u; memcpy(&u, &f, 4); return u; }      // g, f >= 0: the bits order as the numbers do
-HY_FN double wrap(double a) {
+HY_FN double wrap(double a) {      // this search's own, not the host search's: bounded at 1 024 turns like every loop here (the host's takes any yaw)
     for (int i = 0; i < 1024 && a > HY_PI; i++) a -= 2 * HY_PI;
     for (int i = 0; i < 1024 && a < -HY_PI; i++) a += 2 * HY_PI;
     return a;
 }
 HY_FN double dist2(double dx, double dy) { return sqrt(dx * dx + dy * dy); }
 
-// ---------------------------------------------------------------- collision (collides_cs of obca_planner.cpp, statement by statement)
-HY_FN int clip(const P2 *in, int n, double ax, double ay, double bb, P2 *out) {
-    int m = 0;
-    for (int i = 0; i < n; i++) {
-        const P2 p = in[i], q = in[i + 1 == n ? 0 : i + 1];
-        const double dp = ax * p.x + ay * p.y - bb, dq = ax * q.x + ay * q.y - bb;
-        if (dp <= 0) out[m++] = p;
-        if ((dp < 0 && dq > 0) || (dp > 0 && dq < 0)) { const double t = dp / (dp - dq); out[m].x = p.x + t * (q.x - p.x); out[m].y = p.y + t * (q.y - p.y); m++; }
-    }
-    return m;
-}
-HY_FN double min2(double a, double b) { return a < b ? a : b; }
-HY_FN double max2(double a, double b) { return a > b ? a : b; }
-HY_FN bool collides_cs(const Params &P, const Field &w, double x, double y, double c, double s) {
-    if (x < P.xmin || x > P.xmax || y < P.ymin || y > P.ymax) return true;
-    const double m = P.margin;
-    const double f = P.ego[0] + m, l = P.ego[1] + m, r = P.ego[2] + m, rt = P.ego[3] + m;
-    const P2 car[4] = {{x + f * c - l * s, y + f * s + l * c}, {x - r * c - l * s, y - r * s + l * c}, {x - r * c + rt * s, y - r * s - rt * c}, {x + f * c + rt * s, y + f * s - rt * c}};
-    for (int j = 0; j < w.nOb; j++) {
-        bool apart = false; double deep[4] = {1e300, 1e300, 1e300, 1e300};
-        for (int i = 0; i < w.v[j]; i++) {
-            const int rix = w.off[j] + i; const double ax = w.A[2 * rix], ay = w.A[2 * rix + 1], bb = w.b[rix];
-            const double d0 = ax * car[0].x + ay * car[0].y - bb, d1 = ax * car[1].x + ay * car[1].y - bb, d2 = ax * car[2].x + ay * car[2].y - bb, d3 = ax * car[3].x + ay * car[3].y - bb;
-            if (d0 > 0 && d1 > 0 && d2 > 0 && d3 > 0) { apart = true; break; }
-            const double n_ = w.rn[rix];
-            deep[0] = min2(deep[0], -d0 * n_); deep[1] = min2(deep[1], -d1 * n_); deep[2] = min2(deep[2], -d2 * n_); deep[3] = min2(deep[3], -d3 * n_);
-        }
-        if (apart) continue;
-        if (max2(max2(deep[0], deep[1]), max2(deep[2], deep[3])) > 1e-3) return true;
-        {
-            const int v0 = w.voff[j], v1 = w.voff[j + 1];
-            double umin = 1e300, umax = -1e300, wmin = 1e300, wmax = -1e300;
-            for (int q = v0; q < v1; q++) {
-                const double dx = w.vert[2 * q] - x, dy = w.vert[2 * q + 1] - y, u = c * dx + s * dy, v_ = -s * dx + c * dy;
-                umin = min2(umin, u); umax = max2(umax, u); wmin = min2(wmin, v_); wmax = max2(wmax, v_);
-            }
-            if (v1 > v0 && (umin > f + 1e-7 || umax < -r - 1e-7 || wmin > l + 1e-7 || wmax < -rt - 1e-7)) continue;
-        }
-        P2 bufA[HY_CLIP], bufB[HY_CLIP];
-        int n = 4; for (int i = 0; i < 4; i++) bufA[i] = car[i];
-        P2 *cur = bufA, *nxt = bufB;
-        for (int i = 0; i < w.v[j] && n > 0; i++) {
-            const int rix = w.off[j] + i;
-            n = clip(cur, n, w.A[2 * rix], w.A[2 * rix + 1], w.b[rix], nxt);
-            P2 *t = cur; cur = nxt; nxt = t;
-        }
-        if (n >= 3) {
-            double area = 0; for (int i = 0; i < n; i++) { const P2 p = cur[i], q = cur[i + 1 == n ? 0 : i + 1]; area += p.x * q.y - q.x * p.y; }
-            if (fabs(area) > 1e-9) return true;
-        }
-    }
-    return false;
-}
+// ---------------------------------------------------------------- collision: the shared test, its clip scratch two local arrays (at most OBCA_HYBRID_MAXROWS rows per obstacle)
+// The shared test makes its scratch from the carrier where a clip starts (the host search's points into the carrier's heap buffers): this one takes P and needs nothing of it.
+struct ClipLocal { P2 a[HY_CLIP], b[HY_CLIP]; HY_MEMBER ClipLocal(const Params &) {} };
+HY_FN bool collides_cs(const Params &P, const Field &w, double x, double y, double c, double s) { return geom::collides_cs<ClipLocal>(P, w, x, y, c, s); }
 
 // The field of instance i of a batch of scenes (the values are the same in every lane of the workgroup)
 HY_HD Field field_of(const Fields &S, int i) {
@@ -182,113 +129,10 @@ HY_HD Field field_of(const Fields &S, int i) {
     F.A = S.A + 2 * (size_t)row; F.b = S.b + row; F.rn = S.rn + row; F.nrm = S.nrm + row; F.vert = S.vert + 2 * (size_t)vx;
     return F;
 }
-// Can a disc of radius P.rad stand on cell (ix, iy) of the holonomic map?  disc_collides (below, the host's: obca_planner.cpp's) for one cell, statement by statement,
-// with the host's hypot(A0, A1) read from F.nrm: no libm, no contraction, the same fp64 operations in the same order -- so the same byte as the host's map.
-HY_HD bool cell_blocked(const Params &P, const Field &F, int ix, int iy) {
-    const double x = P.xmin + ix * P.res, y = P.ymin + iy * P.res, rad = P.rad;
-    for (int j = 0; j < F.nOb; j++) {
-        double worst = -1e300;
-        for (int i = 0; i < F.v[j]; i++) { const int r = F.off[j] + i; const double e = (F.A[2 * r] * x + F.A[2 * r + 1] * y - F.b[r]) / F.nrm[r]; worst = e > worst ? e : worst; }
-        if (worst < rad) {
-            if (worst <= 0) return true;
-            int cnt = 0; double d2 = 0;
-            for (int i = 0; i < F.v[j]; i++) { const int r = F.off[j] + i; const double e = (F.A[2 * r] * x + F.A[2 * r + 1] * y - F.b[r]) / F.nrm[r]; if (e > 0) { d2 += e * e; cnt++; } }
-            if (cnt <= 1 || d2 < rad * rad) return true;
-        }
-    }
-    return false;
-}
+// Can a disc of radius P.rad stand on cell (ix, iy) of the holonomic map?  The shared disc test at the cell's corner: the byte the host's map holds for the cell.
+HY_HD bool cell_blocked(const Params &P, const Field &F, int ix, int iy) { return disc_collides(F, P.xmin + ix * P.res, P.ymin + iy * P.res, P.rad); }
 
-// ---------------------------------------------------------------- Reeds-Shepp curves (namespace rs of obca_planner.cpp restated: the only code here that calls libm)
-struct RsPath { char type[5]; double len[5]; int n; double total; };
-struct Pre { double x, y, phi, sp, cp, xm, em, rm, tm, xp, ep, rp, tp; };
-#define HY_ZERO 1e-12
-HY_FN double mod2pi(double x) { double v = fabs(x) < 2 * HY_PI ? x : fmod(x, 2 * HY_PI); if (v < -HY_PI) v += 2 * HY_PI; else if (v > HY_PI) v -= 2 * HY_PI; return v; }
-HY_FN void tau_omega(double u, double v, double xi, double eta, double phi, double &tau, double &omega) {
-    const double delta = mod2pi(u - v), A = sin(u) - sin(delta), B = cos(u) - cos(delta) - 1.0;
-    const double t1 = atan2(eta * A - xi * B, xi * A + eta * B), t2 = 2.0 * (cos(delta) - cos(v) - cos(u)) + 3.0;
-    tau = t2 < 0 ? mod2pi(t1 + HY_PI) : mod2pi(t1);
-    omega = mod2pi(tau - u + v - phi);
-}
-HY_FN Pre make_pre(double x, double y, double phi, double sp, double cp, bool polar_p) {
-    Pre q; q.x = x; q.y = y; q.phi = phi; q.sp = sp; q.cp = cp;
-    q.xm = x - sp; q.em = y - 1.0 + cp; q.rm = hypot(q.xm, q.em); q.tm = atan2(q.em, q.xm);
-    q.xp = x + sp; q.ep = y - 1.0 - cp; q.rp = hypot(q.xp, q.ep); q.tp = polar_p && q.rp >= 2.0 ? atan2(q.ep, q.xp) : 0;
-    return q;
-}
-// the families by number: 0 LpSpLp, 1 LpSpRp, 2 LpRmL, 3 LpRupLumRm, 4 LpRumLumRp, 5 LpRmSmLm, 6 LpRmSmRm, 7 LpRmSLmRp
-HY_FN bool family(int fam, const Pre &q, double &t, double &u, double &v) {
-    switch (fam) {
-    case 0: u = q.rm; t = q.tm; if (t >= -HY_ZERO) { v = mod2pi(q.phi - t); if (v >= -HY_ZERO) return true; } return false;
-    case 1: { double u1 = q.rp; const double t1 = q.tp; u1 *= u1;
-              if (u1 >= 4.0) { u = sqrt(u1 - 4.0); const double th = atan2(2.0, u); t = mod2pi(t1 + th); v = mod2pi(t - q.phi); return t >= -HY_ZERO && v >= -HY_ZERO; } return false; }
-    case 2: { const double u1 = q.rm, th = q.tm;
-              if (u1 <= 4.0) { u = -2.0 * asin(0.25 * u1); t = mod2pi(th + 0.5 * u + HY_PI); v = mod2pi(q.phi - t + u); return t >= -HY_ZERO && u <= HY_ZERO; } return false; }
-    case 3: { const double rho = 0.25 * (2.0 + q.rp);
-              if (rho <= 1.0) { u = acos(rho); tau_omega(u, -u, q.xp, q.ep, q.phi, t, v); return t >= -HY_ZERO && v <= HY_ZERO; } return false; }
-    case 4: { const double rho = (20.0 - q.xp * q.xp - q.ep * q.ep) / 16.0;
-              if (rho >= 0 && rho <= 1) { u = -acos(rho); if (u >= -0.5 * HY_PI) { tau_omega(u, u, q.xp, q.ep, q.phi, t, v); return t >= -HY_ZERO && v >= -HY_ZERO; } } return false; }
-    case 5: { const double rho = q.rm, th = q.tm;
-              if (rho >= 2.0) { const double r = sqrt(rho * rho - 4.0); u = 2.0 - r; t = mod2pi(th + atan2(r, -2.0)); v = mod2pi(q.phi - 0.5 * HY_PI - t); return t >= -HY_ZERO && u <= HY_ZERO && v <= HY_ZERO; } return false; }
-    case 6: { const double rho = q.rp;
-              if (rho >= 2.0 && !(q.xp < -1e-9 * (1.0 + fabs(q.ep)))) { t = atan2(q.xp, -q.ep); u = 2.0 - rho; v = mod2pi(t + 0.5 * HY_PI - q.phi); return t >= -HY_ZERO && u <= HY_ZERO && v <= HY_ZERO; } return false; }
-    default: { const double xi = q.xp, eta = q.ep, rho = q.rp;
-              if (rho >= 2.0) { u = 4.0 - sqrt(rho * rho - 4.0);
-                  if (u <= HY_ZERO) { t = mod2pi(atan2((4.0 - u) * xi - 2.0 * eta, -2.0 * xi + (u - 4.0) * eta)); v = mod2pi(t - q.phi); return t >= -HY_ZERO && v >= -HY_ZERO; } } return false; }
-    }
-}
-// how (t, u, v) become the segment lengths: 0 t u v, 1 v u t, 2 t u -u v, 3 t u u v, 4 t -pi/2 u v, 5 v u -pi/2 t, 6 t -pi/2 u -pi/2 v
-HY_FN void fill(int how, double t, double u, double v, double *l) {
-    const double q = -0.5 * HY_PI;
-    switch (how) {
-    case 0: l[0] = t; l[1] = u; l[2] = v; break;
-    case 1: l[0] = v; l[1] = u; l[2] = t; break;
-    case 2: l[0] = t; l[1] = u; l[2] = -u; l[3] = v; break;
-    case 3: l[0] = t; l[1] = u; l[2] = u; l[3] = v; break;
-    case 4: l[0] = t; l[1] = q; l[2] = u; l[3] = v; break;
-    case 5: l[0] = v; l[1] = u; l[2] = q; l[3] = t; break;
-    default: l[0] = t; l[1] = q; l[2] = u; l[3] = q; l[4] = v; break;
-    }
-}
-// word: the n segment types packed two bits each (0 S, 1 L, 2 R); mirror: L <-> R
-HY_FN void offer(RsPath &best, int word, bool mirror, int n, const double *len, bool neg) {
-    double tot = 0; for (int i = 0; i < n; i++) tot += fabs(len[i]);
-    if (tot < best.total) {
-        best.n = n; best.total = tot;
-        for (int i = 0; i < n; i++) { const int ty = (word >> (2 * i)) & 3; best.type[i] = (char)(ty == 0 ? 0 : (mirror ? 3 - ty : ty)); best.len[i] = neg ? -len[i] : len[i]; }
-    }
-}
-HY_FN void four(RsPath &best, int fam, const Pre *q, int word, int n, int how) {
-    double t, u, v, len[5];
-    for (int k = 0; k < 4; k++)      // the query, its time flip (lengths negated), its reflection (L <-> R) and both
-        if (family(fam, q[k], t, u, v)) { fill(how, t, u, v, len); offer(best, word, k >= 2, n, len, (k & 1) != 0); }
-}
-#define HY_WORD(a, b, c, d, e) ((a) | ((b) << 2) | ((c) << 4) | ((d) << 6) | ((e) << 8))
-HY_FN RsPath rs_shortest(double x, double y, double phi) {
-    RsPath best; best.n = 0; best.total = 1e300;
-    for (int i = 0; i < 5; i++) { best.type[i] = 0; best.len[i] = 0.0; }
-    const double sp = sin(phi), cp = cos(phi);
-    const double xb = x * cp + y * sp, yb = x * sp - y * cp;
-    const Pre q[4] = {make_pre(x, y, phi, sp, cp, true), make_pre(-x, y, -phi, -sp, cp, true), make_pre(x, -y, -phi, -sp, cp, true), make_pre(-x, -y, phi, sp, cp, true)};
-    const Pre qb[4] = {make_pre(xb, yb, phi, sp, cp, false), make_pre(-xb, yb, -phi, -sp, cp, false), make_pre(xb, -yb, -phi, -sp, cp, false), make_pre(-xb, -yb, phi, sp, cp, false)};
-    enum { S = 0, L = 1, R = 2 };
-    four(best, 0, q, HY_WORD(L, S, L, 0, 0), 3, 0);
-    four(best, 1, q, HY_WORD(L, S, R, 0, 0), 3, 0);
-    four(best, 2, q, HY_WORD(L, R, L, 0, 0), 3, 0);
-    four(best, 2, qb, HY_WORD(L, R, L, 0, 0), 3, 1);
-    four(best, 3, q, HY_WORD(L, R, L, R, 0), 4, 2);
-    four(best, 4, q, HY_WORD(L, R, L, R, 0), 4, 3);
-    four(best, 5, q, HY_WORD(L, R, S, L, 0), 4, 4);
-    four(best, 6, q, HY_WORD(L, R, S, R, 0), 4, 4);
-    four(best, 5, qb, HY_WORD(L, S, R, L, 0), 4, 5);
-    four(best, 6, qb, HY_WORD(R, S, R, L, 0), 4, 5);
-    four(best, 7, q, HY_WORD(L, R, S, L, R), 5, 6);
-    return best;
-}
-HY_FN void advance_sc(int ty, double s, double &x, double &y, double &yaw, double &sy, double &cy) {
-    if (ty == 0) { x += s * cy; y += s * sy; }
-    else { const double k = ty == 1 ? 1.0 : -1.0, y1 = yaw + k * s, s1 = sin(y1), c1 = cos(y1); x += k * (s1 - sy); y += -k * (c1 - cy); yaw = y1; sy = s1; cy = c1; }
-}
+// ---------------------------------------------------------------- the analytic expansion
 // the shortest curve from the pose to the goal (unit = Rmin); the walk along it, sampled every <= 0.2 m: test (path == NULL: false at the first pose that collides)
 // or record (cap - at poses from `at`; returns the count through *nout)
 HY_FN RsPath rs_to_goal(const Params &P, const Pose &q, const double *goal) {
@@ -316,7 +160,8 @@ HY_FN bool rs_walk(const Params &P, const Field &F, const Pose &q, const RsPath 
 }
 
 // ---------------------------------------------------------------- primitives, cells, heuristic
-// one primitive from the pose: direction d, steering command si; check: collision-test every sub-step (false at the first that collides)
+// one primitive from the pose: direction d, steering command si; check: collision-test every sub-step (false at the first that collides).  This search's own integration:
+// the heading is rotated by per-primitive constants, where the host search asks libm per sub-step.
 HY_FN bool prim_apply(const Params &P, const Field &F, Pose &q, int d, int si, bool check) {
     const double kap = P.kap[si], ds = d * P.dsub, sd = d * P.sd[si], cd = P.cd[si];
     for (int j = 0; j < P.sub; j++) {
@@ -642,39 +487,15 @@ struct HostField { std::vector<int> v, off, voff; std::vector<double> A, b, rn, 
 struct HostFields { std::vector<int> rec, v, off, voff; std::vector<double> A, b, rn, nrm, vert; };
 
 static inline bool finite_(double v) { return v - v == 0.0; }
-static inline double hmin(double a, double b) { return a < b ? a : b; }
-static inline double hmax(double a, double b) { return a > b ? a : b; }
-static inline bool disc_collides(const HostField &w, int nOb, double x, double y, double rad) {      // obca_planner.cpp's, statement by statement
-    for (int j = 0; j < nOb; j++) {
-        double worst = -1e300;
-        for (int i = 0; i < w.v[j]; i++) { const int r = w.off[j] + i; const double n = hypot(w.A[2 * r], w.A[2 * r + 1]); const double e = (w.A[2 * r] * x + w.A[2 * r + 1] * y - w.b[r]) / n; worst = e > worst ? e : worst; }
-        if (worst < rad) {
-            if (worst <= 0) return true;
-            int cnt = 0; double d2 = 0;
-            for (int i = 0; i < w.v[j]; i++) { const int r = w.off[j] + i; const double n = hypot(w.A[2 * r], w.A[2 * r + 1]); const double e = (w.A[2 * r] * x + w.A[2 * r + 1] * y - w.b[r]) / n; if (e > 0) { d2 += e * e; cnt++; } }
-            if (cnt <= 1 || d2 < rad * rad) return true;
-        }
-    }
-    return false;
+static inline Field view(const HostField &W, int nOb) {
+    Field F; F.nOb = nOb; F.v = W.v.data(); F.off = W.off.data(); F.voff = W.voff.data(); F.A = W.A.data(); F.b = W.b.data(); F.rn = W.rn.data(); F.vert = W.vert.data(); F.nrm = W.nrm.data();
+    return F;
 }
-static inline int host_clip(const P2 *in, int n, double ax, double ay, double bb, P2 *out) {
-    int m = 0;
-    for (int i = 0; i < n; i++) {
-        const P2 p = in[i], q = in[(i + 1) % n];
-        const double dp = ax * p.x + ay * p.y - bb, dq = ax * q.x + ay * q.y - bb;
-        if (dp <= 0) out[m++] = p;
-        if ((dp < 0 && dq > 0) || (dp > 0 && dq < 0)) { const double t = dp / (dp - dq); out[m].x = p.x + t * (q.x - p.x); out[m].y = p.y + t * (q.y - p.y); m++; }
-    }
-    return m;
-}
-// one obstacle as a polygon (World::finish): its `rows` half-planes cut from a square of half side far_; the vertices are appended to `vert`
+// one obstacle as a polygon, the vertices appended to `vert`
 static inline void host_polygon(const double *A, const double *b, int rows, double far_, std::vector<double> &vert) {
-    P2 pa[HY_CLIP] = {{far_, far_}, {-far_, far_}, {-far_, -far_}, {far_, -far_}}, pb[HY_CLIP];
-    int n = 4; P2 *cur = pa, *nxt = pb;
-    for (int i = 0; i < rows && n > 0; i++) { n = host_clip(cur, n, A[2 * i], A[2 * i + 1], b[i], nxt); P2 *t = cur; cur = nxt; nxt = t; }
-    for (int i = 0; i < n; i++) { vert.push_back(cur[i].x); vert.push_back(cur[i].y); }
+    P2 pa[HY_CLIP], pb[HY_CLIP];
+    append_polygon(A, b, rows, far_, pa, pb, vert);
 }
-static inline double host_far(const double *XYbounds) { return 1e3 + hmax(hmax(fabs(XYbounds[0]), fabs(XYbounds[1])), hmax(fabs(XYbounds[2]), fabs(XYbounds[3]))); }
 
 // NULL if the call is good (then P, W, blocked and inst -- B x 10 doubles: start and goal with sin, cos of their headings -- are filled), else what is wrong
 static inline const char *make_params(int B, const double *starts, const double *goals, int nOb, const int *vOb, const double *A, const double *b, const double *ego, double L,
@@ -684,7 +505,7 @@ static inline const char *make_params(int B, const double *starts, const double 
     if (cap < 2) return "need cap >= 2";
     if (opts_in && (nopts < 0 || nopts > OBCA_PLAN_NOPTS)) return "need 0 <= nopts <= OBCA_PLAN_NOPTS";
     if (nOb > OBCA_HYBRID_MAXOB) return "more than OBCA_HYBRID_MAXOB obstacles";
-    double o[OBCA_PLAN_NOPTS] = {0.25, 7.5, 0.6, 0.6, 2, 0.1, 0.3, 8.0, 1.5, 2.0, 0.3, 400000, 1.0, 0.2, 1.0, 0.0, 0.0, 7.5};
+    double o[OBCA_PLAN_NOPTS] = HY_DEFAULT_OPTS;
     for (int i = 0; opts_in && i < nopts; i++) o[i] = opts_in[i];
     for (int i = 0; i < OBCA_PLAN_NOPTS; i++) if (!finite_(o[i])) return "an option is not finite";
     if (!finite_(L) || !(L > 0) || !finite_(bucket_width)) return "need L > 0 and a finite bucket_width";
@@ -719,7 +540,7 @@ static inline const char *make_params(int B, const double *starts, const double 
         const int k = si + P.nst; P.steer[k] = P.smax * si / P.nst; P.kap[k] = tan(P.smax * si / P.nst) / L;
         P.sd[k] = sin(P.dsub * P.kap[k]); P.cd[k] = cos(P.dsub * P.kap[k]);
     }
-    // the obstacle field: rows, their norms, the obstacles as polygons (World::finish)
+    // the obstacle field: rows, their norms, the obstacles as polygons
     W.v.assign(vOb, vOb + nOb); W.off.assign(nOb + 1, 0);
     for (int j = 0; j < nOb; j++) { if (vOb[j] < 1 || vOb[j] > OBCA_HYBRID_MAXROWS) return "need 1 .. OBCA_HYBRID_MAXROWS rows per obstacle"; W.off[j + 1] = W.off[j] + vOb[j]; }
     const int M_ = W.off[nOb];
@@ -736,10 +557,10 @@ static inline const char *make_params(int B, const double *starts, const double 
     }
     P.nOb = nOb; P.nrows = M_; P.nvert = (int)W.vert.size() / 2;
     // the cells a disc of the car's half width cannot stand on (the holonomic map's obstacles): a property of the field, not of the goal
-    const double rad = hmin(hmin(ego[1], ego[3]), 0.5 * (ego[0] + ego[2])) * 0.9;
-    P.rad = rad;
+    P.rad = min2(min2(ego[1], ego[3]), 0.5 * (ego[0] + ego[2])) * 0.9;
     blocked.assign((size_t)P.nmap, 0);
-    for (int iy = 0; iy < P.ny; iy++) for (int ix = 0; ix < P.nx; ix++) blocked[(size_t)iy * P.nx + ix] = disc_collides(W, nOb, P.xmin + ix * P.res, P.ymin + iy * P.res, rad);
+    const Field F = view(W, nOb);
+    for (int iy = 0; iy < P.ny; iy++) for (int ix = 0; ix < P.nx; ix++) blocked[(size_t)iy * P.nx + ix] = cell_blocked(P, F, ix, iy);
     inst.resize((size_t)B * 10);
     for (int i = 0; i < B; i++) for (int e = 0; e < 2; e++) {
         const double *p = (e ? goals : starts) + 3 * (size_t)i; double *q = &inst[(size_t)i * 10 + 5 * e];

@@ -5,8 +5,8 @@
 // plan_pack_instance: one wavefront per instance.  It reads instance i's record (PH_* of obca_solver.h, as batch_upload_range packs it) and writes what the search reads:
 //   the search's instance record, 10 doubles: x0[0..2], sin, cos of the heading, xF[0..2], sin, cos -- the only two libm calls per pose, and of this text;
 //   the instance's part of hy::Fields: A, b = the record's UNIT rows as they stand, rn = nrm = 1.0 (the norm is 1 by construction: no hypot), per obstacle its row count,
-//   row offset, vertex offset and its polygon -- the rows cut from the square of half side far_ by hy::clip, host_polygon of the planner's host code statement by statement --,
-//   and the four-int record rec.
+//   row offset, vertex offset and its polygon -- the rows cut from the square of half side far_ by the polygon() the planner's host code calls --, and the four-int
+//   record rec.
 // Strides are FIXED per instance, so no prefix sum runs over the batch: nObMax obstacles, MMax rows, nObMax + 1 entries of off / voff, PLR_NV vertices per obstacle (a
 // convex polygon gains at most one vertex per half-plane: 4 + OB_VMAX).  field_of computes F.v = S.v + rec[0], F.off = S.off + rec[0] + i, so rec = { i nObMax, i MMax,
 // i nObMax PLR_NV, nOb } lands instance i on its own block of nObMax counts and of nObMax + 1 offsets; inside the block the polygons lie one behind the other, as the
@@ -63,13 +63,10 @@ HY_HD hy::Fields fields_of(const Block &o) {
 }
 
 HY_FN int cut(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-// obstacle j of the record as a polygon: its rows cut from the square of half side far_ (host_polygon).  The vertices are in the buffer returned, n of them.
+// obstacle j of the record as a polygon: its rows cut from the square of half side far_ (the planners' one polygon()).  The vertices are in the buffer returned, n of them.
 HY_FN const hy::P2 *polygon(const double *p, int j, double far_, hy::P2 *pa, hy::P2 *pb, int &n) {
     const int rows = cut((int)p[PH_VOB + j], 0, OB_VMAX), r0 = cut((int)p[PH_ROFF + j], 0, OB_MMAX - rows);
-    pa[0].x = far_; pa[0].y = far_; pa[1].x = -far_; pa[1].y = far_; pa[2].x = -far_; pa[2].y = -far_; pa[3].x = far_; pa[3].y = -far_;
-    n = 4; hy::P2 *cur = pa, *nxt = pb;
-    for (int i = 0; i < rows && n > 0; i++) { n = hy::clip(cur, n, p[PH_A + 2 * (r0 + i)], p[PH_A + 2 * (r0 + i) + 1], p[PH_B + r0 + i], nxt); hy::P2 *t = cur; cur = nxt; nxt = t; }
-    return cur;
+    return hy::polygon(p + PH_A + 2 * r0, p + PH_B + r0, rows, far_, pa, pb, n);
 }
 
 // instance i of a batch whose blocks hold nObMax obstacles and MMax rows; p: its problem record; far_ = host_far(XYbounds)

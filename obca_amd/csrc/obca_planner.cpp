@@ -22,237 +22,48 @@
 #include <atomic>
 #include <thread>
 #include "../../include/obca_plan.h"
+#include "obca_plan_geom.h"      // the car and the disc against the obstacle field, the polygons, the Reeds-Shepp curves, the option defaults: ONE text with the device search
 
 namespace {
-
-struct P2 { double x, y; };
+using namespace obca::geom;
 
 struct World {
     int nOb; std::vector<int> v, off; std::vector<double> A, b;   // obstacle j: rows off[j] .. off[j]+v[j]
     double xmin, xmax, ymin, ymax;                               // XYbounds of the rear-axle position
     double ego[4], margin;                                        // front, left, rear, right extents from the rear axle; inflation
-    mutable std::vector<P2> bufA, bufB;                           // clip scratch of collides(), sized for the obstacle with the most rows
-    std::vector<double> rn;                                       // 1 / |a_i| of every row
-    std::vector<P2> vert; std::vector<int> voff;                  // obstacle j as a polygon (cut to a box far outside the bounds if it is unbounded): vert[voff[j] .. voff[j+1])
+    mutable std::vector<P2> bufA, bufB;                           // clip scratch of collides(), sized for the obstacle with the most rows (any number: only the device caps them)
+    std::vector<double> rn, nrm;                                  // 1 / |a_i| and |a_i| of every row
+    std::vector<double> vert; std::vector<int> voff;              // obstacle j as a polygon (cut to a box far outside the bounds if it is unbounded): x, y of vertices voff[j] .. voff[j+1]
+    Field F;                                                      // the view of all this that the shared tests read (finish): pointers into the vectors above, so no copies
+    World() = default; World(const World &) = delete; World &operator=(const World &) = delete;
     void finish();
 };
-
-// convex polygon clipped by the half-plane a.p <= bb (Sutherland-Hodgman); returns the number of vertices left
-static int clip(const P2 *in, int n, double ax, double ay, double bb, P2 *out) {
-    int m = 0;
-    for (int i = 0; i < n; i++) {
-        const P2 &p = in[i], &q = in[(i + 1) % n];
-        const double dp = ax * p.x + ay * p.y - bb, dq = ax * q.x + ay * q.y - bb;
-        if (dp <= 0) out[m++] = p;
-        if ((dp < 0 && dq > 0) || (dp > 0 && dq < 0)) { const double t = dp / (dp - dq); out[m++] = {p.x + t * (q.x - p.x), p.y + t * (q.y - p.y)}; }
-    }
-    return m;
-}
 
 void World::finish() {     // what collides() needs besides the rows: their norms, the obstacles' vertices, the clip scratch
     int vmax = 0; for (int j = 0; j < nOb; j++) vmax = std::max(vmax, v[j]);
     bufA.resize(4 + vmax + 1); bufB.resize(4 + vmax + 1);         // every half-plane adds at most one vertex to a convex polygon
-    rn.resize(off[nOb]);
-    for (int r = 0; r < off[nOb]; r++) { const double n = std::hypot(A[2 * r], A[2 * r + 1]); rn[r] = n > 0 ? 1.0 / n : 0.0; }
-    const double far_ = 1e3 + std::max(std::max(std::fabs(xmin), std::fabs(xmax)), std::max(std::fabs(ymin), std::fabs(ymax)));
+    rn.resize(off[nOb]); nrm.resize(off[nOb]);
+    for (int r = 0; r < off[nOb]; r++) { const double n = std::hypot(A[2 * r], A[2 * r + 1]); rn[r] = n > 0 ? 1.0 / n : 0.0; nrm[r] = n; }
+    const double xy[4] = {xmin, xmax, ymin, ymax}, far_ = host_far(xy);
     voff.assign(nOb + 1, 0); vert.clear();
-    std::vector<P2> pa(4 + vmax + 1), pb(4 + vmax + 1);
-    for (int j = 0; j < nOb; j++) {
-        int n = 4; pa[0] = {far_, far_}; pa[1] = {-far_, far_}; pa[2] = {-far_, -far_}; pa[3] = {far_, -far_};
-        P2 *cur = pa.data(), *nxt = pb.data();
-        for (int i = 0; i < v[j] && n > 0; i++) { const int r = off[j] + i; n = clip(cur, n, A[2 * r], A[2 * r + 1], b[r], nxt); std::swap(cur, nxt); }
-        vert.insert(vert.end(), cur, cur + n); voff[j + 1] = (int)vert.size();
-    }
+    for (int j = 0; j < nOb; j++) { append_polygon(A.data() + 2 * (size_t)off[j], b.data() + off[j], v[j], far_, bufA.data(), bufB.data(), vert); voff[j + 1] = (int)vert.size() / 2; }
+    F.nOb = nOb; F.v = v.data(); F.off = off.data(); F.voff = voff.data(); F.A = A.data(); F.b = b.data(); F.rn = rn.data(); F.vert = vert.data(); F.nrm = nrm.data();
 }
 
-// Does the (inflated) car rectangle at the pose overlap an obstacle?  The answer is DEFINED by the clipped overlap area (car cut by every half-plane of the obstacle,
-// area > 1e-9); nearly every call is settled before that by the separating-axis tests of a rectangle against a convex polygon, which agree with it: a row all four corners
-// violate (the clip would leave nothing), a car side every vertex of the obstacle lies beyond, or a corner deep inside every row.
-static bool collides_cs(const World &w, double x, double y, double c, double s) {      // c, s = cos, sin of the heading
-    if (x < w.xmin || x > w.xmax || y < w.ymin || y > w.ymax) return true;
-    const double m = w.margin;
-    const double f = w.ego[0] + m, l = w.ego[1] + m, r = w.ego[2] + m, rt = w.ego[3] + m;
-    const P2 car[4] = {{x + f * c - l * s, y + f * s + l * c}, {x - r * c - l * s, y - r * s + l * c},
-                       {x - r * c + rt * s, y - r * s - rt * c}, {x + f * c + rt * s, y + f * s - rt * c}};
-    std::vector<P2> &bufA = w.bufA, &bufB = w.bufB;
-    for (int j = 0; j < w.nOb; j++) {
-        bool apart = false; double deep[4] = {1e300, 1e300, 1e300, 1e300};      // deep[q]: how far corner q is inside the obstacle (least over its rows)
-        for (int i = 0; i < w.v[j]; i++) {
-            const int rix = w.off[j] + i; const double ax = w.A[2 * rix], ay = w.A[2 * rix + 1], bb = w.b[rix];
-            const double d0 = ax * car[0].x + ay * car[0].y - bb, d1 = ax * car[1].x + ay * car[1].y - bb, d2 = ax * car[2].x + ay * car[2].y - bb, d3 = ax * car[3].x + ay * car[3].y - bb;
-            if (d0 > 0 && d1 > 0 && d2 > 0 && d3 > 0) { apart = true; break; }
-            const double n_ = w.rn[rix];
-            deep[0] = std::min(deep[0], -d0 * n_); deep[1] = std::min(deep[1], -d1 * n_); deep[2] = std::min(deep[2], -d2 * n_); deep[3] = std::min(deep[3], -d3 * n_);
-        }
-        if (apart) continue;
-        if (std::max(std::max(deep[0], deep[1]), std::max(deep[2], deep[3])) > 1e-3) return true;   // a quarter disc of radius 1e-3 around that corner is overlap: area > 7e-7
-        {   // the car's own sides: in its frame the obstacle's vertices are (u, v_); a side with every vertex beyond it (by more than a rounding margin) separates
-            const int v0 = w.voff[j], v1 = w.voff[j + 1];
-            double umin = 1e300, umax = -1e300, wmin = 1e300, wmax = -1e300;
-            for (int q = v0; q < v1; q++) {
-                const double dx = w.vert[q].x - x, dy = w.vert[q].y - y, u = c * dx + s * dy, v_ = -s * dx + c * dy;
-                umin = std::min(umin, u); umax = std::max(umax, u); wmin = std::min(wmin, v_); wmax = std::max(wmax, v_);
-            }
-            if (v1 > v0 && (umin > f + 1e-7 || umax < -r - 1e-7 || wmin > l + 1e-7 || wmax < -rt - 1e-7)) continue;
-        }
-        int n = 4; std::memcpy(bufA.data(), car, sizeof car);
-        P2 *cur = bufA.data(), *nxt = bufB.data();
-        for (int i = 0; i < w.v[j] && n > 0; i++) {
-            const int rix = w.off[j] + i;
-            n = clip(cur, n, w.A[2 * rix], w.A[2 * rix + 1], w.b[rix], nxt);
-            std::swap(cur, nxt);
-        }
-        if (n >= 3) {   // non-degenerate overlap
-            double area = 0; for (int i = 0; i < n; i++) { const P2 &p = cur[i], &q = cur[(i + 1) % n]; area += p.x * q.y - q.x * p.y; }
-            if (std::fabs(area) > 1e-9) return true;
-        }
-    }
-    return false;
-}
+struct ClipHeap { P2 *a, *b; ClipHeap(const World &w) : a(w.bufA.data()), b(w.bufB.data()) {} };      // the clip scratch of the shared test: World's, of any size
+static inline bool collides_cs(const World &w, double x, double y, double c, double s) { return obca::geom::collides_cs<ClipHeap>(w, w.F, x, y, c, s); }      // c, s = cos, sin of the heading
 static inline bool collides(const World &w, double x, double y, double yaw) { return collides_cs(w, x, y, std::cos(yaw), std::sin(yaw)); }
 
-static bool disc_collides(const World &w, double x, double y, double rad) {
-    for (int j = 0; j < w.nOb; j++) {   // distance of the point to the convex set (intersection of half-planes), conservative via max row slack
-        double worst = -1e300;
-        for (int i = 0; i < w.v[j]; i++) { const int r = w.off[j] + i; const double n = std::hypot(w.A[2 * r], w.A[2 * r + 1]); worst = std::max(worst, (w.A[2 * r] * x + w.A[2 * r + 1] * y - w.b[r]) / n); }
-        if (worst < rad) {   // inside the rad-offset of every half-plane: within rad of the set unless near a corner (then slightly conservative)
-            if (worst <= 0) return true;
-            // corner case: exact distance to the set is >= worst; test the rounded corner with the two most violated rows
-            int cnt = 0; double d2 = 0;
-            for (int i = 0; i < w.v[j]; i++) { const int r = w.off[j] + i; const double n = std::hypot(w.A[2 * r], w.A[2 * r + 1]); const double e = (w.A[2 * r] * x + w.A[2 * r + 1] * y - w.b[r]) / n; if (e > 0) { d2 += e * e; cnt++; } }
-            if (cnt <= 1 || d2 < rad * rad) return true;
-        }
-    }
-    return false;
-}
-
 struct Node { double x, y, yaw, g; int parent; int8_t dir, steer; };
+// this search's own, not the device search's (whose wrap is bounded at 1 024 turns): any yaw comes back into (-pi, pi]
 static inline double wrap(double a) { while (a > M_PI) a -= 2 * M_PI; while (a < -M_PI) a += 2 * M_PI; return a; }
+// advance a pose along one Reeds-Shepp segment (type 0 S, 1 L, 2 R) by the signed amount s (unit radius); advance_sc is the form a walk uses
+static inline void advance(int ty, double s, double &x, double &y, double &yaw) {
+    if (ty == 0) { x += s * std::cos(yaw); y += s * std::sin(yaw); }
+    else { const double k = ty == 1 ? 1.0 : -1.0, y1 = yaw + k * s; x += k * (std::sin(y1) - std::sin(yaw)); y += -k * (std::cos(y1) - std::cos(yaw)); yaw = y1; }
+}
 
 }  // namespace
-
-// ---------------------------------------------------------------- Reeds-Shepp curves (the planner's analytic expansion)
-// Shortest path of a car that drives forwards and backwards with a bounded turning radius (Reeds & Shepp 1990), in the normalised problem
-// (unit radius, start at the origin with heading 0): the 48 candidate words are generated from the closed-form families CSC, CCC, CCCC, CCSC,
-// CCSCC and the time-flip / reflection / backwards symmetries, the shortest is kept.  Stands where hybrid_a_star.jl:262-300 calls
-// reeds_shepp.calc_shortest_path (reeds_shepp.jl).  A path is at most five segments: type 'L' / 'R' (arc, signed angle) or 'S' (signed length).
-namespace rs {
-struct Path { char type[5]; double len[5]; int n; double total; };
-static const double PI = M_PI, ZERO = 1e-12;
-static inline double mod2pi(double x) { double v = std::fabs(x) < 2 * PI ? x : std::fmod(x, 2 * PI); if (v < -PI) v += 2 * PI; else if (v > PI) v -= 2 * PI; return v; }   // (fmod returns such an x itself)
-static inline void polar(double x, double y, double &r, double &th) { r = std::hypot(x, y); th = std::atan2(y, x); }
-static inline void tau_omega(double u, double v, double xi, double eta, double phi, double &tau, double &omega) {
-    const double delta = mod2pi(u - v), A = std::sin(u) - std::sin(delta), B = std::cos(u) - std::cos(delta) - 1.0;
-    const double t1 = std::atan2(eta * A - xi * B, xi * A + eta * B), t2 = 2.0 * (std::cos(delta) - std::cos(v) - std::cos(u)) + 3.0;
-    tau = t2 < 0 ? mod2pi(t1 + PI) : mod2pi(t1);
-    omega = mod2pi(tau - u + v - phi);
-}
-// One mirror image of the query, (x, y, phi), with what the families share: sin / cos of phi, the two centre offsets (xi, eta) = (x -+ sin phi, y - 1 +- cos phi) and
-// their polar forms.  A family is a few lines on top of these; evaluating the 44 family calls of a query from scratch costs ~200 libm calls, from here ~50.
-struct Pre {
-    double x, y, phi, sp, cp;
-    double xm, em, rm, tm;        // (x - sin phi, y - 1 + cos phi) and its polar form         (LSL, LRL, LRSL)
-    double xp, ep, rp, tp;        // (x + sin phi, y - 1 - cos phi) and its polar form         (LSR, LRLR, LRSR, LRSLR)
-};
-static inline Pre make_pre(double x, double y, double phi, double sp, double cp, bool polar_p) {
-    Pre q; q.x = x; q.y = y; q.phi = phi; q.sp = sp; q.cp = cp;
-    q.xm = x - sp; q.em = y - 1.0 + cp; polar(q.xm, q.em, q.rm, q.tm);
-    q.xp = x + sp; q.ep = y - 1.0 - cp; q.rp = std::hypot(q.xp, q.ep); q.tp = polar_p && q.rp >= 2.0 ? std::atan2(q.ep, q.xp) : 0;      // (the angle: LSR only, which needs rp >= 2)
-    return q;
-}
-static bool LpSpLp(const Pre &q, double &t, double &u, double &v) {
-    u = q.rm; t = q.tm;
-    if (t >= -ZERO) { v = mod2pi(q.phi - t); if (v >= -ZERO) return true; }
-    return false;
-}
-static bool LpSpRp(const Pre &q, double &t, double &u, double &v) {
-    double u1 = q.rp; const double t1 = q.tp;
-    u1 *= u1;
-    if (u1 >= 4.0) { u = std::sqrt(u1 - 4.0); const double th = std::atan2(2.0, u); t = mod2pi(t1 + th); v = mod2pi(t - q.phi); return t >= -ZERO && v >= -ZERO; }
-    return false;
-}
-static bool LpRmL(const Pre &q, double &t, double &u, double &v) {
-    const double u1 = q.rm, th = q.tm;
-    if (u1 <= 4.0) { u = -2.0 * std::asin(0.25 * u1); t = mod2pi(th + 0.5 * u + PI); v = mod2pi(q.phi - t + u); return t >= -ZERO && u <= ZERO; }
-    return false;
-}
-static bool LpRupLumRm(const Pre &q, double &t, double &u, double &v) {
-    const double rho = 0.25 * (2.0 + q.rp);
-    if (rho <= 1.0) { u = std::acos(rho); tau_omega(u, -u, q.xp, q.ep, q.phi, t, v); return t >= -ZERO && v <= ZERO; }
-    return false;
-}
-static bool LpRumLumRp(const Pre &q, double &t, double &u, double &v) {
-    const double rho = (20.0 - q.xp * q.xp - q.ep * q.ep) / 16.0;
-    if (rho >= 0 && rho <= 1) { u = -std::acos(rho); if (u >= -0.5 * PI) { tau_omega(u, u, q.xp, q.ep, q.phi, t, v); return t >= -ZERO && v >= -ZERO; } }
-    return false;
-}
-static bool LpRmSmLm(const Pre &q, double &t, double &u, double &v) {
-    const double rho = q.rm, th = q.tm;
-    if (rho >= 2.0) { const double r = std::sqrt(rho * rho - 4.0); u = 2.0 - r; t = mod2pi(th + std::atan2(r, -2.0)); v = mod2pi(q.phi - 0.5 * PI - t); return t >= -ZERO && u <= ZERO && v <= ZERO; }
-    return false;
-}
-static bool LpRmSmRm(const Pre &q, double &t, double &u, double &v) {
-    const double rho = q.rp;                                       // polar form of (-eta, xi): the same radius, the angle atan2(xi, -eta) -- negative (a reject) for xi < 0
-    if (rho >= 2.0 && !(q.xp < -1e-9 * (1.0 + std::fabs(q.ep)))) { t = std::atan2(q.xp, -q.ep); u = 2.0 - rho; v = mod2pi(t + 0.5 * PI - q.phi); return t >= -ZERO && u <= ZERO && v <= ZERO; }
-    return false;
-}
-static bool LpRmSLmRp(const Pre &q, double &t, double &u, double &v) {
-    const double xi = q.xp, eta = q.ep, rho = q.rp;
-    if (rho >= 2.0) {
-        u = 4.0 - std::sqrt(rho * rho - 4.0);
-        if (u <= ZERO) { t = mod2pi(std::atan2((4.0 - u) * xi - 2.0 * eta, -2.0 * xi + (u - 4.0) * eta)); v = mod2pi(t - q.phi); return t >= -ZERO && v >= -ZERO; }
-    }
-    return false;
-}
-static void offer(Path &best, const char *ty, int n, const double *len) {
-    double tot = 0; for (int i = 0; i < n; i++) tot += std::fabs(len[i]);
-    if (tot < best.total) { best.n = n; best.total = tot; for (int i = 0; i < n; i++) { best.type[i] = ty[i]; best.len[i] = len[i]; } }
-}
-// every family is tried on (x, y, phi), its time flip (-x, y, -phi: all lengths negated), its reflection (x, -y, -phi: L <-> R) and both: q[0..3]
-template <class F> static void four(Path &best, F f, const Pre *q, const char *ty, const char *tyr, int n, void (*fill)(double, double, double, double *)) {
-    double t, u, v, len[5];
-    if (f(q[0], t, u, v)) { fill(t, u, v, len); offer(best, ty, n, len); }
-    if (f(q[1], t, u, v)) { fill(t, u, v, len); for (int i = 0; i < n; i++) len[i] = -len[i]; offer(best, ty, n, len); }
-    if (f(q[2], t, u, v)) { fill(t, u, v, len); offer(best, tyr, n, len); }
-    if (f(q[3], t, u, v)) { fill(t, u, v, len); for (int i = 0; i < n; i++) len[i] = -len[i]; offer(best, tyr, n, len); }
-}
-static void f_tuv(double t, double u, double v, double *l) { l[0] = t; l[1] = u; l[2] = v; }
-static void f_vut(double t, double u, double v, double *l) { l[0] = v; l[1] = u; l[2] = t; }
-static void f_tuuv_m(double t, double u, double v, double *l) { l[0] = t; l[1] = u; l[2] = -u; l[3] = v; }
-static void f_tuuv_p(double t, double u, double v, double *l) { l[0] = t; l[1] = u; l[2] = u; l[3] = v; }
-static void f_t_q_u_v(double t, double u, double v, double *l) { l[0] = t; l[1] = -0.5 * PI; l[2] = u; l[3] = v; }
-static void f_v_u_q_t(double t, double u, double v, double *l) { l[0] = v; l[1] = u; l[2] = -0.5 * PI; l[3] = t; }
-static void f_t_q_u_q_v(double t, double u, double v, double *l) { l[0] = t; l[1] = -0.5 * PI; l[2] = u; l[3] = -0.5 * PI; l[4] = v; }
-static Path shortest(double x, double y, double phi) {
-    Path best; best.n = 0; best.total = 1e300;
-    const double sp = std::sin(phi), cp = std::cos(phi);        // (sin, cos of -phi are -sp, cp: libm's sin is odd and its cos even to the last bit)
-    const double xb = x * cp + y * sp, yb = x * sp - y * cp;    // the same word driven backwards
-    const Pre q[4] = {make_pre(x, y, phi, sp, cp, true), make_pre(-x, y, -phi, -sp, cp, true), make_pre(x, -y, -phi, -sp, cp, true), make_pre(-x, -y, phi, sp, cp, true)};
-    const Pre qb[4] = {make_pre(xb, yb, phi, sp, cp, false), make_pre(-xb, yb, -phi, -sp, cp, false), make_pre(xb, -yb, -phi, -sp, cp, false), make_pre(-xb, -yb, phi, sp, cp, false)};
-    four(best, LpSpLp, q, "LSL", "RSR", 3, f_tuv);
-    four(best, LpSpRp, q, "LSR", "RSL", 3, f_tuv);
-    four(best, LpRmL, q, "LRL", "RLR", 3, f_tuv);
-    four(best, LpRmL, qb, "LRL", "RLR", 3, f_vut);
-    four(best, LpRupLumRm, q, "LRLR", "RLRL", 4, f_tuuv_m);
-    four(best, LpRumLumRp, q, "LRLR", "RLRL", 4, f_tuuv_p);
-    four(best, LpRmSmLm, q, "LRSL", "RLSR", 4, f_t_q_u_v);
-    four(best, LpRmSmRm, q, "LRSR", "RLSL", 4, f_t_q_u_v);
-    four(best, LpRmSmLm, qb, "LSRL", "RSLR", 4, f_v_u_q_t);
-    four(best, LpRmSmRm, qb, "RSRL", "LSLR", 4, f_v_u_q_t);
-    four(best, LpRmSLmRp, q, "LRSLR", "RLSRL", 5, f_t_q_u_q_v);
-    return best;
-}
-// advance a pose along one segment by the signed amount s (unit radius)
-static inline void advance(char ty, double s, double &x, double &y, double &yaw) {
-    if (ty == 'S') { x += s * std::cos(yaw); y += s * std::sin(yaw); }
-    else { const double k = ty == 'L' ? 1.0 : -1.0, y1 = yaw + k * s; x += k * (std::sin(y1) - std::sin(yaw)); y += -k * (std::cos(y1) - std::cos(yaw)); yaw = y1; }
-}
-// the same with sin / cos of the heading carried along (sy, cy: of `yaw` on entry and on exit) -- a walk along a path asks libm for each angle once
-static inline void advance_sc(char ty, double s, double &x, double &y, double &yaw, double &sy, double &cy) {
-    if (ty == 'S') { x += s * cy; y += s * sy; }
-    else { const double k = ty == 'L' ? 1.0 : -1.0, y1 = yaw + k * s, s1 = std::sin(y1), c1 = std::cos(y1); x += k * (s1 - sy); y += -k * (c1 - cy); yaw = y1; sy = s1; cy = c1; }
-}
-}  // namespace rs
 
 // ---------------------------------------------------------------- non-holonomic-WITH-obstacles heuristic on a lattice (round 6)
 // Cost-to-go of the search's own motion model -- arcs of the same curvatures, the same reverse / steering / direction-switch costs -- on a coarse (x, y, yaw, direction of arrival)
@@ -342,7 +153,7 @@ static int hybrid_astar_impl(const double start[3], const double goal[3], int nO
     if (!start || !goal || nOb < 0 || !vOb || !A || !b || !ego || !XYbounds || !path || !dir || cap < 2) return -1;
     if (opts_in && (nopts < 0 || nopts > OBCA_PLAN_NOPTS)) return -1;
     // the caller's first nopts options over the defaults: an array of the 14 options of rounds 1-4 leaves the newer ones at their defaults and nothing is read beyond its end
-    double optbuf[OBCA_PLAN_NOPTS] = {0.25, 7.5, 0.6, 0.6, 2, 0.1, 0.3, 8.0, 1.5, 2.0, 0.3, 400000, 1.0, 0.2, 1.0, 0.0, 0.0, 7.5};
+    double optbuf[OBCA_PLAN_NOPTS] = HY_DEFAULT_OPTS;
     for (int i = 0; opts_in && i < nopts; i++) optbuf[i] = opts_in[i];
     const double *opts = optbuf;
     if (!(opts[14] > 0.0) || !std::isfinite(opts[14])) return -1;      // heuristic weight: positive and finite (0, negative or NaN would silently corrupt the search order)
@@ -363,13 +174,14 @@ static int hybrid_astar_impl(const double start[3], const double goal[3], int nO
     std::memcpy(w.ego, ego, sizeof w.ego); w.margin = margin; w.finish();
     if (collides(w, start[0], start[1], start[2]) || collides(w, goal[0], goal[1], goal[2])) return -2;
 
-    // holonomic heuristic: Dijkstra on the xy grid from the goal for a disc of the car's half width (hybrid_a_star.jl's grid heuristic)
+    // holonomic heuristic: Dijkstra on the xy grid from the goal for a disc of the car's half width (hybrid_a_star.jl's grid heuristic).  The blocked cells are the shared
+    // disc test's; the map itself is this search's own (the device search relaxes its map in LDS)
     const int nx = (int)std::ceil((w.xmax - w.xmin) / res) + 1, ny = (int)std::ceil((w.ymax - w.ymin) / res) + 1;
     std::vector<float> hmap((size_t)nx * ny, 1e9f);
     {
         const double rad = std::min(std::min(ego[1], ego[3]), 0.5 * (ego[0] + ego[2])) * 0.9;
         std::vector<uint8_t> blocked((size_t)nx * ny, 0);
-        for (int iy = 0; iy < ny; iy++) for (int ix = 0; ix < nx; ix++) blocked[(size_t)iy * nx + ix] = disc_collides(w, w.xmin + ix * res, w.ymin + iy * res, rad);
+        for (int iy = 0; iy < ny; iy++) for (int ix = 0; ix < nx; ix++) blocked[(size_t)iy * nx + ix] = disc_collides(w.F, w.xmin + ix * res, w.ymin + iy * res, rad);
         typedef std::pair<float, int> QE; std::priority_queue<QE, std::vector<QE>, std::greater<QE>> pq;
         const int gx = std::min(nx - 1, std::max(0, (int)std::lround((goal[0] - w.xmin) / res))), gy = std::min(ny - 1, std::max(0, (int)std::lround((goal[1] - w.ymin) / res)));
         hmap[(size_t)gy * nx + gx] = 0; pq.push({0.f, gy * nx + gx});
@@ -399,7 +211,7 @@ static int hybrid_astar_impl(const double start[3], const double goal[3], int nO
         double h = std::max(h2, Rmin * std::fabs(wrap(yaw - goal[2])) * 0.5);
         if (rs_heur) {      // length of the shortest Reeds-Shepp curve to the goal: what the car needs at least, obstacles ignored (hybrid_a_star.jl:58, 542: max(c_h_dp, c_h_rs))
             const double dx = goal[0] - x, dy = goal[1] - y, c = std::cos(yaw), s_ = std::sin(yaw);
-            const rs::Path p = rs::shortest((c * dx + s_ * dy) / Rmin, (-s_ * dx + c * dy) / Rmin, wrap(goal[2] - yaw));
+            const RsPath p = rs_shortest((c * dx + s_ * dy) / Rmin, (-s_ * dx + c * dy) / Rmin, wrap(goal[2] - yaw));
             if (p.n > 0) h = std::max(h, Rmin * p.total);
         }
         if (nh) { const double hn = nh->lookup(x - nh_dx, y - nh_dy, yaw, dir_in); if (hn >= 0) h = std::max(h, hn); }
@@ -437,16 +249,18 @@ static int hybrid_astar_impl(const double start[3], const double goal[3], int nO
         if (analytic > 0 && (dgoal < 6.0 * Rmin || nexp % 16 == 0)) {
             // shortest Reeds-Shepp curve from this node to the goal: if the car can follow it without touching anything, the search is over
             const double dx = goal[0] - cur.x, dy = goal[1] - cur.y, c = cy0, s_ = sy0;
-            const rs::Path p = rs::shortest((c * dx + s_ * dy) / Rmin, (-s_ * dx + c * dy) / Rmin, wrap(goal[2] - cur.yaw));
+            const RsPath p = rs_shortest((c * dx + s_ * dy) / Rmin, (-s_ * dx + c * dy) / Rmin, wrap(goal[2] - cur.yaw));
             // the walk along it, sampled every <= 0.2 m: nearly every curve hits something within a few samples, so the first pass only tests (heading cos / sin by the
-            // addition theorem from those the walk carries) and the one curve that passes is walked again to record its poses
+            // addition theorem from those the walk carries) and the one curve that passes is walked again to record its poses.  This search's own walk, over the shared
+            // advance_sc and collision test, and left so on purpose: the device search's walk wraps with its bounded wrap, reads its parameter block and tests through its
+            // local clip scratch, so one text would be a template over all three for these dozen lines, and would change the device's kernels once more.
             auto walk = [&](bool record) {
                 double x = 0, y = 0, yaw = 0, sy = std::sin(0.0), cy = std::cos(0.0);
                 for (int i = 0; i < p.n; i++) {
                     const double L_ = std::fabs(p.len[i]); if (L_ < 1e-12) continue;
                     const int d = p.len[i] >= 0 ? 1 : -1, m = std::max(1, (int)std::ceil(L_ * Rmin / 0.2));
                     for (int q = 0; q < m; q++) {
-                        rs::advance_sc(p.type[i], p.len[i] / m, x, y, yaw, sy, cy);
+                        advance_sc(p.type[i], p.len[i] / m, x, y, yaw, sy, cy);
                         const double wx = cur.x + Rmin * (c * x - s_ * y), wy = cur.y + Rmin * (s_ * x + c * y);
                         if (record) { tail.insert(tail.end(), {wx, wy, wrap(cur.yaw + yaw)}); taild.push_back(d); }
                         else if (collides_cs(w, wx, wy, c * cy - s_ * sy, s_ * cy + c * sy)) return false;
@@ -459,6 +273,7 @@ static int hybrid_astar_impl(const double start[3], const double goal[3], int nO
         for (int d = 1; d >= -1; d -= 2)
             for (int si = -nst; si <= nst; si++) {
                 const double steer = smax * si / nst, kap = kappa[si + nst];
+                // this search's own integration of a primitive: libm per sub-step (the device search rotates the heading by per-primitive constants instead)
                 double x = cur.x, y = cur.y, yaw = cur.yaw, sy = sy0, cy = cy0; bool ok = true;      // (sy, cy: sin, cos of yaw -- each angle goes to libm once)
                 for (int q = 0; q < sub && ok; q++) {
                     const double ds = d * step / sub;
@@ -521,7 +336,7 @@ int obca_plan_hybrid_astar_batch2(int B, const double *starts, const double *goa
     // the lattice heuristic (options 16, 17) is a property of the obstacle field and the goal: ONE table for the batch, built around the goal in the middle of the batch's goals
     NhTable table; const NhTable *shared = nullptr;
     if (B > 0 && opts && nopts > 16 && opts[16] > 0 && nOb >= 0 && vOb && A && b && ego && XYbounds) {
-        double o_[OBCA_PLAN_NOPTS] = {0.25, 7.5, 0.6, 0.6, 2, 0.1, 0.3, 8.0, 1.5, 2.0, 0.3, 400000, 1.0, 0.2, 1.0, 0.0, 0.0, 7.5};
+        double o_[OBCA_PLAN_NOPTS] = HY_DEFAULT_OPTS;
         for (int i = 0; i < nopts; i++) o_[i] = opts[i];
         if (std::isfinite(o_[16]) && o_[16] >= 0.05 && o_[17] > 0.05 && (int)o_[4] >= 0) {
             std::vector<double> gxs(B), gys(B);
@@ -575,9 +390,9 @@ int obca_plan_reeds_shepp(const double start[3], const double goal[3], double R,
                           double *seglen, double *total) {
     if (!start || !goal || !(R > 0) || !(step > 0) || !path || !dir || cap < 2) return -1;
     const double dx = goal[0] - start[0], dy = goal[1] - start[1], c = std::cos(start[2]), s_ = std::sin(start[2]);
-    const rs::Path p = rs::shortest((c * dx + s_ * dy) / R, (-s_ * dx + c * dy) / R, wrap(goal[2] - start[2]));
+    const RsPath p = rs_shortest((c * dx + s_ * dy) / R, (-s_ * dx + c * dy) / R, wrap(goal[2] - start[2]));
     if (p.n == 0) return -1;
-    if (word) { for (int i = 0; i < p.n; i++) word[i] = p.type[i]; word[p.n] = 0; }
+    if (word) { for (int i = 0; i < p.n; i++) word[i] = "SLR"[(int)p.type[i]]; word[p.n] = 0; }
     if (seglen) for (int i = 0; i < 5; i++) seglen[i] = i < p.n ? p.len[i] * R : 0.0;
     if (total) *total = p.total * R;
     int cnt = 0;
@@ -591,7 +406,7 @@ int obca_plan_reeds_shepp(const double start[3], const double goal[3], double R,
     for (int i = 0; i < p.n; i++) {
         const double L_ = std::fabs(p.len[i]); if (L_ < 1e-12) continue;
         const int d = p.len[i] >= 0 ? 1 : -1, m = std::max(1, (int)std::ceil(L_ * R / step));
-        for (int q = 0; q < m; q++) { rs::advance(p.type[i], p.len[i] / m, x, y, yaw); if (!emit(d)) return -1; }
+        for (int q = 0; q < m; q++) { advance(p.type[i], p.len[i] / m, x, y, yaw); if (!emit(d)) return -1; }
     }
     return cnt;
 }

@@ -318,6 +318,7 @@ def test_host_build_goes_through_the_one_rule(tmp_path, monkeypatch):
             todo.append(os.path.realpath(os.path.join(os.path.dirname(f), inc)))
     csrc = os.path.join(ROOT, "obca_amd", "csrc")
     assert os.path.realpath(os.path.join(csrc, "obca_hybrid.h")) in seen and os.path.realpath(os.path.join(ROOT, "include", "obca_plan_device.h")) in seen
+    assert os.path.realpath(os.path.join(csrc, "obca_plan_geom.h")) in seen      # the geometry and the Reeds-Shepp curves, one text with the host search
     assert os.path.realpath(os.path.join(csrc, "obca_solver.h")) not in seen      # the planner shares no text with the solve kernels
     calls = []
 
@@ -338,3 +339,8 @@ def test_host_build_goes_through_the_one_rule(tmp_path, monkeypatch):
     for f in os.listdir(csrc):
         if f.endswith(".h") and f != "obca_hybrid.h":
             assert "obca_hybrid.h" not in open(os.path.join(csrc, f)).read(), f
+    # the text both planners share is included by the host search and by the kernel text (there behind the pragma), by nothing else
+    users = {f for f in os.listdir(csrc) if f.endswith((".h", ".hip", ".cpp")) and re.search(r'#[ \t]*include[ \t]*"obca_plan_geom\.h"', open(os.path.join(csrc, f)).read())}
+    assert users == {"obca_planner.cpp", "obca_hybrid.h"}, users
+    kernel_text = open(os.path.join(csrc, "obca_hybrid.h")).read()
+    assert kernel_text.index("fp contract(off)") < kernel_text.index('#include "obca_plan_geom.h"')

@@ -272,7 +272,7 @@ def test_host_build_goes_through_the_one_rule(tmp_path, monkeypatch):
             assert os.path.exists(os.path.join(os.path.dirname(f), inc)), (f, inc)
             todo.append(os.path.realpath(os.path.join(os.path.dirname(f), inc)))
     csrc = os.path.join(ROOT, "obca_amd", "csrc")
-    for h in ("obca_plan_resident.h", "obca_hybrid.h", "obca_path_ws.h"):
+    for h in ("obca_plan_resident.h", "obca_hybrid.h", "obca_plan_geom.h", "obca_path_ws.h"):
         assert os.path.realpath(os.path.join(csrc, h)) in seen, h
     calls = []
 

@@ -32,6 +32,20 @@ def test_collision_test_known_answers():
         PL.hybrid_astar([0.0, 4.0, 0.0], S.PARALLEL["xF"][:3], v, A, b)
 
 
+@pytest.mark.parametrize("k, bad", [(0, np.nan), (1, np.nan), (2, np.nan), (2, np.inf), (2, -np.inf), (0, np.inf), (1, -np.inf)])
+def test_a_pose_that_is_not_a_number_collides(k, bad):
+    """The host planner refuses no pose at its door (the device planner does): in a field with an obstacle a NaN or an infinity in the pose counts as a collision, for the
+    exported test and as a start or a goal of the search (return code -2), never as a free pose to search from."""
+    A, b, v = S.scenario_hrep(S.PARALLEL)
+    pose = np.array(S.PARALLEL["x0"][:3], float)
+    assert PL.collides(pose, v, A, b) is False      # (the pose the case is made from is free)
+    pose[k] = bad
+    assert PL.collides(pose, v, A, b) is True
+    for start, goal in ((pose, S.PARALLEL["xF"][:3]), (S.PARALLEL["x0"][:3], pose)):
+        with pytest.raises(ValueError, match="collides"):
+            PL.hybrid_astar(start, goal, v, A, b)
+
+
 def _overlap_area2(pose, rows_A, rows_b, ego, margin):
     """twice the area of (car rectangle inflated by margin) cut by the half-planes rows_A p <= rows_b: the definition of the planner's collision test, in numpy"""
     x, y, yaw = pose; c, s = np.cos(yaw), np.sin(yaw); f, l, r, rt = (e + margin for e in ego)

@@ -337,7 +337,7 @@ def test_host_build_goes_through_the_one_rule(tmp_path, monkeypatch):
             assert os.path.exists(os.path.join(os.path.dirname(f), inc)), (f, inc)
             todo.append(os.path.realpath(os.path.join(os.path.dirname(f), inc)))
     csrc = os.path.join(ROOT, "obca_amd", "csrc")
-    for h in (os.path.join(csrc, "obca_hybrid.h"), os.path.join(ROOT, "include", "obca_plan_scenes.h"), os.path.join(ROOT, "include", "obca_plan_device.h")):
+    for h in (os.path.join(csrc, "obca_hybrid.h"), os.path.join(csrc, "obca_plan_geom.h"), os.path.join(ROOT, "include", "obca_plan_scenes.h"), os.path.join(ROOT, "include", "obca_plan_device.h")):
         assert os.path.realpath(h) in seen, h
     assert os.path.realpath(os.path.join(csrc, "obca_solver.h")) not in seen
     calls = []
