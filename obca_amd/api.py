@@ -293,6 +293,14 @@ def _norm_obstacles(B, vOb, A, b):
     return np.full(B, len(v), np.int32), np.tile(v, B), np.tile(A, (B, 1)), np.tile(b, B)
 
 
+def _selection(select):
+    """the instances `select` of a batch as the ABI takes them: a boolean mask or an index array -> int32 indices; None stays None, and the caller says what "all" means"""
+    if select is None:
+        return None
+    sel = np.asarray(select)
+    return np.flatnonzero(sel).astype(np.int32) if sel.dtype == bool else np.ascontiguousarray(sel, np.int32).ravel()
+
+
 def _path_arrays(paths, dirs, counts, B):
     """the planner's dense output as the ABI takes it: paths (B, cap, 3) float64, dirs (B, cap) int32, counts (B,) int32 -- arrays of that kind pass unconverted"""
     paths = _in(paths); dirs = _in(dirs, np.int32); counts = _in(counts, np.int32)
@@ -373,17 +381,42 @@ class _DeviceBatch(_Handle):
         getattr(_load(), f"{self._c}_scratch_bytes")(self._h, C.byref(v))
         return v.value
 
+    def _floats(self, name, n=1):
+        """what obca_[quad_]batch_<name> writes through its n `float *`: HIP-event durations [ms]; one number for n = 1, else a tuple"""
+        v = [C.c_float(0) for _ in range(n)]
+        self._call(name, *map(C.byref, v))
+        return v[0].value if n == 1 else tuple(x.value for x in v)
+
     def validate_ms(self):
         """HIP-event duration of the last validate kernel"""
-        a = C.c_float(0)
-        self._call("validate_ms", C.byref(a))
-        return a.value
+        return self._floats("validate_ms")
 
     def clearance_ms(self):
         """HIP-event duration of the last clearance kernel"""
-        a = C.c_float(0)
-        self._call("clearance_ms", C.byref(a))
-        return a.value
+        return self._floats("clearance_ms")
+
+    def _refine_into(self, entry, limit, extra, select, factor, into):
+        """What Batch.refine and QuadBatch.refine share: the selection (None: all) checked against the batch, the factor against `limit`, the destination (`into`, or a new
+        batch of this kind, closed again if the call fails) and the call of `entry` with its one own argument `extra`.  Returns (destination, selection, status)."""
+        sel = _selection(select)
+        sel = np.arange(self.B, dtype=np.int32) if sel is None else sel
+        n = int(sel.size); factor = int(factor)
+        if n < 1:
+            raise ObcaError("refine: the selection is empty")
+        if sel.min() < 0 or sel.max() >= self.B:
+            raise ObcaError(f"refine: an index outside 0 .. {self.B - 1}")
+        if into is None and not (1 <= factor <= limit):
+            raise ObcaError(f"refine: need 1 <= factor <= {limit}")
+        dst = into if into is not None else type(self)(self.ctx, n, factor * self.N)
+        st = np.zeros(n, np.int32)
+        try:
+            self.ctx._check(getattr(_load(), entry)(dst._h, self._h, factor, extra, sel, n, st), entry)
+        except ObcaError:
+            if into is None:
+                dst.close()
+            raise
+        dst.B = n
+        return dst, sel, st
 
 
 class Batch(_DeviceBatch):
@@ -413,9 +446,7 @@ class Batch(_DeviceBatch):
 
     def path_ws_ms(self):
         """HIP-event duration of the last set_path_warm_start kernel"""
-        a = C.c_float(0)
-        self._call("path_ws_ms", C.byref(a))
-        return a.value
+        return self._floats("path_ws_ms")
 
     def plan_warm_start(self, bucket_width=None, cap=1024, v_nom=0.5, smooth=False, use_xF=True, **planner_options):
         """The resident route (obca_batch_plan_warm_start): every instance of the uploaded batch is planned ON THE DEVICE in its own obstacle field -- put together there
@@ -424,9 +455,7 @@ class Batch(_DeviceBatch):
         planner.scene_astar_many takes them (planner.DEFAULT_OPTS); bucket_width, cap: scene_astar_batch's (cap <= PATH_WS_MAXNODES); v_nom, smooth, use_xF:
         set_path_warm_start's.  Returns (counts, status, expansions, rounds), (B,) int32 each: counts as scene_astar_batch (HYBRID_STATUS), status as set_path_warm_start
         (PATH_WS_STATUS; an instance with a negative one keeps what was uploaded)."""
-        from . import planner
-        o = dict(planner.DEFAULT_OPTS); o.update(planner_options)
-        opts = np.array([o[k] for k in planner.DEFAULT_OPTS], float)
+        opts = planner._opts_array(planner_options)
         cnt, st, nexp, rounds = (np.zeros(self.B, np.int32) for _ in range(4))
         self._call("plan_warm_start", opts, len(opts), 0.0 if bucket_width is None else float(bucket_width), int(cap), bool(use_xF), float(v_nom), 0.3 if smooth else 0.0,
                    cnt, st, nexp, rounds)
@@ -434,9 +463,7 @@ class Batch(_DeviceBatch):
 
     def plan_ms(self):
         """HIP-event durations (pack, search, ws) of the three kernels of the last plan_warm_start [ms]"""
-        a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
-        self._call("plan_ms", C.byref(a), C.byref(b), C.byref(c))
-        return a.value, b.value, c.value
+        return self._floats("plan_ms", 3)
 
     def plan_paths(self):
         """What the last plan_warm_start planned, for plots and tests: (paths (B, cap, 3), dirs (B, cap), inst (B, 10) -- the instance records the packing kernel wrote:
@@ -464,9 +491,7 @@ class Batch(_DeviceBatch):
 
     def kernel_ms(self):
         """(ipm_ms, dualws_ms) of the last solve, measured with HIP events on the launch stream."""
-        a, b = C.c_float(0), C.c_float(0)
-        self._call("kernel_ms", C.byref(a), C.byref(b))
-        return a.value, b.value
+        return self._floats("kernel_ms", 2)
 
     def last_schedule(self):
         """(ipm launches, slice passes) of the last solve: (1, 0) single launch, (2, q) the two-launch schedule with a q-pass first slice"""
@@ -504,35 +529,14 @@ class Batch(_DeviceBatch):
         safer one).  into: a Batch of this context with horizon factor * N and room for the selection; None: a new one.  Returns (batch, status) with status (n,) int32,
         REFINE_STATUS: 0 refined from the solution, 1 from the start iterate (the last solve failed or left non-finite numbers), -1 zero start.  The result is uploaded, not
         solved; only `status` crosses the bus."""
-        if select is None:
-            sel = np.arange(self.B, dtype=np.int32)
-        else:
-            sel = np.asarray(select)
-            sel = np.flatnonzero(sel).astype(np.int32) if sel.dtype == bool else np.ascontiguousarray(sel, np.int32).ravel()
-        n = int(sel.size); factor = int(factor)
-        if n < 1:
-            raise ObcaError("refine: the selection is empty")
-        if sel.min() < 0 or sel.max() >= self.B:
-            raise ObcaError(f"refine: an index outside 0 .. {self.B - 1}")
-        if into is None and not (1 <= factor <= REFINE_MAXFACTOR):
-            raise ObcaError(f"refine: need 1 <= factor <= {REFINE_MAXFACTOR}")
-        dst = into if into is not None else Batch(self.ctx, n, factor * self.N)
-        st = np.zeros(n, np.int32)
-        try:
-            self.ctx._check(_load().obca_batch_refine_into(dst._h, self._h, factor, int(duals), sel, n, st), "obca_batch_refine_into")
-        except ObcaError:
-            if into is None:
-                dst.close()
-            raise
-        dst.B = n; dst.nObs = self.nObs[sel]; dst.Ms = self.Ms[sel]
+        dst, sel, st = self._refine_into("obca_batch_refine_into", REFINE_MAXFACTOR, int(duals), select, factor, into)
+        dst.nObs = self.nObs[sel]; dst.Ms = self.Ms[sel]
         ends = np.cumsum(self.nObs); dst.vflat = np.concatenate([self.vflat[ends[i] - self.nObs[i]:ends[i]] for i in sel.tolist()])
         return dst, st
 
     def refine_ms(self):
         """HIP-event duration of the last refine kernel that wrote into THIS batch (the destination of refine)"""
-        a = C.c_float(0)
-        self._call("refine_ms", C.byref(a))
-        return a.value
+        return self._floats("refine_ms")
 
 
 def hybrid_configure(slots=0, max_nodes=0, max_chunks=0, device=0):
@@ -541,31 +545,40 @@ def hybrid_configure(slots=0, max_nodes=0, max_chunks=0, device=0):
     ctx._check(_load().obca_hybrid_configure(ctx._h, int(slots), int(max_nodes), int(max_chunks)), "obca_hybrid_configure")
 
 
+def _context_ms(entry, device):
+    """the HIP-event duration [ms] that `entry` reports for the context of `device`"""
+    ctx = _ctx(device); a = C.c_float(0)
+    ctx._check(getattr(_load(), entry)(ctx._h, C.byref(a)), entry)
+    return a.value
+
+
 def hybrid_ms(device=0):
     """HIP-event duration of the last search kernel of the context's device planner [ms]"""
-    ctx = _ctx(device); a = C.c_float(0)
-    ctx._check(_load().obca_hybrid_ms(ctx._h, C.byref(a)), "obca_hybrid_ms")
-    return a.value
+    return _context_ms("obca_hybrid_ms", device)
+
+
+def _astar_batch(entry, field, starts, goals, ego, L, XYbounds, opts, bucket_width, cap, device):
+    """what hybrid_astar_batch and scene_astar_batch share; `field`: the obstacle arguments as `entry` takes them, marshalled"""
+    s = np.ascontiguousarray(np.asarray(starts, float)[:, :3]); g = np.ascontiguousarray(np.asarray(goals, float)[:, :3]); B = len(s); cap = int(cap)
+    o = None if opts is None else np.ascontiguousarray(opts, float)
+    paths = np.zeros((B, max(cap, 0), 3)); dirs = np.zeros((B, max(cap, 0)), np.int32); cnt = np.zeros(B, np.int32); nexp = np.zeros(B, np.int32); rounds = np.zeros(B, np.int32)
+    ctx = _ctx(device)
+    rc = getattr(_load(), entry)(ctx._h, B, s, g, *field, _in(ego), float(L), _in(XYbounds), o, 0 if o is None else len(o),
+                                 0.0 if bucket_width is None else float(bucket_width), paths, dirs, cap, cnt, nexp, rounds)
+    ctx._check(rc, entry)
+    return paths, dirs, cnt, nexp, rounds
 
 
 def hybrid_astar_batch(starts, goals, vOb, A, b, ego, L, XYbounds, opts=None, bucket_width=None, cap=1024, device=0):
     """obca_hybrid_astar_batch as it is: B Hybrid A* searches in one obstacle field on the GPU, one workgroup each.  starts, goals (B, >= 3); opts: the option array of
     obca_plan.h or None.  Returns (paths (B, cap, 3), dirs (B, cap), counts (B,), expansions (B,), rounds (B,)); counts as the host planner's, -3: HYBRID_STATUS."""
-    s = np.ascontiguousarray(np.asarray(starts, float)[:, :3]); g = np.ascontiguousarray(np.asarray(goals, float)[:, :3]); B = len(s); cap = int(cap)
-    vOb = np.ascontiguousarray(vOb, np.int32); o = None if opts is None else np.ascontiguousarray(opts, float)
-    paths = np.zeros((B, max(cap, 0), 3)); dirs = np.zeros((B, max(cap, 0)), np.int32); cnt = np.zeros(B, np.int32); nexp = np.zeros(B, np.int32); rounds = np.zeros(B, np.int32)
-    ctx = _ctx(device)
-    rc = _load().obca_hybrid_astar_batch(ctx._h, B, s, g, len(vOb), vOb, _in(A), _in(b), _in(ego), float(L), _in(XYbounds), o, 0 if o is None else len(o),
-                                         0.0 if bucket_width is None else float(bucket_width), paths, dirs, cap, cnt, nexp, rounds)
-    ctx._check(rc, "obca_hybrid_astar_batch")
-    return paths, dirs, cnt, nexp, rounds
+    vOb = np.ascontiguousarray(vOb, np.int32)
+    return _astar_batch("obca_hybrid_astar_batch", (len(vOb), vOb, _in(A), _in(b)), starts, goals, ego, L, XYbounds, opts, bucket_width, cap, device)
 
 
 def scene_ms(device=0):
     """HIP-event duration of the last per-instance search kernel (scene_astar_batch) of the context's device planner [ms]; hybrid_ms keeps the shared-field one"""
-    ctx = _ctx(device); a = C.c_float(0)
-    ctx._check(_load().obca_scene_astar_ms(ctx._h, C.byref(a)), "obca_scene_astar_ms")
-    return a.value
+    return _context_ms("obca_scene_astar_ms", device)
 
 
 def scene_astar_batch(starts, goals, vOb, A, b, ego, L, XYbounds, opts=None, bucket_width=None, cap=1024, device=0):
@@ -573,15 +586,8 @@ def scene_astar_batch(starts, goals, vOb, A, b, ego, L, XYbounds, opts=None, buc
     (taken as they are) or one field (broadcast), as everywhere here (_norm_obstacles); an instance without obstacles is a free field inside XYbounds.  The rest is
     hybrid_astar_batch's: starts, goals (B, >= 3), opts, the slots of hybrid_configure, the return value (paths (B, cap, 3), dirs (B, cap), counts (B,), expansions (B,),
     rounds (B,)) and the counts codes (HYBRID_STATUS; -2: the pose collides with the instance's own field)."""
-    s = np.ascontiguousarray(np.asarray(starts, float)[:, :3]); g = np.ascontiguousarray(np.asarray(goals, float)[:, :3]); B = len(s); cap = int(cap)
-    nObs, vflat, Aflat, bflat = _norm_obstacles(B, vOb, A, b)
-    o = None if opts is None else np.ascontiguousarray(opts, float)
-    paths = np.zeros((B, max(cap, 0), 3)); dirs = np.zeros((B, max(cap, 0)), np.int32); cnt = np.zeros(B, np.int32); nexp = np.zeros(B, np.int32); rounds = np.zeros(B, np.int32)
-    ctx = _ctx(device)
-    rc = _load().obca_scene_astar_batch(ctx._h, B, s, g, _in(nObs, np.int32), _in(vflat, np.int32), _in(Aflat), _in(bflat), _in(ego), float(L), _in(XYbounds), o,
-                                        0 if o is None else len(o), 0.0 if bucket_width is None else float(bucket_width), paths, dirs, cap, cnt, nexp, rounds)
-    ctx._check(rc, "obca_scene_astar_batch")
-    return paths, dirs, cnt, nexp, rounds
+    nObs, vflat, Aflat, bflat = _norm_obstacles(len(starts), vOb, A, b)
+    return _astar_batch("obca_scene_astar_batch", (_in(nObs, np.int32), _in(vflat, np.int32), _in(Aflat), _in(bflat)), starts, goals, ego, L, XYbounds, opts, bucket_width, cap, device)
 
 
 def parking_refine_batch(N, Ts, L, x, u, timeScale=None, factor=2, device=0):
@@ -794,14 +800,9 @@ class QuadBatch(_DeviceBatch):
         timeWS: None (every instance keeps its time scale) or one number > 0 for the planned instances.  Returns (counts, sweeps), (B,) int32 each: counts as
         planner.plan3d_paths (QUAD_PLAN_STATUS: >= 2 way-points, 0, -1, -2, -3) and -4 for an instance that was not selected; an instance with a count below 2 keeps
         its uploaded record to the last bit.  The batch counts as unsolved afterwards."""
-        if select is None:
-            sel, n = None, 0
-        else:
-            sel = np.asarray(select)
-            sel = np.flatnonzero(sel).astype(np.int32) if sel.dtype == bool else np.ascontiguousarray(sel, np.int32).ravel()
-            n = int(sel.size)
-            if n < 1:
-                raise ObcaError("plan_warm_start: the selection is empty")
+        sel = _selection(select); n = 0 if sel is None else int(sel.size)      # (all: NULL, 0; no range check here: the library refuses a bad index)
+        if sel is not None and n < 1:
+            raise ObcaError("plan_warm_start: the selection is empty")
         cnt = np.zeros(self.B, np.int32); sw = np.zeros(self.B, np.int32)
         self._call("grid_plan_warm_start", float(clear), np.ascontiguousarray(room, float), float(res), int(cap), sel, n,
                    None if timeWS is None else np.array([timeWS], float), cnt, sw)
@@ -809,9 +810,7 @@ class QuadBatch(_DeviceBatch):
 
     def plan_ms(self):
         """HIP-event duration of the last plan_warm_start's kernel [ms]"""
-        a = C.c_float(0)
-        self._call("grid_plan_ms", C.byref(a))
-        return a.value
+        return self._floats("grid_plan_ms")
 
     def plan_paths(self):
         """The way-points of the last plan_warm_start, for plots and tests: (B, cap, 3) -- start point, grid nodes, goal point; the rows behind an instance's count, and all
@@ -831,9 +830,7 @@ class QuadBatch(_DeviceBatch):
         return xws, tws
 
     def kernel_ms(self):
-        a = C.c_float(0)
-        self._call("kernel_ms", C.byref(a))
-        return a.value
+        return self._floats("kernel_ms")
 
     def download(self):
         B, N = self.B, self.N
@@ -861,34 +858,12 @@ class QuadBatch(_DeviceBatch):
         horizon factor * N and room for the selection; None: a new one.  Returns (batch, status) with status (n,) int32, QUAD_REFINE_STATUS: 0 refined from the solution,
         1 interpolated from the uploaded warm start (the last solve failed or left non-finite numbers), -1 zero warm start.  The result is uploaded, not solved; only the
         selection and `status` cross the bus."""
-        if select is None:
-            sel = np.arange(self.B, dtype=np.int32)
-        else:
-            sel = np.asarray(select)
-            sel = np.flatnonzero(sel).astype(np.int32) if sel.dtype == bool else np.ascontiguousarray(sel, np.int32).ravel()
-        n = int(sel.size); factor = int(factor)
-        if n < 1:
-            raise ObcaError("refine: the selection is empty")
-        if sel.min() < 0 or sel.max() >= self.B:
-            raise ObcaError(f"refine: an index outside 0 .. {self.B - 1}")
-        if into is None and not (1 <= factor <= QUAD_SUBDIVIDE_MAXFACTOR):
-            raise ObcaError(f"refine: need 1 <= factor <= {QUAD_SUBDIVIDE_MAXFACTOR}")
-        dst = into if into is not None else QuadBatch(self.ctx, n, factor * self.N)
-        st = np.zeros(n, np.int32)
-        try:
-            self.ctx._check(_load().obca_quad_batch_subdivide_into(dst._h, self._h, factor, float(margin), sel, n, st), "obca_quad_batch_subdivide_into")
-        except ObcaError:
-            if into is None:
-                dst.close()
-            raise
-        dst.B = n
+        dst, _, st = self._refine_into("obca_quad_batch_subdivide_into", QUAD_SUBDIVIDE_MAXFACTOR, float(margin), select, factor, into)
         return dst, st
 
     def refine_ms(self):
         """HIP-event duration of the last refine kernel that wrote into THIS batch (the destination of refine)"""
-        a = C.c_float(0)
-        self._call("subdivide_ms", C.byref(a))
-        return a.value
+        return self._floats("subdivide_ms")
 
 
 def quadcopter_refine_batch(x, timeScale, Ts, factor=2, device=0):

@@ -38,10 +38,15 @@ REFERENCE_GRID = dict(xy_res=0.3, yaw_res_deg=5.0, steer_samples=2)      # (too 
 # mean 43.4 / worst 400 iterations at 1.0, 37.4 / 71 at 0.85, 40.6 / 90 without the expansion), hence 0.85.
 
 
+def _opts_array(kw):
+    """the option array of obca_plan.h: DEFAULT_OPTS with the options given by name, in its order"""
+    o = dict(DEFAULT_OPTS); o.update(kw)
+    return np.array([o[k] for k in DEFAULT_OPTS], float)
+
+
 def _search_args(vOb, A, b, ego, L, XYbounds, kw):
     """the obstacle field and the options of a Hybrid A* call as the ABI orders them: nOb, vOb, A, b, ego, L, XYbounds, opts, nopts"""
-    o = dict(DEFAULT_OPTS); o.update(kw)
-    opts = np.array([o[k] for k in DEFAULT_OPTS], float)
+    opts = _opts_array(kw)
     vOb = np.ascontiguousarray(vOb, np.int32)
     return (len(vOb), vOb, *(np.ascontiguousarray(a, float) for a in (A, b, ego)), L, np.ascontiguousarray(XYbounds, float), opts, len(opts))
 
@@ -285,13 +290,92 @@ def _hybrid_astar_dense(starts, goals, vOb, A, b, ego, L, XYbounds, threads, cap
     return s, g, paths, dirs, cnt, nexp
 
 
-def _hybrid_astar_dense_device(starts, goals, vOb, A, b, ego, L, XYbounds, cap, kw, device, bucket_width=None):
-    """obca_hybrid_astar_batch (include/obca_plan_device.h) with the return value of _hybrid_astar_dense: the searches run on the GPU, one workgroup each"""
+# ---------------------------------------------------------------- the batch routes: one search, the long paths searched again, one of two consumers
+# A backend runs the searches of the instances idx with room for cap nodes per path: (s (B, 3), g (B, 3), idx, cap) -> (paths (n, cap, 3), dirs (n, cap), counts (n,),
+# expansions (n,)).  A count of -3 (that search outgrew its slot -- api.hybrid_configure) ends its instance alone and is "no path" for the consumers below.
+def _host_backend(vOb, A, b, ego, L, XYbounds, kw, threads):
+    """the host threads of the planner library (obca_plan_hybrid_astar_batch2)"""
+    return lambda s, g, idx, cap: _hybrid_astar_dense(s[idx], g[idx], vOb, A, b, ego, L, XYbounds, threads, cap, kw)[2:]
+
+
+def _device_backend(vOb, A, b, ego, L, XYbounds, kw, device, bucket_width):
+    """one obstacle field on the GPU, one workgroup per search (obca_hybrid_astar_batch, include/obca_plan_device.h)"""
     from . import api
-    s = np.ascontiguousarray(np.asarray(starts, float)[:, :3]); g = np.ascontiguousarray(np.asarray(goals, float)[:, :3])
-    nOb, v, A_, b_, ego_, L_, xy, opts, _ = _search_args(vOb, A, b, ego, L, XYbounds, kw)
-    paths, dirs, cnt, nexp, _ = api.hybrid_astar_batch(s, g, v, A_, b_, ego_, L_, xy, opts, bucket_width, cap, device)
-    return s, g, paths, dirs, cnt, nexp      # (cnt -3: that search outgrew its slot -- api.hybrid_configure; it ends alone and counts as "no path" for the callers below)
+    _, v, A_, b_, ego_, L_, xy, opts, _ = _search_args(vOb, A, b, ego, L, XYbounds, kw)
+    return lambda s, g, idx, cap: api.hybrid_astar_batch(s[idx], g[idx], v, A_, b_, ego_, L_, xy, opts, bucket_width, cap, device)[:4]
+
+
+def _fields_of(vOb, A, b, idx, B):
+    """the obstacle fields of the instances idx: per-instance lists are cut, one shared field stays what it is"""
+    if isinstance(vOb, (list, tuple)) and len(vOb) == B and np.ndim(vOb[0]) >= 1:
+        return [vOb[i] for i in idx], [A[i] for i in idx], [b[i] for i in idx]
+    return vOb, A, b
+
+
+def _scene_backend(vOb, A, b, ego, L, XYbounds, kw, device, bucket_width):
+    """every search on the GPU in the obstacle field of its own instance (obca_scene_astar_batch, include/obca_plan_scenes.h)"""
+    from . import api
+    opts = _opts_array(kw)
+    return lambda s, g, idx, cap: api.scene_astar_batch(s[idx], g[idx], *_fields_of(vOb, A, b, idx, len(s)), ego, L, XYbounds, opts, bucket_width, cap, device)[:4]
+
+
+def _found(paths, dirs, cnt, nexp, i):
+    """(path, dir, expansions) of instance i of a dense result, None without a path"""
+    return (paths[i, :cnt[i]].copy(), dirs[i, :cnt[i]].copy(), int(nexp[i])) if cnt[i] > 0 else None
+
+
+def _in_one_call(backend):
+    """the second search of the device routes: the backend once more for the long paths, with room for 20000 nodes"""
+    def second(s, g, long_):
+        found = backend(s, g, long_, 20000)
+        return [_found(*found, j) for j in range(len(long_))]
+    return second
+
+
+def _one_by_one(vOb, A, b, ego, L, XYbounds, kw):
+    """the second search of the host route: single calls (which also report bad arguments); a start or goal pose that collides is no path"""
+    def one(start, goal):
+        try:
+            return hybrid_astar(start, goal, vOb, A, b, ego, L, XYbounds, **kw)
+        except ValueError:
+            return None
+    return lambda s, g, long_: [one(s[i], g[i]) for i in long_]
+
+
+def _shared_field_route(field, kw, device, bucket_width, threads):
+    """(backend, second search) of the routes in one obstacle field: the device planner where `device` says so, else the host's threads and its single calls"""
+    if device is None:
+        return _host_backend(*field, kw, threads), _one_by_one(*field, kw)
+    backend = _device_backend(*field, kw, device, bucket_width)
+    return backend, _in_one_call(backend)
+
+
+def _again(second, s, g, cnt):
+    """the instances whose path has more than cap nodes (count -1), searched again: pairs (instance, (path, dir, expansions) / None)"""
+    long_ = np.flatnonzero(cnt == -1)
+    return zip(long_.tolist(), second(s, g, long_)) if len(long_) else ()
+
+
+def _paths_many(backend, second, starts, goals, cap):
+    """a list of (path, dir, expansions) / None"""
+    s, g = (np.ascontiguousarray(np.asarray(p, float)[:, :3]) for p in (starts, goals))
+    found = backend(s, g, np.arange(len(s)), cap)
+    out = [_found(*found, i) for i in range(len(s))]
+    for i, r in _again(second, s, g, found[2]):
+        out[i] = r
+    return out
+
+
+def _warm_starts_many(backend, second, x0, xF, cap, N, device, **ws):
+    """a list of (Ts, xWS, uWS) / None: path_to_warm_start_many on the dense arrays (on `device`), numpy's path_to_warm_start on the paths that were searched again.
+    ws: what both take of v_nom, L and smooth"""
+    s, g = (np.ascontiguousarray(np.asarray(p, float)[:, :3]) for p in (x0, xF))
+    paths, dirs, cnt, _ = backend(s, g, np.arange(len(s)), cap)
+    Ts, xWS, uWS, ok = path_to_warm_start_many(paths, dirs, cnt, N, xF, device=device, **ws)
+    out = [(float(Ts[i]), xWS[i], uWS[i]) if ok[i] else None for i in range(len(cnt))]
+    for i, r in _again(second, s, g, cnt):
+        out[i] = None if r is None else path_to_warm_start(r[0], r[1], N, xF[i], **ws)
+    return out
 
 
 def hybrid_astar_many(starts, goals, vOb, A, b, ego=S.EGO, L=S.L_WHEELBASE, XYbounds=S.XYBOUNDS, threads=0, cap=1024, device=None, bucket_width=None, **kw):
@@ -299,26 +383,7 @@ def hybrid_astar_many(starts, goals, vOb, A, b, ego=S.EGO, L=S.L_WHEELBASE, XYbo
     (no path, or the start / goal pose collides).  device (an index or an api.Context): the searches run on that GPU instead (obca_hybrid_astar_batch: a round-synchronous
     Hybrid A* with open-set buckets of width bucket_width, None = the library's default); a path of more than cap nodes is searched again there with room for 20000; an
     instance whose search outgrew its slot (count -3, api.HYBRID_STATUS) is None like one without a path, the others keep their results."""
-    if device is not None:
-        s, g, paths, dirs, cnt, nexp = _hybrid_astar_dense_device(starts, goals, vOb, A, b, ego, L, XYbounds, cap, kw, device, bucket_width)
-        long_ = np.flatnonzero(cnt == -1)
-        out = [(paths[i, :cnt[i]].copy(), dirs[i, :cnt[i]].copy(), int(nexp[i])) if cnt[i] > 0 else None for i in range(len(s))]
-        if len(long_):
-            _, _, p2, d2, c2, n2 = _hybrid_astar_dense_device(s[long_], g[long_], vOb, A, b, ego, L, XYbounds, 20000, kw, device, bucket_width)
-            for j, i in enumerate(long_):
-                out[i] = (p2[j, :c2[j]].copy(), d2[j, :c2[j]].copy(), int(n2[j])) if c2[j] > 0 else None
-        return out
-    s, g, paths, dirs, cnt, nexp = _hybrid_astar_dense(starts, goals, vOb, A, b, ego, L, XYbounds, threads, cap, kw); B = len(s)
-    out = []
-    for i in range(B):
-        if cnt[i] == -1:          # a path longer than cap nodes (or bad arguments, which the single call reports)
-            try:
-                out.append(hybrid_astar(s[i], g[i], vOb, A, b, ego, L, XYbounds, **kw))
-            except ValueError:
-                out.append(None)
-        else:
-            out.append((paths[i, :cnt[i]].copy(), dirs[i, :cnt[i]].copy(), int(nexp[i])) if cnt[i] > 0 else None)
-    return out
+    return _paths_many(*_shared_field_route((vOb, A, b, ego, L, XYbounds), kw, device, bucket_width, threads), starts, goals, cap)
 
 
 def warm_start_many(sc, x0, xF, N, workers=None, smooth=False, device=None, search="host", bucket_width=None, **kw):
@@ -341,49 +406,9 @@ def warm_start_many(sc, x0, xF, N, workers=None, smooth=False, device=None, sear
     if device is None:
         res = hybrid_astar_many(x0[:, :3], xF[:, :3], vrows, A, b, threads=workers or effective_cpus(), **o)
         return [None if r is None else path_to_warm_start(r[0], r[1], N, xF[i], v_nom=v_nom, smooth=smooth) for i, r in enumerate(res)]
-    geo = dict(ego=o.pop("ego", S.EGO), L=o.pop("L", S.L_WHEELBASE), XYbounds=o.pop("XYbounds", S.XYBOUNDS)); cap = o.pop("cap", 1024)      # hybrid_astar_many's named parameters
-    if search == "device":
-        s, g, paths, dirs, cnt, _ = _hybrid_astar_dense_device(x0[:, :3], xF[:, :3], vrows, A, b, geo["ego"], geo["L"], geo["XYbounds"], cap, o, device, bucket_width)
-    else:
-        s, g, paths, dirs, cnt, _ = _hybrid_astar_dense(x0[:, :3], xF[:, :3], vrows, A, b, geo["ego"], geo["L"], geo["XYbounds"], workers or effective_cpus(), cap, o)
-    Ts, xWS, uWS, ok = path_to_warm_start_many(paths, dirs, cnt, N, xF, v_nom=v_nom, smooth=smooth, device=device)
-    out = [(float(Ts[i]), xWS[i], uWS[i]) if ok[i] else None for i in range(len(cnt))]
-    long_ = np.flatnonzero(cnt == -1)
-    if search == "device" and len(long_):      # longer than cap nodes: searched again where the caller asked for, with room for 20000 nodes; resampled by numpy
-        _, _, p2, d2, c2, _ = _hybrid_astar_dense_device(s[long_], g[long_], vrows, A, b, geo["ego"], geo["L"], geo["XYbounds"], 20000, o, device, bucket_width)
-        for j, i in enumerate(long_):
-            out[i] = None if c2[j] <= 0 else path_to_warm_start(p2[j, :c2[j]], d2[j, :c2[j]], N, xF[i], v_nom=v_nom, smooth=smooth)
-        return out
-    for i in long_:
-        try:
-            r = hybrid_astar(s[i], g[i], vrows, A, b, **geo, **o)
-        except ValueError:
-            r = None
-        out[i] = None if r is None else path_to_warm_start(r[0], r[1], N, xF[i], v_nom=v_nom, smooth=smooth)
-    return out
-
-
-def _scene_dense(starts, goals, vOb, A, b, ego, L, XYbounds, cap, kw, device, bucket_width=None):
-    """obca_scene_astar_batch (include/obca_plan_scenes.h) with the return value of _hybrid_astar_dense: every search on the GPU, in the field of its own instance"""
-    from . import api
-    s = np.ascontiguousarray(np.asarray(starts, float)[:, :3]); g = np.ascontiguousarray(np.asarray(goals, float)[:, :3])
-    o = dict(DEFAULT_OPTS); o.update(kw)
-    opts = np.array([o[k] for k in DEFAULT_OPTS], float)
-    paths, dirs, cnt, nexp, _ = api.scene_astar_batch(s, g, vOb, A, b, ego, L, XYbounds, opts, bucket_width, cap, device)
-    return s, g, paths, dirs, cnt, nexp
-
-
-def _fields_of(vOb, A, b, idx, B):
-    """the obstacle fields of the instances idx: per-instance lists are cut, one shared field stays what it is"""
-    if isinstance(vOb, (list, tuple)) and len(vOb) == B and np.ndim(vOb[0]) >= 1:
-        return [vOb[i] for i in idx], [A[i] for i in idx], [b[i] for i in idx]
-    return vOb, A, b
-
-
-def _scene_again(s, g, vOb, A, b, ego, L, XYbounds, kw, device, bucket_width, long_):
-    """the searches whose path has more than cap nodes, once more on the device with room for 20000"""
-    v2, A2, b2 = _fields_of(vOb, A, b, long_, len(s))
-    return _scene_dense(s[long_], g[long_], v2, A2, b2, ego, L, XYbounds, 20000, kw, device, bucket_width)
+    field = (vrows, A, b, o.pop("ego", S.EGO), o.pop("L", S.L_WHEELBASE), o.pop("XYbounds", S.XYBOUNDS)); cap = o.pop("cap", 1024)      # hybrid_astar_many's named parameters
+    route = _shared_field_route(field, o, device if search == "device" else None, bucket_width, workers or effective_cpus())
+    return _warm_starts_many(*route, x0, xF, cap, N, device, v_nom=v_nom, smooth=smooth)      # (L reaches the search alone: the resampling keeps its default wheelbase)
 
 
 def scene_astar_many(starts, goals, vOb, A, b, ego=S.EGO, L=S.L_WHEELBASE, XYbounds=S.XYBOUNDS, device=0, bucket_width=None, cap=1024, **kw):
@@ -391,14 +416,8 @@ def scene_astar_many(starts, goals, vOb, A, b, ego=S.EGO, L=S.L_WHEELBASE, XYbou
     (path, dir, expansions) / None -- hybrid_astar_many(device=...)'s contract: a path of more than cap nodes is searched again on the device with room for 20000; an
     instance without a path, with a start or goal pose that collides with its own field, or whose search outgrew its slot (count -3, api.HYBRID_STATUS) is None, alone.
     There is no host fallback."""
-    s, g, paths, dirs, cnt, nexp = _scene_dense(starts, goals, vOb, A, b, ego, L, XYbounds, cap, kw, device, bucket_width)
-    out = [(paths[i, :cnt[i]].copy(), dirs[i, :cnt[i]].copy(), int(nexp[i])) if cnt[i] > 0 else None for i in range(len(s))]
-    long_ = np.flatnonzero(cnt == -1)
-    if len(long_):
-        _, _, p2, d2, c2, n2 = _scene_again(s, g, vOb, A, b, ego, L, XYbounds, kw, device, bucket_width, long_)
-        for j, i in enumerate(long_):
-            out[i] = (p2[j, :c2[j]].copy(), d2[j, :c2[j]].copy(), int(n2[j])) if c2[j] > 0 else None
-    return out
+    backend = _scene_backend(vOb, A, b, ego, L, XYbounds, kw, device, bucket_width)
+    return _paths_many(backend, _in_one_call(backend), starts, goals, cap)
 
 
 def scene_warm_start_many(x0, xF, N, vOb, A, b, device=0, smooth=False, v_nom=0.5, bucket_width=None, **kw):
@@ -406,19 +425,12 @@ def scene_warm_start_many(x0, xF, N, vOb, A, b, device=0, smooth=False, v_nom=0.
     list of (Ts, xWS (N+1, 4), uWS (N, 2)) / None; a path of more than `cap` nodes is searched again on the device and resampled by numpy, as in
     warm_start_many(search="device").  kw: ego, L, XYbounds, cap and the search options."""
     o = dict(kw)
-    geo = dict(ego=o.pop("ego", S.EGO), L=o.pop("L", S.L_WHEELBASE), XYbounds=o.pop("XYbounds", S.XYBOUNDS)); cap = o.pop("cap", 1024)
+    ego, L, XYbounds, cap = o.pop("ego", S.EGO), o.pop("L", S.L_WHEELBASE), o.pop("XYbounds", S.XYBOUNDS), o.pop("cap", 1024)
     x0 = np.asarray(x0, float); xF = np.asarray(xF, float)
     if len(x0) == 0:
         return []
-    s, g, paths, dirs, cnt, _ = _scene_dense(x0[:, :3], xF[:, :3], vOb, A, b, geo["ego"], geo["L"], geo["XYbounds"], cap, o, device, bucket_width)
-    Ts, xWS, uWS, ok = path_to_warm_start_many(paths, dirs, cnt, N, xF, v_nom=v_nom, L=geo["L"], smooth=smooth, device=device)
-    out = [(float(Ts[i]), xWS[i], uWS[i]) if ok[i] else None for i in range(len(cnt))]
-    long_ = np.flatnonzero(cnt == -1)
-    if len(long_):
-        _, _, p2, d2, c2, _ = _scene_again(s, g, vOb, A, b, geo["ego"], geo["L"], geo["XYbounds"], o, device, bucket_width, long_)
-        for j, i in enumerate(long_):
-            out[i] = None if c2[j] <= 0 else path_to_warm_start(p2[j, :c2[j]], d2[j, :c2[j]], N, xF[i], v_nom=v_nom, L=geo["L"], smooth=smooth)
-    return out
+    backend = _scene_backend(vOb, A, b, ego, L, XYbounds, o, device, bucket_width)
+    return _warm_starts_many(backend, _in_one_call(backend), x0, xF, cap, N, device, v_nom=v_nom, L=L, smooth=smooth)
 
 
 # ---------------------------------------------------------------- quadcopter: 3-D grid A* (a_star_3D.jl, mainQuadcopter.jl:108-138)
