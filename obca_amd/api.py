@@ -21,7 +21,7 @@ import time
 import numpy as np
 from . import buildflags, cabi, planner
 from .cabi import Opts      # `typedef struct obca_opts` of include/obca_hip.h, read from the header
-from .validate import VIOL_NAMES, QUAD_VIOL_NAMES, DMIN, CLR_OUT
+from .validate import VIOL_NAMES, QUAD_VIOL_NAMES, DMIN, CLR_OUT, ROLL_OUT
 
 _LIBPATH = os.environ.get("OBCA_HIP_LIBRARY") or buildflags.PIECES["hip"].out   # override: diagnostic builds
 _lib = None
@@ -61,6 +61,7 @@ def _load():
     cabi.bind(_lib, "obca_plan_resident.h")               # ... from the records of an uploaded batch
     cabi.bind(_lib, "obca_plan_resident_check.h")         # ... and the diagnostic that hands out what its packing kernel wrote
     cabi.bind(_lib, "obca_quad_plan_resident.h")          # the quadcopter's grid planner from the records of an uploaded batch
+    cabi.bind(_lib, "obca_rollout.h")                     # solved batches applied to the continuous vehicle models
     return _lib
 
 
@@ -99,6 +100,10 @@ PLAN_RESIDENT_CHECK_EXPORTS = ["obca_batch_packed_block"]      # include/obca_pl
 # (QuadBatch.plan_warm_start, plan_ms, plan_paths), and the read-back of the start a batch will solve from (QuadBatch.warm_start)
 QUAD_PLAN_RESIDENT_EXPORTS = ["obca_quad_batch_grid_plan_warm_start", "obca_quad_batch_grid_plan_ms", "obca_quad_batch_grid_plan_download", "obca_quad_batch_start_download"]
 QUAD_PLAN_SKIPPED = -4      # OBCA_QUAD_PLAN_SKIPPED
+# include/obca_rollout.h: solutions and trajectories on the continuous vehicle models (Batch.rollout, QuadBatch.rollout, rollout_states, rollout_ms, parking_rollout_batch,
+# quadcopter_rollout_batch)
+ROLLOUT_EXPORTS = ["obca_batch_rollout", "obca_batch_rollout_ms", "obca_batch_rollout_states", "obca_parking_rollout_batch", "obca_quad_batch_rollout",
+                   "obca_quad_batch_rollout_ms", "obca_quad_batch_rollout_states", "obca_quadcopter_rollout_batch"]
 QUAD_PLAN_STATUS = {0: "no path", -1: "more way-points than cap", -2: "the start or goal point is blocked, or a coordinate of the record is not finite",
                     -3: "the relaxation hit its sweep bound", -4: "not selected"}
 QUAD_REFINE_STATUS = {0: "refined from the solution", 1: "interpolated from the uploaded warm start (the last solve failed, or its iterate is not finite)",
@@ -209,9 +214,26 @@ def _clearance(B, substeps, nOb, call):
     instance's own obstacles); finite (B,) bool -- False: a non-finite number in the trajectory, the values of that instance are NaN"""
     rec = np.zeros((B, CLR_OUT))
     call(rec)
+    return _clearance_dict(rec, substeps, nOb)
+
+
+def _clearance_dict(rec, substeps, nOb):
+    """the dict of _clearance from records (B, CLR_OUT)"""
     q = rec[:, 2].astype(np.int64); S = int(substeps)
     return dict(min=rec[:, 0], min_nodes=rec[:, 1], sample=q, stage=np.where(q >= 0, q // S, -1), substep=np.where(q >= 0, q % S, -1), obstacle=rec[:, 3].astype(np.int64),
                 below=rec[:, 4].astype(np.int64), samples=rec[:, 5].astype(np.int64), per_obstacle=rec[:, 8:8 + int(nOb)], finite=rec[:, 6] == 0)
+
+
+def _rollout(B, substeps, nOb, call):
+    """the records of a rollout entry point, `call(out)` with out (B, ROLL_OUT), and the dict they are returned in: dev_pos (B,) the largest position deviation of the rolled
+    node states from the trajectory's own over the nodes 1..N, dev_node its node (-1 where not finite); dev_att, dev_vel, dev_rate likewise for attitude, velocity and body
+    rates; end_pos, end_att, end_vel, end_rate the same at node N; restart, substeps as the call had them; finite (B,) bool -- False: a non-finite number in the trajectory
+    or among the rolled states, the values of that instance are NaN; clearance: the dict of _clearance for the rolled samples"""
+    rec = np.zeros((B, ROLL_OUT))
+    call(rec)
+    return dict(dev_pos=rec[:, 1], dev_node=rec[:, 2].astype(np.int64), dev_att=rec[:, 3], dev_vel=rec[:, 4], dev_rate=rec[:, 5], end_pos=rec[:, 6], end_att=rec[:, 7],
+                end_vel=rec[:, 8], end_rate=rec[:, 9], restart=rec[:, 10] != 0, substeps=rec[:, 11].astype(np.int64), finite=rec[:, 0] == 0,
+                clearance=_clearance_dict(rec[:, 16:], substeps, nOb))
 
 
 class _Handle:
@@ -395,6 +417,20 @@ class _DeviceBatch(_Handle):
         """HIP-event duration of the last clearance kernel"""
         return self._floats("clearance_ms")
 
+    def _rollout(self, nOb, substeps, restart, need):
+        return _rollout(self.B, substeps, nOb, lambda out: self._call("rollout", int(substeps), int(restart), float(need), out))
+
+    def rollout_states(self):
+        """The node states of the last rollout(), fetched from the device: (B, N+1, nx), nx = 4 (parking) or 12 (quadcopter); NaN for an instance that was not finite.
+        rollout_states()[:, shift] of a chain-mode rollout is the state the vehicle reaches after `shift` intervals: the x0_new of shift_warm_start(shift, x0_new=...)."""
+        X = np.zeros((self.B, self.N + 1, self._nx))
+        self._call("rollout_states", X)
+        return X
+
+    def rollout_ms(self):
+        """HIP-event duration of the last rollout kernel"""
+        return self._floats("rollout_ms")
+
     def _refine_into(self, entry, limit, extra, select, factor, into):
         """What Batch.refine and QuadBatch.refine share: the selection (None: all) checked against the batch, the factor against `limit`, the destination (`into`, or a new
         batch of this kind, closed again if the call fails) and the call of `entry` with its one own argument `extra`.  Returns (destination, selection, status)."""
@@ -422,6 +458,7 @@ class _DeviceBatch(_Handle):
 class Batch(_DeviceBatch):
     """Device-resident batch: upload once, solve (repeatedly), download."""
     _c = "obca_batch"
+    _nx = 4
 
     def upload(self, x0, xF, Ts, L, ego, XYbounds, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, lWS=None, nWS=None, dist=False):
         """lWS/nWS, when given, are packed per instance as (N+1, M_i) / (N+1, 4 nOb_i) row-major blocks (= the reference's
@@ -513,6 +550,14 @@ class Batch(_DeviceBatch):
         viol (B, 14) in the order of `names` = VIOL_NAMES).  Only these 16 numbers per instance are downloaded."""
         return _verdict(self.B, VIOL_NAMES, lambda *out: self._call("validate", tol, *out), ref_ok=True)
 
+    def rollout(self, substeps=8, restart=False, need=DMIN):
+        """The last solution applied to the CONTINUOUS kinematic bicycle, ON THE DEVICE (obca_batch_rollout; the numpy statement is obca_amd.validate.rollout_parking +
+        rollout_record): u_k held over interval k, classical RK4 with `substeps` steps per interval.  restart=False: the open loop from the solution's first node;
+        True: every interval starts at the solution's own node -- the defect of one interval.  validate() and clearance() measure against the NLP's midpoint rule; this
+        is what the car does.  Returns the dict of _rollout: deviations of the rolled node states from the solution's, and `clearance`, the dict of clearance() for the
+        rolled samples (need: its `need`).  The rolled states stay on the device: rollout_states()."""
+        return self._rollout(int(self.nObs.max()), substeps, restart, need)
+
     def clearance(self, substeps=8, need=DMIN):
         """Clearance of the last solution BETWEEN its nodes, ON THE DEVICE (obca_batch_clearance; the numpy statement is obca_amd.validate.parking_samples + a DualMultWS
         distance per pose): every interval is sampled `substeps` times with the discretisation's own partial step and the car's distance to every obstacle computed anew,
@@ -543,6 +588,21 @@ def hybrid_configure(slots=0, max_nodes=0, max_chunks=0, device=0):
     """the slots of the device planner of a context (obca_hybrid_configure): searches in flight, nodes and bucket chunks per search; 0 = the default"""
     ctx = _ctx(device)
     ctx._check(_load().obca_hybrid_configure(ctx._h, int(slots), int(max_nodes), int(max_chunks)), "obca_hybrid_configure")
+
+
+def parking_rollout_batch(N, Ts, L, ego, vOb, A, b, x, u, timeScale=None, substeps=8, restart=False, need=DMIN, device=0, states=True):
+    """Batch.rollout for arbitrary trajectories (obca_parking_rollout_batch): the arguments of parking_clearance_batch, then the mode.  Returns the dict of Batch.rollout,
+    with `states` (B, N+1, 4), the rolled node states, unless states=False."""
+    x = np.asarray(x, float); u = np.asarray(u, float); N = int(N); B = x.shape[0]
+    if x.shape != (B, 4, N + 1) or u.shape != (B, 2, N):
+        raise ObcaError(f"x must be (B,4,N+1) and u (B,2,N); got {x.shape}, {u.shape}")
+    ctx = _ctx(device)
+    nObs, vflat, Aflat, bflat = _norm_obstacles(B, vOb, A, b)
+    ins = (_per_instance(Ts, B), L, _in(ego), _in(nObs, np.int32), _in(vflat, np.int32), _in(Aflat), _in(bflat), _in(np.transpose(x, (0, 2, 1))), _in(np.transpose(u, (0, 2, 1))),
+           None if timeScale is None else _time_scale(timeScale, B, N + 1), int(substeps), int(restart), float(need))
+    X = np.zeros((B, N + 1, 4)) if states else None
+    r = _rollout(B, substeps, int(nObs.max()), lambda out: ctx._check(_load().obca_parking_rollout_batch(ctx._h, B, N, *ins, out, X), "obca_parking_rollout_batch"))
+    return dict(r, **({"states": X} if states else {}))
 
 
 def _context_ms(entry, device):
@@ -781,6 +841,7 @@ def _unpack_quad(T, xp, up, ts, ef, lp, sl, info):
 class QuadBatch(_DeviceBatch):
     """Device-resident batch of quadcopter signed-distance NLPs (obca_quad_batch_* in include/obca_hip.h)."""
     _c = "obca_quad_batch"
+    _nx = 12
 
     def upload(self, x0, xF, Ts, R, ob, xWS, timeWS, dual_ws=True, dist=False):
         B = self.B = self.capacity; N = self.N      # (an upload fills the batch)
@@ -842,6 +903,12 @@ class QuadBatch(_DeviceBatch):
     def validate(self, tol=1e-3):
         """constrSatisfaction on the last solution, on the device (obca_quad_batch_validate): dict(ok (B,) bool, viol (B, 9) in the order of `names` = QUAD_VIOL_NAMES)"""
         return _verdict(self.B, QUAD_VIOL_NAMES, lambda *out: self._call("validate", tol, *out))
+
+    def rollout(self, substeps=8, restart=False, need=0.0):
+        """The last solution applied to the continuous rigid body, on the device (obca_quad_batch_rollout; numpy: obca_amd.validate.rollout_quad + rollout_record): the
+        rotor speeds held over every interval, classical RK4 with `substeps` steps per interval, the gyroscopic products at the current rates.  The NLP's rows are forward
+        Euler: restart=True shows what one interval of it is off by, restart=False where the open loop ends up.  Returns the dict of Batch.rollout, 5 obstacles."""
+        return self._rollout(5, substeps, restart, need)
 
     def clearance(self, substeps=8, need=0.0):
         """Clearance of the last solution between its nodes, on the device (obca_quad_batch_clearance; numpy: obca_amd.validate.quad_clearance): the straight segment of every
@@ -922,6 +989,20 @@ def quadcopter_clearance_batch(x, timeScale, Ts, ob, R, substeps=8, need=0.0, de
     ctx = _ctx(device)
     ins = (_per_instance(Ts, B), R, _boxes(ob, B), _in(np.transpose(x, (0, 2, 1))), _time_scale(1.0 if timeScale is None else timeScale, B, N1), int(substeps), float(need))
     return _clearance(B, substeps, 5, lambda out: ctx._check(_load().obca_quadcopter_clearance_batch(ctx._h, B, N1 - 1, *ins, out), "obca_quadcopter_clearance_batch"))
+
+
+def quadcopter_rollout_batch(x, u, timeScale, Ts, ob, R, substeps=8, restart=False, need=0.0, device=0, states=True):
+    """QuadBatch.rollout for arbitrary trajectories (obca_quadcopter_rollout_batch): x (B,12,N+1), u (B,4,N), timeScale scalar, (B,), (B,N+1) or None (= 1), ob (5,6)
+    shared or (B,5,6).  Returns the dict of QuadBatch.rollout, with `states` (B, N+1, 12) unless states=False."""
+    x = np.asarray(x, float); u = np.asarray(u, float); B, _, N1 = x.shape
+    if x.shape != (B, 12, N1) or u.shape != (B, 4, N1 - 1):
+        raise ObcaError(f"x must be (B,12,N+1) and u (B,4,N); got {x.shape}, {u.shape}")
+    ctx = _ctx(device)
+    ins = (_per_instance(Ts, B), R, _boxes(ob, B), _in(np.transpose(x, (0, 2, 1))), _in(np.transpose(u, (0, 2, 1))), _time_scale(1.0 if timeScale is None else timeScale, B, N1),
+           int(substeps), int(restart), float(need))
+    X = np.zeros((B, N1, 12)) if states else None
+    r = _rollout(B, substeps, 5, lambda out: ctx._check(_load().obca_quadcopter_rollout_batch(ctx._h, B, N1 - 1, *ins, out, X), "obca_quadcopter_rollout_batch"))
+    return dict(r, **({"states": X} if states else {}))
 
 
 def constrSatisfaction(x, u, timeScale, x0, xF, Ts, lam, ob1, ob2, ob3, ob4, ob5, R, device=0):

@@ -7,6 +7,7 @@
 //   obca_dualws_kernel      : one lane per (instance, stage, obstacle) convex sub-problem of DualMultWS (obca_model.h).
 //   obca_validate_*_kernel  : one wavefront per instance, the a-posteriori feasibility classes of a solution or of a caller's trajectory (obca_validate.h).
 //   obca_clearance_*_kernel : one wavefront per instance, the clearance of a solution or of a caller's trajectory between its nodes (obca_clearance.h).
+//   obca_rollout_*_kernel   : one wavefront per instance, a solution or a caller's trajectory applied to the continuous vehicle model: deviations, clearance of the rolled samples (obca_rollout.h).
 //   obca_refine_*_kernel    : one wavefront per destination instance, a solved parking instance on a finer horizon (obca_refine.h): into a second resident batch or host-bound arrays.
 //   obca_quad_subdivide_*_kernel : the same for a solved quadcopter instance (obca_quad_subdivide.h): it rewrites a problem record.
 //   obca_path_ws_*_kernel   : one wavefront per instance, the parking warm start from a planner path (obca_path_ws.h): into host-bound arrays or into a resident batch.
@@ -39,11 +40,13 @@
 #include "obca_clearance.h"
 #include "obca_refine.h"
 #include "obca_quad_subdivide.h"
+#include "obca_rollout.h"
 #include "../../include/obca_hip.h"
 #include "../../include/obca_path_ws.h"
 #include "../../include/obca_clearance.h"
 #include "../../include/obca_refine.h"
 #include "../../include/obca_quad_subdivide.h"
+#include "../../include/obca_rollout.h"
 
 using namespace obca;
 #ifdef OBCA_POISON
@@ -57,6 +60,7 @@ static_assert(OBCA_QUAD_NMAX == QNMAX, "ABI limits must match the kernels");
 static_assert(OBCA_PATH_WS_MAXNODES == PW_MAXNODES, "ABI limits must match the kernels");
 static_assert(OBCA_CLR_OUT == CL_OUT && OBCA_CLR_MAXSUB == CL_SMAX && OBCA_CLR_TOUCH == CL_TOUCH, "ABI limits must match the kernels");
 static_assert(OBCA_REFINE_MAXFACTOR == RF_MAXFACTOR, "ABI limits must match the kernels");
+static_assert(OBCA_ROLL_OUT == RO_OUT && OBCA_ROLL_CLR == RO_CLR && OBCA_ROLL_MAXSUB == CL_SMAX, "ABI limits must match the kernels");
 static_assert(OBCA_VMAX == OB_VMAX && OBCA_NOBMAX == OB_NOBMAX && OBCA_NMAX == OB_NMAX && OBCA_MMAX == OB_MMAX, "ABI limits must match the kernels");
 
 struct DevBufs {
@@ -321,6 +325,24 @@ __global__ __launch_bounds__(QNT) void obca_clearance_quad_kernel(int B, int N, 
     clr::clearance_quad_instance(N, prob + (size_t)inst * s_prob, x + (size_t)inst * s_x, ts + (size_t)inst * s_ts, tstride, S, need, 0, out + (size_t)inst * CL_OUT);
 }
 
+// rollout on the continuous models (obca_rollout.h): one wavefront per instance; the arguments of the clearance kernels, then the two regions of the work buffer: the sample
+// poses (s_pose doubles per instance) and the node states (s_X)
+template <int VM>
+__global__ __launch_bounds__(OB_NT) void obca_rollout_parking_kernel(int B, int N, const double *prob, size_t s_prob, const double *z, size_t s_z, const double *ts, int S, int restart, double need,
+                                                                     double *pose, size_t s_pose, double *X, size_t s_X, double *out) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    roll::rollout_parking_instance<VM>(N, prob + (size_t)inst * s_prob, z + (size_t)inst * s_z, ts ? ts + (size_t)inst * (N + 1) : nullptr, S, restart, need, 0,
+                                       pose + (size_t)inst * s_pose, X + (size_t)inst * s_X, out + (size_t)inst * RO_OUT);
+}
+__global__ __launch_bounds__(QNT) void obca_rollout_quad_kernel(int B, int N, const double *prob, size_t s_prob, const double *x, size_t s_x, const double *u, size_t s_u, const double *ts, size_t s_ts, int tstride,
+                                                                int S, int restart, double need, double *pose, size_t s_pose, double *X, size_t s_X, double *out) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    roll::rollout_quad_instance(N, prob + (size_t)inst * s_prob, x + (size_t)inst * s_x, u + (size_t)inst * s_u, ts + (size_t)inst * s_ts, tstride, S, restart, need, 0,
+                                pose + (size_t)inst * s_pose, X + (size_t)inst * s_X, out + (size_t)inst * RO_OUT);
+}
+
 // warm starts from planner paths (obca_path_ws.h): one wavefront per instance.  paths / dirs: B x rows (x 3) dense on the device -- the rows below the longest count of the
 // call --, `cap` the rows of the caller's arrays (what a count is checked against).  Host-pointer call: outputs per instance, zeros where the status is negative.
 __global__ __launch_bounds__(OB_NT) void obca_path_ws_host_kernel(int B, int N, const double *paths, const int *dirs, const int *counts, int rows, int cap, const double *xF /* 4 x B or NULL */,
@@ -517,6 +539,9 @@ struct BatchCore {
     hipEvent_t e0 = nullptr, e1 = nullptr;                  // around the kernels of the last solve
     ValBufs val;
     ValBufs clr;                                            // the same set for the clearance calls (obca_clearance.h): a clearance call leaves validate's row lengths and events alone
+    ValBufs rol;                                            // ... and for the rollout calls (obca_rollout.h)
+    DevBuf rol_w;                                           // their work buffer: [ sample poses 3 x (N S + 1) | node states nx x (N + 1) ] x B, allocated by the first call, grown on demand
+    int rol_B = 0, rol_N = 0, rol_S = 0;                    // the instances, horizon and sub-steps of the last rollout (0: none yet): where its node states lie in rol_w
     BatchCore(obca_ctx *c, int dev, hipStream_t s, int B_, int N_) : ctx(c), device(dev), stream(s), B(B_), cap(B_), N(N_) {}
 };
 struct obca_quad_batch : BatchCore {
@@ -578,7 +603,8 @@ static int core_phase_cycles(BatchCore *bt, const double *prof, double *out /* B
 #endif
 // everything of the core that a batch's destroy releases, except `stage` (it goes with the family's device buffers); the batch's device is selected
 static void core_release(BatchCore *bt) {
-    for (ValBufs *pv : {&bt->val, &bt->clr}) {
+    bt->rol_w.release();
+    for (ValBufs *pv : {&bt->val, &bt->clr, &bt->rol}) {
         ValBufs &v = *pv;
         v.d_in.release(); v.d_out.release(); v.h_in.release(); v.h_out.release(); v.ev.release();
     }
@@ -1020,6 +1046,47 @@ static int batch_clearance_range(obca_batch *bt, bool host, const double *ts, in
     }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * CL_OUT, o, sizeof(double) * CL_OUT); });
 }
 
+// What the two rollout routes share (obca_rollout.h).  Before the kernel: the work buffer for B instances of horizon N at S sub-steps (grown on demand).  After it: the
+// bookkeeping of the *_states calls and, for a host-pointer call, the node states of the chunk into the caller's X (nx x (N + 1) per instance, instance lo + i of the call).
+static int rollout_reserve(BatchCore *bt, int nx, int S) {
+    use_device(bt->device);
+    if (bt->rol_w.reserve((size_t)bt->B * (roll::rollout_pose_len(bt->N, S) + roll::rollout_state_len(bt->N, nx)), bt->stream) != hipSuccess) { bt->err = "hipMalloc(rollout work buffer) failed"; return -2; }
+    return 0;
+}
+static inline double *rollout_states_at(BatchCore *bt, int S) { return bt->rol_w + (size_t)bt->B * roll::rollout_pose_len(bt->N, S); }
+static int rollout_finish(BatchCore *bt, int rc, int nx, int S, int lo, double *X) {
+    bt->rol_B = bt->rol_N = bt->rol_S = 0;
+    if (rc) return rc;
+    bt->rol_B = bt->B; bt->rol_N = bt->N; bt->rol_S = S;
+    const size_t n = (size_t)bt->B * roll::rollout_state_len(bt->N, nx);
+    if (X) HIPCHK(bt, hipMemcpy(X + (size_t)lo * roll::rollout_state_len(bt->N, nx), rollout_states_at(bt, S), n * sizeof(double), hipMemcpyDeviceToHost));      // (run_validate has synchronised the stream)
+    return 0;
+}
+static int rollout_states(BatchCore *bt, int nx, double *X, const char *entry) {
+    if (!X) { bt->ctx->err = std::string(entry) + ": NULL argument"; return -1; }
+    if (!bt->rol_B || bt->rol_B != bt->B || bt->rol_N != bt->N) { bt->ctx->err = std::string(entry) + ": no rollout has run on this batch since it was last filled"; return -1; }
+    use_device(bt->device);
+    if (hipStreamSynchronize(bt->stream) != hipSuccess || hipMemcpy(X, rollout_states_at(bt, bt->rol_S), (size_t)bt->B * roll::rollout_state_len(bt->N, nx) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+        bt->ctx->err = std::string(entry) + ": D2H failed"; return -2;
+    }
+    return 0;
+}
+// Rollout of the batch's parking instances: the arguments of batch_clearance_range, then the mode and the caller's X (host-pointer calls; nullptr: the states stay on the device)
+static int batch_rollout_range(obca_batch *bt, bool host, const double *ts, int S, int restart, double need, int lo, double *out, double *X) {
+    const int B = bt->B, N = bt->N, N1 = N + 1;
+    if (int rc = rollout_reserve(bt, 4, S)) return rc;
+    const int rc = run_validate(bt, bt->rol, ts ? (size_t)N1 : 0, ts != nullptr, RO_OUT, [&](int i, double *a) {
+        memcpy(a, ts + ((size_t)lo + i) * N1, sizeof(double) * N1);
+    }, [&] {
+        const double *z = host ? bt->d.z0 : bt->d.z, *dts = ts ? (const double *)bt->rol.d_in : nullptr;
+#define ROL_LAUNCH(VM) hipLaunchKernelGGL(obca_rollout_parking_kernel<VM>, dim3(B), dim3(OB_NT), 0, bt->stream, B, N, (const double *)bt->d.prob, bt->d.s_prob, z, bt->d.s_z, dts, S, restart, need, \
+                                          (double *)bt->rol_w, roll::rollout_pose_len(N, S), rollout_states_at(bt, S), roll::rollout_state_len(N, 4), (double *)bt->rol.d_out)
+        if (bt->vmax <= 2) ROL_LAUNCH(2); else if (bt->vmax <= OB_VMID) ROL_LAUNCH(OB_VMID); else ROL_LAUNCH(OB_VMAX);      // (the row class of launch_dualws)
+#undef ROL_LAUNCH
+    }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * RO_OUT, o, sizeof(double) * RO_OUT); });
+    return rollout_finish(bt, rc, 4, S, lo, X);
+}
+
 // ---- chunked execution of a host-pointer call over the slots of the context (work queue)
 template <typename F>
 static int run_chunks(obca_ctx *ctx, int B, int chunk, F &&fn /* int(Slot &, int lo, int n, std::string &err) */) {
@@ -1217,6 +1284,29 @@ int obca_parking_clearance_batch(obca_ctx *ctx, int B, int N, const double *Ts, 
     ParkIn in = {Ts, L, ego, XYb, 0, nullptr, nullptr, nOb, vOb, A, b, zero.data(), zero.data(), zero.data(), x, u, nullptr, nullptr, {}, {}};
     if (int rc = park_prefix(ctx->err, B, nOb, vOb, in)) return rc;
     return parking_chunks(ctx, 0, B, N, in, [&](obca_batch *bt, int lo) { return batch_clearance_range(bt, true, timeScale, substeps, need, lo, out); });
+}
+
+int obca_batch_rollout(obca_batch *bt, int substeps, int restart, double need, double *out) {
+    if (!bt) return -1;
+    if (!out) { bt->ctx->err = "obca_batch_rollout: NULL argument"; return -1; }
+    if (const char *bad = roll::rollout_check_args(substeps, restart, need)) { bt->ctx->err = std::string("obca_batch_rollout: ") + bad; return -1; }
+    if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_batch_rollout: nothing has been solved since the last upload or shift"; return -1; }
+    if (bt->N < 1) { bt->ctx->err = "obca_batch_rollout: needs a horizon N>=1"; return -1; }
+    return fin(bt, batch_rollout_range(bt, false, nullptr, substeps, restart, need, 0, out, nullptr));
+}
+int obca_batch_rollout_ms(obca_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->rol.ev, ms, "obca_batch_rollout_ms: no rollout has run on this batch") : -1; }
+int obca_batch_rollout_states(obca_batch *bt, double *X) { return bt ? rollout_states(bt, 4, X, "obca_batch_rollout_states") : -1; }
+int obca_parking_rollout_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const int *nOb, const int *vOb, const double *A, const double *b,
+                               const double *x, const double *u, const double *timeScale, int substeps, int restart, double need, double *out, double *X) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 1 || N > OBCA_NMAX) { ctx->err = "obca_parking_rollout_batch: need B>=1, 1<=N<=OBCA_NMAX"; return -1; }
+    if (!Ts || !ego || !nOb || !vOb || !A || !b || !x || !u || !out) { ctx->err = "obca_parking_rollout_batch: NULL argument"; return -1; }
+    if (const char *bad = roll::rollout_check_args(substeps, restart, need)) { ctx->err = std::string("obca_parking_rollout_batch: ") + bad; return -1; }
+    const std::vector<double> zero((size_t)B * (N + 1), 0.0);      // the tracking reference of a solve: the call does not read it (nor the bounds, the start and the goal)
+    const double XYb[4] = {0, 0, 0, 0};
+    ParkIn in = {Ts, L, ego, XYb, 0, nullptr, nullptr, nOb, vOb, A, b, zero.data(), zero.data(), zero.data(), x, u, nullptr, nullptr, {}, {}};
+    if (int rc = park_prefix(ctx->err, B, nOb, vOb, in)) return rc;
+    return parking_chunks(ctx, 0, B, N, in, [&](obca_batch *bt, int lo) { return batch_rollout_range(bt, true, timeScale, substeps, restart, need, lo, out, X); });
 }
 
 int obca_parking_signed_dist_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const double XYb[4],
@@ -1585,6 +1675,24 @@ static int quad_clearance_range(obca_quad_batch *bt, const double *ts, int S, do
         else hipLaunchKernelGGL(obca_clearance_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)d.z + l.x, d.s_z, (const double *)d.z + l.t, d.s_z, 0, S, need, bt->clr.d_out);
     }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * CL_OUT, o, sizeof(double) * CL_OUT); });
 }
+// the rollout of the batch's quadcopter instances (obca_rollout.h): resident (ts == nullptr: the last solution in d.z, its one t) or a caller's trajectory -- x as
+// quad_upload_range has put it behind the problem header, timeScale and u of the call travelling up as [ timeScale (N + 1) | u 4 x N ] per instance
+static int quad_rollout_range(obca_quad_batch *bt, const double *u, const double *ts, int S, int restart, double need, int lo, double *out, double *X) {
+    const int B = bt->B, N = bt->N, N1 = N + 1; const QDevBufs &d = bt->d;
+    quad::QLay l; quad::q_make_layout(N, l);
+    if (int rc = rollout_reserve(bt, QX, S)) return rc;
+    const size_t W = (size_t)N1 + (size_t)QU * N, sp = roll::rollout_pose_len(N, S), sx = roll::rollout_state_len(N, QX);
+    const int rc = run_validate(bt, bt->rol, ts ? W : 0, ts != nullptr, RO_OUT, [&](int i, double *a) {
+        memcpy(a, ts + ((size_t)lo + i) * N1, sizeof(double) * N1); memcpy(a + N1, u + ((size_t)lo + i) * QU * N, sizeof(double) * QU * N);
+    }, [&] {
+        const double *in = bt->rol.d_in;
+        if (ts) hipLaunchKernelGGL(obca_rollout_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)d.prob + QPH_SIZE, d.s_prob, in + N1, W, in, W, 1,
+                                   S, restart, need, (double *)bt->rol_w, sp, rollout_states_at(bt, S), sx, (double *)bt->rol.d_out);
+        else hipLaunchKernelGGL(obca_rollout_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)d.z + l.x, d.s_z, (const double *)d.z + l.u, d.s_z,
+                                (const double *)d.z + l.t, d.s_z, 0, S, restart, need, (double *)bt->rol_w, sp, rollout_states_at(bt, S), sx, (double *)bt->rol.d_out);
+    }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * RO_OUT, o, sizeof(double) * RO_OUT); });
+    return rollout_finish(bt, rc, QX, S, lo, X);
+}
 // instances (one wavefront each) resident per CU, as OBCA_RESIDENT_PER_CU for the parking kernel: what pick_chunk sizes a quadcopter chunk by
 static const int QUAD_RESIDENT_PER_CU = (QNT == 64 ? 4 : 2) * OBCA_QUAD_WAVES_PER_EU;
 // parking_chunks for the quadcopter; the slot's cached batch only has to hold the chunk at hand
@@ -1675,6 +1783,25 @@ int obca_quadcopter_clearance_batch(obca_ctx *ctx, int B, int N, const double *T
     const std::vector<double> zero((size_t)B * QX, 0.0), one((size_t)B, 1.0);      // start, goal and timeWS of a solve: the check reads none of them
     const QuadIn in = {Ts, R, zero.data(), zero.data(), ob, x, one.data(), 0, 0};
     return quad_chunks(ctx, B, N, in, [&](obca_quad_batch *bt, int lo) { return quad_clearance_range(bt, timeScale, substeps, need, lo, out); });
+}
+int obca_quad_batch_rollout(obca_quad_batch *bt, int substeps, int restart, double need, double *out) {
+    if (!bt) return -1;
+    if (!out) { bt->ctx->err = "obca_quad_batch_rollout: NULL argument"; return -1; }
+    if (const char *bad = roll::rollout_check_args(substeps, restart, need)) { bt->ctx->err = std::string("obca_quad_batch_rollout: ") + bad; return -1; }
+    if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_quad_batch_rollout: nothing has been solved since the last upload or shift"; return -1; }
+    return fin(bt, quad_rollout_range(bt, nullptr, nullptr, substeps, restart, need, 0, out, nullptr));
+}
+int obca_quad_batch_rollout_ms(obca_quad_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->rol.ev, ms, "obca_quad_batch_rollout_ms: no rollout has run on this batch") : -1; }
+int obca_quad_batch_rollout_states(obca_quad_batch *bt, double *X) { return bt ? rollout_states(bt, QX, X, "obca_quad_batch_rollout_states") : -1; }
+int obca_quadcopter_rollout_batch(obca_ctx *ctx, int B, int N, const double *Ts, double R, const double *ob, const double *x, const double *u, const double *timeScale,
+                                  int substeps, int restart, double need, double *out, double *X) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 2 || N > OBCA_QUAD_NMAX) { ctx->err = "obca_quadcopter_rollout_batch: need B>=1, 2<=N<=OBCA_QUAD_NMAX"; return -1; }
+    if (!Ts || !ob || !x || !u || !timeScale || !out) { ctx->err = "obca_quadcopter_rollout_batch: NULL argument"; return -1; }
+    if (const char *bad = roll::rollout_check_args(substeps, restart, need)) { ctx->err = std::string("obca_quadcopter_rollout_batch: ") + bad; return -1; }
+    const std::vector<double> zero((size_t)B * QX, 0.0), one((size_t)B, 1.0);      // start, goal and timeWS of a solve: the call reads none of them
+    const QuadIn in = {Ts, R, zero.data(), zero.data(), ob, x, one.data(), 0, 0};
+    return quad_chunks(ctx, B, N, in, [&](obca_quad_batch *bt, int lo) { return quad_rollout_range(bt, u, timeScale, substeps, restart, need, lo, out, X); });
 }
 int obca_quad_batch_download(obca_quad_batch *bt, double *xp, double *up, double *ts, int *exitflag, double *lp, double *slp, double *info) {
     if (!bt) return -1;

@@ -58,6 +58,24 @@ OBCA_FN void dyn_g_value(const QConsts &c, const double *x, const double *u, dou
     g[11] = (Q_KM * (u[0] * u[0] - u[1] * u[1] + u[2] * u[2] - u[3] * u[3]) - (Q_I2 - Q_I1) * c.gyro[0] * c.gyro[1]) * (1.0 / Q_I3);
 }
 
+// The right-hand side of the CONTINUOUS rigid body that the rows above discretise, xdot = g(x, u), for the rollout of solved trajectories (obca_rollout.h): the terms of
+// :138-155 with the gyroscopic products at the CURRENT rates x[9..11] -- the rows freeze them at stage 1 (c.gyro), a property of the NLP, not of the vehicle.
+// A rolled state is arbitrary: the library's sin and cos and a plain division by cos x[3], as obca_validate.h writes the same terms.  No solve kernel calls this.
+OBCA_FN void dyn_g_continuous(const double *x, const double *u, double g[QX]) {
+    const double s4 = sin(x[3]), c4 = cos(x[3]), s5 = sin(x[4]), c5 = cos(x[4]), s6 = sin(x[5]), c6 = cos(x[5]);
+    const double usq = u[0] * u[0] + u[1] * u[1] + u[2] * u[2] + u[3] * u[3];
+    g[0] = x[6]; g[1] = x[7]; g[2] = x[8];
+    g[3] = c5 * x[9] + s5 * x[11];
+    g[4] = s5 * s4 / c4 * x[9] + x[10] - c5 * s4 / c4 * x[11];
+    g[5] = -s5 / c4 * x[9] + c5 / c4 * x[11];
+    g[6] = Q_KF / Q_MASS * usq * (s4 * c5 * s6 + s5 * c6);
+    g[7] = Q_KF / Q_MASS * usq * (-s4 * c5 * c6 + s5 * s6);
+    g[8] = (Q_KF * usq * c4 * c5 - Q_MASS * Q_GRAV) / Q_MASS;
+    g[9] = (Q_ARM * Q_KF * (u[1] * u[1] - u[3] * u[3]) - (Q_I3 - Q_I2) * x[10] * x[11]) / Q_I1;
+    g[10] = (Q_ARM * Q_KF * (u[2] * u[2] - u[0] * u[0]) - (Q_I1 - Q_I3) * x[9] * x[11]) / Q_I2;
+    g[11] = (Q_KM * (u[0] * u[0] - u[1] * u[1] + u[2] * u[2] - u[3] * u[3]) - (Q_I2 - Q_I1) * x[9] * x[10]) / Q_I3;
+}
+
 // value, Jacobian rows 3..11 w.r.t. the QV local variables (dg[i-3][a]) and HG = sum_i w_i Hess g_i (upper triangle, packed 55)
 OBCA_FN int q_pidx(int a, int b) { int i = a < b ? a : b, j = a < b ? b : a; return i * QV - i * (i - 1) / 2 + (j - i); }
 OBCA_FN void dyn_g_derivs(const QConsts &c, const double *x, const double *u, const double *w, double g[QX], double dg[9][QV], double HG[55]) {

@@ -16,8 +16,11 @@ parking_samples, quad_clearance, clearance_record : the numpy statement of the b
     the sample poses of a parking trajectory, the clearance record of a quadcopter trajectory, and the record of any (samples, obstacles) table of clearances.
 refine_parking : the numpy statement of the refinement of a solved parking instance onto a finer horizon (obca_amd/csrc/obca_refine.h, Batch.refine).
 refine_quad : the same for a solved quadcopter instance (obca_amd/csrc/obca_quad_subdivide.h, QuadBatch.refine).
+rollout_parking, rollout_quad, rollout_record : the numpy statement of the rollout of a solution on the continuous vehicle models (obca_amd/csrc/obca_rollout.h,
+    Batch.rollout, QuadBatch.rollout): held inputs, classical RK4, the rolled node states, the sample poses and the record of deviations and clearances.
 Shapes follow the reference: x (4,N+1), u (2,N), l (M,N+1), n (4nOb,N+1), timeScale (N+1,) .
 """
+import math
 import numpy as np
 
 DMIN = 0.05
@@ -284,3 +287,106 @@ def quad_clearance(x, timeScale, Ts, ob, R, substeps, need=0.0):
                 e = np.maximum(np.maximum(-ob[j, 3:] - pt, pt - ob[j, :3]), 0.0)
                 c[q, j] = np.sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]) - R
     return clearance_record(c, S, need, finite)
+
+
+# ---------------------------------------------------------------- rollout on the continuous models (obca_amd/csrc/obca_rollout.h)
+ROLL_OUT = 40         # doubles of a record: bad, dev_pos, dev_node, dev_att, dev_vel, dev_rate, the same four at node N, restart, S, 4 x 0, then the CLR_OUT clearance record
+_QC = dict(m=0.5, g=9.81, kF=0.0611, kM=0.0015, arm=0.225, I1=3.9e-3, I2=4.4e-3, I3=4.9e-3)      # QuadcopterSignedDist.jl:51-62 (obca_quad_model.h)
+
+
+def _park_rhs(x, u, L):
+    """the kinematic bicycle; u[0] is tan(delta)"""
+    return [x[3] * math.cos(x[2]), x[3] * math.sin(x[2]), x[3] * u[0] / L, u[1]]
+
+
+def _quad_rhs(x, u, _=None):
+    """the rigid body QuadcopterSignedDist.jl:138-155 discretises, gyroscopic products at the CURRENT rates (quad::dyn_g_continuous, term by term)"""
+    q = _QC; s4, c4, s5, c5, s6, c6 = math.sin(x[3]), math.cos(x[3]), math.sin(x[4]), math.cos(x[4]), math.sin(x[5]), math.cos(x[5])
+    usq = u[0] * u[0] + u[1] * u[1] + u[2] * u[2] + u[3] * u[3]
+    return [x[6], x[7], x[8],
+            c5 * x[9] + s5 * x[11], s5 * s4 / c4 * x[9] + x[10] - c5 * s4 / c4 * x[11], -s5 / c4 * x[9] + c5 / c4 * x[11],
+            q["kF"] / q["m"] * usq * (s4 * c5 * s6 + s5 * c6), q["kF"] / q["m"] * usq * (-s4 * c5 * c6 + s5 * s6), (q["kF"] * usq * c4 * c5 - q["m"] * q["g"]) / q["m"],
+            (q["arm"] * q["kF"] * (u[1] * u[1] - u[3] * u[3]) - (q["I3"] - q["I2"]) * x[10] * x[11]) / q["I1"],
+            (q["arm"] * q["kF"] * (u[2] * u[2] - u[0] * u[0]) - (q["I1"] - q["I3"]) * x[9] * x[11]) / q["I2"],
+            (q["kM"] * (u[0] * u[0] - u[1] * u[1] + u[2] * u[2] - u[3] * u[3]) - (q["I2"] - q["I1"]) * x[9] * x[10]) / q["I3"]]
+
+
+def _rk4(f, X, u, h, L):
+    """one classical RK4 step, in the order of roll::rk4_step"""
+    n = len(X)
+    k = f(X, u, L); acc = list(k); xt = [X[i] + h / 2 * k[i] for i in range(n)]
+    k = f(xt, u, L); acc = [acc[i] + 2 * k[i] for i in range(n)]; xt = [X[i] + h / 2 * k[i] for i in range(n)]
+    k = f(xt, u, L); acc = [acc[i] + 2 * k[i] for i in range(n)]; xt = [X[i] + h * k[i] for i in range(n)]
+    k = f(xt, u, L)
+    return [X[i] + h / 6 * (acc[i] + k[i]) for i in range(n)]
+
+
+def _rollout(f, prep, x, u, timeScale, Ts, L, substeps, restart, pole=None):
+    x = np.asarray(x, float); u = np.asarray(u, float); nx, N1 = x.shape; N = N1 - 1; S = int(substeps); ts = _stage_scale(timeScale, N)
+    X = np.zeros((nx, N + 1)); P = np.zeros((N * S + 1, 3)); X[:, 0] = x[:, 0]
+    cur = [float(v) for v in x[:, 0]]; bad = False
+    for k in range(N):
+        if restart:
+            cur = [float(v) for v in x[:, k]]
+        U = prep([float(v) for v in u[:, k]]); h = float(ts[k]) * float(Ts) / S
+        for s in range(S):
+            P[k * S + s] = cur[:3]
+            try:
+                new = _rk4(f, cur, U, h, L)
+                if pole is not None and math.cos(cur[pole]) * math.cos(new[pole]) <= 0.0:      # a step across the pole of the attitude kinematics: the continuous state has diverged
+                    bad = True
+            except (OverflowError, ValueError, ZeroDivisionError):      # (Python's math raises where C returns inf / NaN)
+                new = [math.nan] * nx
+            cur = new
+        X[:, k + 1] = cur
+    P[N * S] = x[:3, N] if restart else cur[:3]
+    if bad or not np.isfinite(X).all():
+        X[:] = np.nan
+    return X, P
+
+
+def rollout_parking(x, u, timeScale, Ts, L, substeps=8, restart=False):
+    """A parking trajectory x (4,N+1), u (2,N) on the continuous kinematic bicycle x' = v cos psi, y' = v sin psi, psi' = v tan(delta) / L, v' = a: u_k held over interval k
+    of length timeScale[k] Ts, classical RK4 with `substeps` equal steps per interval.  restart False: the open loop from x[:, 0] (chain); True: every interval starts at the
+    solution's own node (the defect of one interval).  Returns (X (4,N+1) the rolled node states, samples (N S + 1, 3) the poses (x, y, psi) of the samples q = k S + s of
+    parking_samples: the state after s steps of interval k; s = 0 and the last one are X_k (chain) or the nodes (restart))."""
+    return _rollout(_park_rhs, lambda U: [math.tan(U[0]), U[1]], x, u, timeScale, Ts, float(L), substeps, restart)
+
+
+def rollout_quad(x, u, timeScale, Ts, substeps=8, restart=False):
+    """The same for a quadcopter trajectory x (12,N+1), u (4,N) on the rigid body that QuadcopterSignedDist.jl:138-155 steps with forward Euler (gyroscopic products at the
+    current rates).  Returns (X (12,N+1), samples (N S + 1, 3) positions).  A step across cos x[3] = 0 (a pitch through pi/2: the continuous state diverges there), like
+    a number that is not finite, makes all of X NaN."""
+    return _rollout(_quad_rhs, lambda U: U, x, u, timeScale, Ts, None, substeps, restart, pole=3)
+
+
+def quad_point_clearance(points, ob, R):
+    """(n, 5) clearances of points (n, 3) to the boxes ob (5,6) as [hi; -lo]: Euclidean distance (0 inside) - R, as quad_clearance computes them"""
+    ob = np.asarray(ob, float).reshape(5, 6); c = np.zeros((len(points), 5))
+    with np.errstate(invalid="ignore", over="ignore"):
+        for q, pt in enumerate(np.asarray(points, float)):
+            for j in range(5):
+                e = np.maximum(np.maximum(-ob[j, 3:] - pt, pt - ob[j, :3]), 0.0)
+                c[q, j] = np.sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]) - R
+    return c
+
+
+def rollout_record(x, X, c, substeps, restart, need, finite=True):
+    """the ROLL_OUT doubles of a rollout: x the solution (nx,N+1), X the rolled node states, c (N S + 1, nOb) the clearances of the samples.  [1] the largest position
+    deviation |P(X_k) - P(x_k)|_2 over k = 1..N, [2] its node (ties: the smallest), [3] attitude (parking |d psi|; quadcopter max-abs over states 4-6), [4] velocity (parking
+    |d v|; quadcopter Euclidean over states 7-9), [5] body rates (quadcopter max-abs over states 10-12; parking 0), [6..9] the same at node N, [10] restart, [11] S,
+    [16..39] clearance_record(c).  Not finite (`finite` False, or a rolled state or a clearance is not): bad = 1, the real-valued fields NaN, the node -1."""
+    x = np.asarray(x, float); X = np.asarray(X, float); nx = x.shape[0]; S = int(substeps)
+    r = np.zeros(ROLL_OUT); r[10] = int(bool(restart)); r[11] = S
+    finite = bool(finite and np.isfinite(X).all() and np.isfinite(np.asarray(c, float)).all())
+    r[16:] = clearance_record(c, S, need, finite)
+    if not finite:
+        r[0] = 1; r[1:10] = np.nan; r[2] = -1
+        return r
+    e = X[:, 1:] - x[:, 1:]
+    if nx == 4:
+        d = np.array([np.sqrt(e[0] * e[0] + e[1] * e[1]), np.abs(e[2]), np.abs(e[3]), np.zeros(e.shape[1])])
+    else:
+        d = np.array([np.sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]), np.abs(e[3:6]).max(axis=0), np.sqrt(e[6] * e[6] + e[7] * e[7] + e[8] * e[8]), np.abs(e[9:12]).max(axis=0)])
+    r[1] = d[0].max(); r[2] = 1 + int(np.argmax(d[0])); r[3:6] = d[1:].max(axis=1); r[6:10] = d[:, -1]
+    return r
