@@ -21,7 +21,8 @@ import time
 import numpy as np
 from . import buildflags, cabi, planner
 from .cabi import Opts      # `typedef struct obca_opts` of include/obca_hip.h, read from the header
-from .validate import VIOL_NAMES, QUAD_VIOL_NAMES, DMIN, CLR_OUT, ROLL_OUT
+from .validate import (VIOL_NAMES, QUAD_VIOL_NAMES, DMIN, CLR_OUT, ROLL_OUT, TRK_OUT, TRACK_Q_PARKING, TRACK_R_PARKING, TRACK_QF_PARKING, TRACK_Q_QUAD, TRACK_R_QUAD,
+                       TRACK_QF_QUAD)
 
 _LIBPATH = os.environ.get("OBCA_HIP_LIBRARY") or buildflags.PIECES["hip"].out   # override: diagnostic builds
 _lib = None
@@ -62,6 +63,7 @@ def _load():
     cabi.bind(_lib, "obca_plan_resident_check.h")         # ... and the diagnostic that hands out what its packing kernel wrote
     cabi.bind(_lib, "obca_quad_plan_resident.h")          # the quadcopter's grid planner from the records of an uploaded batch
     cabi.bind(_lib, "obca_rollout.h")                     # solved batches applied to the continuous vehicle models
+    cabi.bind(_lib, "obca_track.h")                       # ... and tracked on them by a time-varying LQR
     return _lib
 
 
@@ -104,6 +106,10 @@ QUAD_PLAN_SKIPPED = -4      # OBCA_QUAD_PLAN_SKIPPED
 # quadcopter_rollout_batch)
 ROLLOUT_EXPORTS = ["obca_batch_rollout", "obca_batch_rollout_ms", "obca_batch_rollout_states", "obca_parking_rollout_batch", "obca_quad_batch_rollout",
                    "obca_quad_batch_rollout_ms", "obca_quad_batch_rollout_states", "obca_quadcopter_rollout_batch"]
+# include/obca_track.h: TVLQR gains about solutions and trajectories and the closed loop on the continuous vehicle models (Batch.track, QuadBatch.track, track_states,
+# track_gains, track_ms, parking_track_batch, quadcopter_track_batch)
+TRACK_EXPORTS = ["obca_batch_track", "obca_batch_track_ms", "obca_batch_track_states", "obca_batch_track_gains", "obca_parking_track_batch", "obca_quad_batch_track",
+                 "obca_quad_batch_track_ms", "obca_quad_batch_track_states", "obca_quad_batch_track_gains", "obca_quadcopter_track_batch"]
 QUAD_PLAN_STATUS = {0: "no path", -1: "more way-points than cap", -2: "the start or goal point is blocked, or a coordinate of the record is not finite",
                     -3: "the relaxation hit its sweep bound", -4: "not selected"}
 QUAD_REFINE_STATUS = {0: "refined from the solution", 1: "interpolated from the uploaded warm start (the last solve failed, or its iterate is not finite)",
@@ -231,9 +237,39 @@ def _rollout(B, substeps, nOb, call):
     or among the rolled states, the values of that instance are NaN; clearance: the dict of _clearance for the rolled samples"""
     rec = np.zeros((B, ROLL_OUT))
     call(rec)
+    return _rollout_dict(rec, substeps, nOb)
+
+
+def _rollout_dict(rec, substeps, nOb):
+    """the dict of _rollout from records (B, ROLL_OUT)"""
     return dict(dev_pos=rec[:, 1], dev_node=rec[:, 2].astype(np.int64), dev_att=rec[:, 3], dev_vel=rec[:, 4], dev_rate=rec[:, 5], end_pos=rec[:, 6], end_att=rec[:, 7],
                 end_vel=rec[:, 8], end_rate=rec[:, 9], restart=rec[:, 10] != 0, substeps=rec[:, 11].astype(np.int64), finite=rec[:, 0] == 0,
                 clearance=_clearance_dict(rec[:, 16:], substeps, nOb))
+
+
+def _track(B, substeps, nOb, call):
+    """the records of a track entry point, `call(out)` with out (B, TRK_OUT), and the dict they are returned in: the dict of _rollout for the tracked chain (deviations of
+    the tracked node states from the trajectory's own, `clearance` of the driven samples; finite False: a non-finite number in the trajectory, in dx0 or among the tracked
+    states, or a pivot of the Riccati recursion that was not finite and positive -- the values of that instance are NaN), and saturated (B,) the number of intervals in
+    which an input was clipped, du_max the largest |U_k - u_k| over inputs and intervals, du_node its interval, dx0_pos |dx0| of the position part, feedback, clamp as the
+    call had them"""
+    rec = np.zeros((B, TRK_OUT))
+    call(rec)
+    return dict(_rollout_dict(rec[:, :ROLL_OUT], substeps, nOb), saturated=rec[:, 42].astype(np.int64), du_max=rec[:, 43], du_node=rec[:, 44].astype(np.int64), dx0_pos=rec[:, 45],
+                feedback=rec[:, 40] != 0, clamp=rec[:, 41] != 0)
+
+
+def _track_weights(nx, nu, Q, R, Qf, defaults):
+    """diagonal weights as the ABI takes them: None -> the named defaults (Qf: 10 Q); a scalar is repeated"""
+    q = _in(np.broadcast_to(np.asarray(defaults[0] if Q is None else Q, float), (nx,)))
+    r = _in(np.broadcast_to(np.asarray(defaults[1] if R is None else R, float), (nu,)))
+    qf = _in(np.broadcast_to(np.asarray((defaults[2] if Q is None else 10.0 * q) if Qf is None else Qf, float), (nx,)))
+    return q, r, qf
+
+
+def _track_dx0(dx0, B, nx):
+    """None, (nx,) for every instance or (B, nx)"""
+    return None if dx0 is None else _in(np.broadcast_to(np.asarray(dx0, float), (B, nx)))
 
 
 class _Handle:
@@ -431,6 +467,27 @@ class _DeviceBatch(_Handle):
         """HIP-event duration of the last rollout kernel"""
         return self._floats("rollout_ms")
 
+    def _track(self, nOb, defaults, substeps, dx0, Q, R, Qf, feedback, clamp, need):
+        q, r, qf = _track_weights(self._nx, self._nu, Q, R, Qf, defaults)
+        return _track(self.B, substeps, nOb, lambda out: self._call("track", int(substeps), int(feedback), int(clamp), q, r, qf, _track_dx0(dx0, self.B, self._nx), float(need), out))
+
+    def track_states(self):
+        """The node states of the last track(), fetched from the device: (B, N+1, nx); NaN for an instance that was not finite.  track_states()[:, shift] is the state the
+        vehicle reaches after `shift` intervals under the feedback: the x0_new of shift_warm_start(shift, x0_new=...).  rollout_states() of an earlier rollout stays valid."""
+        X = np.zeros((self.B, self.N + 1, self._nx))
+        self._call("track_states", X)
+        return X
+
+    def track_gains(self):
+        """The gains of the last track(), fetched from the device: (B, N, nu, nx), u = u_k + K[k] (X_k - x_k); NaN for an instance that was not finite."""
+        K = np.zeros((self.B, self.N, self._nu, self._nx))
+        self._call("track_gains", K)
+        return K
+
+    def track_ms(self):
+        """HIP-event duration of the last track kernel"""
+        return self._floats("track_ms")
+
     def _refine_into(self, entry, limit, extra, select, factor, into):
         """What Batch.refine and QuadBatch.refine share: the selection (None: all) checked against the batch, the factor against `limit`, the destination (`into`, or a new
         batch of this kind, closed again if the call fails) and the call of `entry` with its one own argument `extra`.  Returns (destination, selection, status)."""
@@ -459,6 +516,7 @@ class Batch(_DeviceBatch):
     """Device-resident batch: upload once, solve (repeatedly), download."""
     _c = "obca_batch"
     _nx = 4
+    _nu = 2
 
     def upload(self, x0, xF, Ts, L, ego, XYbounds, vOb, A, b, rx, ry, ryaw, fixTime, xWS, uWS, lWS=None, nWS=None, dist=False):
         """lWS/nWS, when given, are packed per instance as (N+1, M_i) / (N+1, 4 nOb_i) row-major blocks (= the reference's
@@ -558,6 +616,15 @@ class Batch(_DeviceBatch):
         rolled samples (need: its `need`).  The rolled states stay on the device: rollout_states()."""
         return self._rollout(int(self.nObs.max()), substeps, restart, need)
 
+    def track(self, substeps=8, dx0=None, Q=None, R=None, Qf=None, feedback=True, clamp=True, need=DMIN):
+        """The last solution TRACKED on the continuous kinematic bicycle by a time-varying LQR about it, ON THE DEVICE (obca_batch_track; the numpy statement is
+        obca_amd.validate.track_parking + track_record): the gains come from the derivative of the map the plant applies over an interval (`substeps` RK4 steps, the input
+        held) and a backward Riccati recursion with diagonal weights Q (4), R (2), Qf (4) -- defaults TRACK_Q_PARKING, TRACK_R_PARKING, 10 Q; untuned --, the loop starts at
+        x0 + dx0 (dx0: (4,) or (B,4)), applies u_k + K_k (X_k - x_k) held over interval k (feedback=False: u_k) and clips it to |delta| <= 0.6, |a| <= 0.4 (clamp).  Returns the
+        dict of _track: the deviations and the clearance of the driven path as rollout() reports them, and saturated, du_max, du_node, dx0_pos, feedback, clamp.  States and
+        gains stay on the device: track_states(), track_gains()."""
+        return self._track(int(self.nObs.max()), (TRACK_Q_PARKING, TRACK_R_PARKING, TRACK_QF_PARKING), substeps, dx0, Q, R, Qf, feedback, clamp, need)
+
     def clearance(self, substeps=8, need=DMIN):
         """Clearance of the last solution BETWEEN its nodes, ON THE DEVICE (obca_batch_clearance; the numpy statement is obca_amd.validate.parking_samples + a DualMultWS
         distance per pose): every interval is sampled `substeps` times with the discretisation's own partial step and the car's distance to every obstacle computed anew,
@@ -603,6 +670,23 @@ def parking_rollout_batch(N, Ts, L, ego, vOb, A, b, x, u, timeScale=None, subste
     X = np.zeros((B, N + 1, 4)) if states else None
     r = _rollout(B, substeps, int(nObs.max()), lambda out: ctx._check(_load().obca_parking_rollout_batch(ctx._h, B, N, *ins, out, X), "obca_parking_rollout_batch"))
     return dict(r, **({"states": X} if states else {}))
+
+
+def parking_track_batch(N, Ts, L, ego, vOb, A, b, x, u, timeScale=None, substeps=8, dx0=None, Q=None, R=None, Qf=None, feedback=True, clamp=True, need=DMIN, device=0,
+                        states=True, gains=True):
+    """Batch.track for arbitrary trajectories (obca_parking_track_batch): the arguments of parking_rollout_batch, then those of Batch.track.  Returns the dict of
+    Batch.track, with `states` (B, N+1, 4) and `gains` (B, N, 2, 4) unless states=False / gains=False."""
+    x = np.asarray(x, float); u = np.asarray(u, float); N = int(N); B = x.shape[0]
+    if x.shape != (B, 4, N + 1) or u.shape != (B, 2, N):
+        raise ObcaError(f"x must be (B,4,N+1) and u (B,2,N); got {x.shape}, {u.shape}")
+    ctx = _ctx(device)
+    nObs, vflat, Aflat, bflat = _norm_obstacles(B, vOb, A, b)
+    q, r, qf = _track_weights(4, 2, Q, R, Qf, (TRACK_Q_PARKING, TRACK_R_PARKING, TRACK_QF_PARKING))
+    ins = (_per_instance(Ts, B), L, _in(ego), _in(nObs, np.int32), _in(vflat, np.int32), _in(Aflat), _in(bflat), _in(np.transpose(x, (0, 2, 1))), _in(np.transpose(u, (0, 2, 1))),
+           None if timeScale is None else _time_scale(timeScale, B, N + 1), int(substeps), int(feedback), int(clamp), q, r, qf, _track_dx0(dx0, B, 4), float(need))
+    X = np.zeros((B, N + 1, 4)) if states else None; K = np.zeros((B, N, 2, 4)) if gains else None
+    t = _track(B, substeps, int(nObs.max()), lambda out: ctx._check(_load().obca_parking_track_batch(ctx._h, B, N, *ins, out, X, K), "obca_parking_track_batch"))
+    return dict(t, **({"states": X} if states else {}), **({"gains": K} if gains else {}))
 
 
 def _context_ms(entry, device):
@@ -842,6 +926,7 @@ class QuadBatch(_DeviceBatch):
     """Device-resident batch of quadcopter signed-distance NLPs (obca_quad_batch_* in include/obca_hip.h)."""
     _c = "obca_quad_batch"
     _nx = 12
+    _nu = 4
 
     def upload(self, x0, xF, Ts, R, ob, xWS, timeWS, dual_ws=True, dist=False):
         B = self.B = self.capacity; N = self.N      # (an upload fills the batch)
@@ -909,6 +994,13 @@ class QuadBatch(_DeviceBatch):
         rotor speeds held over every interval, classical RK4 with `substeps` steps per interval, the gyroscopic products at the current rates.  The NLP's rows are forward
         Euler: restart=True shows what one interval of it is off by, restart=False where the open loop ends up.  Returns the dict of Batch.rollout, 5 obstacles."""
         return self._rollout(5, substeps, restart, need)
+
+    def track(self, substeps=8, dx0=None, Q=None, R=None, Qf=None, feedback=True, clamp=True, need=0.0):
+        """The last solution tracked on the continuous rigid body by a time-varying LQR about it, on the device (obca_quad_batch_track; numpy:
+        obca_amd.validate.track_quad + track_record): Batch.track with Q (12), R (4), Qf (12) -- defaults TRACK_Q_QUAD, TRACK_R_QUAD, 10 Q; untuned --, dx0 (12,) or (B,12),
+        rotor speeds clipped to 1.2 .. 7.8.  The NLP's rows are forward Euler, so the solution is not a trajectory of the continuous model and the feedback cannot make it
+        one: what remains is of the size of one interval's defect (rollout(restart=True)).  Returns the dict of Batch.track, 5 obstacles."""
+        return self._track(5, (TRACK_Q_QUAD, TRACK_R_QUAD, TRACK_QF_QUAD), substeps, dx0, Q, R, Qf, feedback, clamp, need)
 
     def clearance(self, substeps=8, need=0.0):
         """Clearance of the last solution between its nodes, on the device (obca_quad_batch_clearance; numpy: obca_amd.validate.quad_clearance): the straight segment of every
@@ -1003,6 +1095,21 @@ def quadcopter_rollout_batch(x, u, timeScale, Ts, ob, R, substeps=8, restart=Fal
     X = np.zeros((B, N1, 12)) if states else None
     r = _rollout(B, substeps, 5, lambda out: ctx._check(_load().obca_quadcopter_rollout_batch(ctx._h, B, N1 - 1, *ins, out, X), "obca_quadcopter_rollout_batch"))
     return dict(r, **({"states": X} if states else {}))
+
+
+def quadcopter_track_batch(x, u, timeScale, Ts, ob, R, substeps=8, dx0=None, Q=None, R_=None, Qf=None, feedback=True, clamp=True, need=0.0, device=0, states=True, gains=True):
+    """QuadBatch.track for arbitrary trajectories (obca_quadcopter_track_batch): the arguments of quadcopter_rollout_batch (R: the vehicle's radius), then those of
+    QuadBatch.track with the input weights as R_.  Returns the dict of QuadBatch.track, with `states` (B, N+1, 12) and `gains` (B, N, 4, 12) unless switched off."""
+    x = np.asarray(x, float); u = np.asarray(u, float); B, _, N1 = x.shape
+    if x.shape != (B, 12, N1) or u.shape != (B, 4, N1 - 1):
+        raise ObcaError(f"x must be (B,12,N+1) and u (B,4,N); got {x.shape}, {u.shape}")
+    ctx = _ctx(device)
+    q, r, qf = _track_weights(12, 4, Q, R_, Qf, (TRACK_Q_QUAD, TRACK_R_QUAD, TRACK_QF_QUAD))
+    ins = (_per_instance(Ts, B), R, _boxes(ob, B), _in(np.transpose(x, (0, 2, 1))), _in(np.transpose(u, (0, 2, 1))), _time_scale(1.0 if timeScale is None else timeScale, B, N1),
+           int(substeps), int(feedback), int(clamp), q, r, qf, _track_dx0(dx0, B, 12), float(need))
+    X = np.zeros((B, N1, 12)) if states else None; K = np.zeros((B, N1 - 1, 4, 12)) if gains else None
+    t = _track(B, substeps, 5, lambda out: ctx._check(_load().obca_quadcopter_track_batch(ctx._h, B, N1 - 1, *ins, out, X, K), "obca_quadcopter_track_batch"))
+    return dict(t, **({"states": X} if states else {}), **({"gains": K} if gains else {}))
 
 
 def constrSatisfaction(x, u, timeScale, x0, xF, Ts, lam, ob1, ob2, ob3, ob4, ob5, R, device=0):

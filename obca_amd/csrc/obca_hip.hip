@@ -8,6 +8,7 @@
 //   obca_validate_*_kernel  : one wavefront per instance, the a-posteriori feasibility classes of a solution or of a caller's trajectory (obca_validate.h).
 //   obca_clearance_*_kernel : one wavefront per instance, the clearance of a solution or of a caller's trajectory between its nodes (obca_clearance.h).
 //   obca_rollout_*_kernel   : one wavefront per instance, a solution or a caller's trajectory applied to the continuous vehicle model: deviations, clearance of the rolled samples (obca_rollout.h).
+//   obca_track_*_kernel     : one wavefront per instance, TVLQR gains about a solution or a caller's trajectory and the closed loop rolled on the continuous model (obca_track.h).
 //   obca_refine_*_kernel    : one wavefront per destination instance, a solved parking instance on a finer horizon (obca_refine.h): into a second resident batch or host-bound arrays.
 //   obca_quad_subdivide_*_kernel : the same for a solved quadcopter instance (obca_quad_subdivide.h): it rewrites a problem record.
 //   obca_path_ws_*_kernel   : one wavefront per instance, the parking warm start from a planner path (obca_path_ws.h): into host-bound arrays or into a resident batch.
@@ -41,12 +42,14 @@
 #include "obca_refine.h"
 #include "obca_quad_subdivide.h"
 #include "obca_rollout.h"
+#include "obca_track.h"
 #include "../../include/obca_hip.h"
 #include "../../include/obca_path_ws.h"
 #include "../../include/obca_clearance.h"
 #include "../../include/obca_refine.h"
 #include "../../include/obca_quad_subdivide.h"
 #include "../../include/obca_rollout.h"
+#include "../../include/obca_track.h"
 
 using namespace obca;
 #ifdef OBCA_POISON
@@ -61,6 +64,7 @@ static_assert(OBCA_PATH_WS_MAXNODES == PW_MAXNODES, "ABI limits must match the k
 static_assert(OBCA_CLR_OUT == CL_OUT && OBCA_CLR_MAXSUB == CL_SMAX && OBCA_CLR_TOUCH == CL_TOUCH, "ABI limits must match the kernels");
 static_assert(OBCA_REFINE_MAXFACTOR == RF_MAXFACTOR, "ABI limits must match the kernels");
 static_assert(OBCA_ROLL_OUT == RO_OUT && OBCA_ROLL_CLR == RO_CLR && OBCA_ROLL_MAXSUB == CL_SMAX, "ABI limits must match the kernels");
+static_assert(OBCA_TRK_OUT == TK_OUT, "ABI limits must match the kernels");
 static_assert(OBCA_VMAX == OB_VMAX && OBCA_NOBMAX == OB_NOBMAX && OBCA_NMAX == OB_NMAX && OBCA_MMAX == OB_MMAX, "ABI limits must match the kernels");
 
 struct DevBufs {
@@ -343,6 +347,29 @@ __global__ __launch_bounds__(QNT) void obca_rollout_quad_kernel(int B, int N, co
                                 pose + (size_t)inst * s_pose, X + (size_t)inst * s_X, out + (size_t)inst * RO_OUT);
 }
 
+// closed-loop rollout (obca_track.h): one wavefront per instance; the arguments of the rollout kernels with the two modes and the weights, `aux` (s_aux doubles per
+// instance, dx0 first; has_dx0 0: none), then the regions of the work buffer -- [A|B] with the applied inputs behind it (s_AB doubles per instance), the sample poses, the
+// node states -- and the gains (s_K)
+template <int VM>
+__global__ __launch_bounds__(OB_NT) void obca_track_parking_kernel(int B, int N, const double *prob, size_t s_prob, const double *z, size_t s_z, const double *aux, size_t s_aux, int has_dx0, int has_ts,
+                                                                   int S, int feedback, int clamp, trk::Weights w, double need, double *AB, size_t s_AB, double *pose, size_t s_pose,
+                                                                   double *X, size_t s_X, double *K, size_t s_K, double *out) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    const double *a = aux + (size_t)inst * s_aux;
+    trk::track_parking_instance<VM>(N, prob + (size_t)inst * s_prob, z + (size_t)inst * s_z, has_ts ? a + 4 : nullptr, S, feedback, clamp, w, has_dx0 ? a : nullptr, need, 0,
+                                    AB + (size_t)inst * s_AB, AB + (size_t)inst * s_AB + (size_t)N * 4 * 6, pose + (size_t)inst * s_pose, X + (size_t)inst * s_X, K + (size_t)inst * s_K, out + (size_t)inst * TK_OUT);
+}
+__global__ __launch_bounds__(QNT) void obca_track_quad_kernel(int B, int N, const double *prob, size_t s_prob, const double *x, size_t s_x, const double *u, size_t s_u, const double *ts, size_t s_ts, int tstride,
+                                                              const double *aux, size_t s_aux, int has_dx0, int S, int feedback, int clamp, trk::Weights w, double need,
+                                                              double *AB, size_t s_AB, double *pose, size_t s_pose, double *X, size_t s_X, double *K, size_t s_K, double *out) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    trk::track_quad_instance(N, prob + (size_t)inst * s_prob, x + (size_t)inst * s_x, u + (size_t)inst * s_u, ts + (size_t)inst * s_ts, tstride, S, feedback, clamp, w,
+                             has_dx0 ? aux + (size_t)inst * s_aux : nullptr, need, 0, AB + (size_t)inst * s_AB, AB + (size_t)inst * s_AB + (size_t)N * QX * (QX + QU), pose + (size_t)inst * s_pose, X + (size_t)inst * s_X,
+                             K + (size_t)inst * s_K, out + (size_t)inst * TK_OUT);
+}
+
 // warm starts from planner paths (obca_path_ws.h): one wavefront per instance.  paths / dirs: B x rows (x 3) dense on the device -- the rows below the longest count of the
 // call --, `cap` the rows of the caller's arrays (what a count is checked against).  Host-pointer call: outputs per instance, zeros where the status is negative.
 __global__ __launch_bounds__(OB_NT) void obca_path_ws_host_kernel(int B, int N, const double *paths, const int *dirs, const int *counts, int rows, int cap, const double *xF /* 4 x B or NULL */,
@@ -542,6 +569,9 @@ struct BatchCore {
     ValBufs rol;                                            // ... and for the rollout calls (obca_rollout.h)
     DevBuf rol_w;                                           // their work buffer: [ sample poses 3 x (N S + 1) | node states nx x (N + 1) ] x B, allocated by the first call, grown on demand
     int rol_B = 0, rol_N = 0, rol_S = 0;                    // the instances, horizon and sub-steps of the last rollout (0: none yet): where its node states lie in rol_w
+    ValBufs trk;                                            // ... and for the track calls (obca_track.h), with a work buffer of their own: a rollout's node states stay valid
+    DevBuf trk_w, trk_K;                                    // [ [A|B] N nx (nx + nu) + applied inputs N nu | sample poses | node states ] x B; the gains N nu nx x B
+    int trk_B = 0, trk_N = 0, trk_S = 0;                    // as rol_B, rol_N, rol_S
     BatchCore(obca_ctx *c, int dev, hipStream_t s, int B_, int N_) : ctx(c), device(dev), stream(s), B(B_), cap(B_), N(N_) {}
 };
 struct obca_quad_batch : BatchCore {
@@ -603,8 +633,8 @@ static int core_phase_cycles(BatchCore *bt, const double *prof, double *out /* B
 #endif
 // everything of the core that a batch's destroy releases, except `stage` (it goes with the family's device buffers); the batch's device is selected
 static void core_release(BatchCore *bt) {
-    bt->rol_w.release();
-    for (ValBufs *pv : {&bt->val, &bt->clr, &bt->rol}) {
+    bt->rol_w.release(); bt->trk_w.release(); bt->trk_K.release();
+    for (ValBufs *pv : {&bt->val, &bt->clr, &bt->rol, &bt->trk}) {
         ValBufs &v = *pv;
         v.d_in.release(); v.d_out.release(); v.h_in.release(); v.h_out.release(); v.ev.release();
     }
@@ -1087,6 +1117,61 @@ static int batch_rollout_range(obca_batch *bt, bool host, const double *ts, int 
     return rollout_finish(bt, rc, 4, S, lo, X);
 }
 
+// What the two track routes share (obca_track.h), as the rollout's: the work buffer and the gains for B instances before the kernel; after it the bookkeeping of the
+// *_states / *_gains calls and, for a host-pointer call, the chunk's node states and gains into the caller's X and K.
+struct TrackDims { int nx, nu; size_t ab, pose, st, gain; };
+static TrackDims track_dims(const BatchCore *bt, int nx, int nu, int S) {
+    return {nx, nu, trk::track_ab_len(bt->N, nx, nu), roll::rollout_pose_len(bt->N, S), roll::rollout_state_len(bt->N, nx), trk::track_gain_len(bt->N, nx, nu)};
+}
+static int track_reserve(BatchCore *bt, const TrackDims &d) {
+    use_device(bt->device);
+    if (bt->trk_w.reserve((size_t)bt->B * (d.ab + d.pose + d.st), bt->stream) != hipSuccess || bt->trk_K.reserve((size_t)bt->B * d.gain, bt->stream) != hipSuccess) {
+        bt->err = "hipMalloc(track work buffer) failed"; return -2;
+    }
+    return 0;
+}
+static inline double *track_poses_at(BatchCore *bt, const TrackDims &d) { return bt->trk_w + (size_t)bt->B * d.ab; }
+static inline double *track_states_at(BatchCore *bt, const TrackDims &d) { return bt->trk_w + (size_t)bt->B * (d.ab + d.pose); }
+static int track_finish(BatchCore *bt, int rc, const TrackDims &d, int S, int lo, double *X, double *K) {
+    bt->trk_B = bt->trk_N = bt->trk_S = 0;
+    if (rc) return rc;
+    bt->trk_B = bt->B; bt->trk_N = bt->N; bt->trk_S = S;
+    if (X) HIPCHK(bt, hipMemcpy(X + (size_t)lo * d.st, track_states_at(bt, d), (size_t)bt->B * d.st * sizeof(double), hipMemcpyDeviceToHost));      // (run_validate has synchronised the stream)
+    if (K) HIPCHK(bt, hipMemcpy(K + (size_t)lo * d.gain, (const double *)bt->trk_K, (size_t)bt->B * d.gain * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+static int track_fetch(BatchCore *bt, int nx, int nu, bool gains, double *dst, const char *entry) {
+    if (!dst) { bt->ctx->err = std::string(entry) + ": NULL argument"; return -1; }
+    if (!bt->trk_B || bt->trk_B != bt->B || bt->trk_N != bt->N) { bt->ctx->err = std::string(entry) + ": no track call has run on this batch since it was last filled"; return -1; }
+    const TrackDims d = track_dims(bt, nx, nu, bt->trk_S);
+    use_device(bt->device);
+    if (hipStreamSynchronize(bt->stream) != hipSuccess ||
+        hipMemcpy(dst, gains ? (const double *)bt->trk_K : track_states_at(bt, d), (size_t)bt->B * (gains ? d.gain : d.st) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+        bt->ctx->err = std::string(entry) + ": D2H failed"; return -2;
+    }
+    return 0;
+}
+// The closed-loop rollout of the batch's parking instances: the arguments of batch_rollout_range with the modes, the weights and dx0 (4 per instance of the call, or nullptr);
+// per instance [ dx0 4 | timeScale N + 1 (host-pointer calls) ] travels up
+static int batch_track_range(obca_batch *bt, bool host, const double *ts, int S, int feedback, int clamp, const trk::Weights &w, const double *dx0, double need, int lo, double *out, double *X, double *K) {
+    const int B = bt->B, N = bt->N, N1 = N + 1;
+    const TrackDims d = track_dims(bt, 4, 2, S);
+    if (int rc = track_reserve(bt, d)) return rc;
+    const size_t W = 4 + (ts ? (size_t)N1 : 0);
+    const int rc = run_validate(bt, bt->trk, W, true, TK_OUT, [&](int i, double *a) {
+        if (dx0) memcpy(a, dx0 + ((size_t)lo + i) * 4, sizeof(double) * 4); else memset(a, 0, sizeof(double) * 4);
+        if (ts) memcpy(a + 4, ts + ((size_t)lo + i) * N1, sizeof(double) * N1);
+    }, [&] {
+        const double *z = host ? bt->d.z0 : bt->d.z;
+#define TRK_LAUNCH(VM) hipLaunchKernelGGL(obca_track_parking_kernel<VM>, dim3(B), dim3(OB_NT), 0, bt->stream, B, N, (const double *)bt->d.prob, bt->d.s_prob, z, bt->d.s_z, (const double *)bt->trk.d_in, W, \
+                                          dx0 ? 1 : 0, ts ? 1 : 0, S, feedback, clamp, w, need, (double *)bt->trk_w, d.ab, track_poses_at(bt, d), d.pose, track_states_at(bt, d), d.st, \
+                                          (double *)bt->trk_K, d.gain, (double *)bt->trk.d_out)
+        if (bt->vmax <= 2) TRK_LAUNCH(2); else if (bt->vmax <= OB_VMID) TRK_LAUNCH(OB_VMID); else TRK_LAUNCH(OB_VMAX);      // (the row class of launch_dualws)
+#undef TRK_LAUNCH
+    }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * TK_OUT, o, sizeof(double) * TK_OUT); });
+    return track_finish(bt, rc, d, S, lo, X, K);
+}
+
 // ---- chunked execution of a host-pointer call over the slots of the context (work queue)
 template <typename F>
 static int run_chunks(obca_ctx *ctx, int B, int chunk, F &&fn /* int(Slot &, int lo, int n, std::string &err) */) {
@@ -1307,6 +1392,32 @@ int obca_parking_rollout_batch(obca_ctx *ctx, int B, int N, const double *Ts, do
     ParkIn in = {Ts, L, ego, XYb, 0, nullptr, nullptr, nOb, vOb, A, b, zero.data(), zero.data(), zero.data(), x, u, nullptr, nullptr, {}, {}};
     if (int rc = park_prefix(ctx->err, B, nOb, vOb, in)) return rc;
     return parking_chunks(ctx, 0, B, N, in, [&](obca_batch *bt, int lo) { return batch_rollout_range(bt, true, timeScale, substeps, restart, need, lo, out, X); });
+}
+
+int obca_batch_track(obca_batch *bt, int substeps, int feedback, int clamp, const double q[4], const double r[2], const double qf[4], const double *dx0, double need, double *out) {
+    if (!bt) return -1;
+    if (!out) { bt->ctx->err = "obca_batch_track: NULL argument"; return -1; }
+    if (const char *bad = trk::track_check_args(substeps, feedback, clamp, q, r, qf, 4, 2, need)) { bt->ctx->err = std::string("obca_batch_track: ") + bad; return -1; }
+    if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_batch_track: nothing has been solved since the last upload or shift"; return -1; }
+    if (bt->N < 1) { bt->ctx->err = "obca_batch_track: needs a horizon N>=1"; return -1; }
+    return fin(bt, batch_track_range(bt, false, nullptr, substeps, feedback, clamp, trk::make_weights(q, r, qf, 4, 2), dx0, need, 0, out, nullptr, nullptr));
+}
+int obca_batch_track_ms(obca_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->trk.ev, ms, "obca_batch_track_ms: no track call has run on this batch") : -1; }
+int obca_batch_track_states(obca_batch *bt, double *X) { return bt ? track_fetch(bt, 4, 2, false, X, "obca_batch_track_states") : -1; }
+int obca_batch_track_gains(obca_batch *bt, double *K) { return bt ? track_fetch(bt, 4, 2, true, K, "obca_batch_track_gains") : -1; }
+int obca_parking_track_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const int *nOb, const int *vOb, const double *A, const double *b,
+                             const double *x, const double *u, const double *timeScale, int substeps, int feedback, int clamp, const double q[4], const double r[2], const double qf[4],
+                             const double *dx0, double need, double *out, double *X, double *K) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 1 || N > OBCA_NMAX) { ctx->err = "obca_parking_track_batch: need B>=1, 1<=N<=OBCA_NMAX"; return -1; }
+    if (!Ts || !ego || !nOb || !vOb || !A || !b || !x || !u || !out) { ctx->err = "obca_parking_track_batch: NULL argument"; return -1; }
+    if (const char *bad = trk::track_check_args(substeps, feedback, clamp, q, r, qf, 4, 2, need)) { ctx->err = std::string("obca_parking_track_batch: ") + bad; return -1; }
+    const std::vector<double> zero((size_t)B * (N + 1), 0.0);      // the tracking reference of a solve: the call does not read it (nor the bounds, the start and the goal)
+    const double XYb[4] = {0, 0, 0, 0};
+    ParkIn in = {Ts, L, ego, XYb, 0, nullptr, nullptr, nOb, vOb, A, b, zero.data(), zero.data(), zero.data(), x, u, nullptr, nullptr, {}, {}};
+    if (int rc = park_prefix(ctx->err, B, nOb, vOb, in)) return rc;
+    const trk::Weights w = trk::make_weights(q, r, qf, 4, 2);
+    return parking_chunks(ctx, 0, B, N, in, [&](obca_batch *bt, int lo) { return batch_track_range(bt, true, timeScale, substeps, feedback, clamp, w, dx0, need, lo, out, X, K); });
 }
 
 int obca_parking_signed_dist_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const double XYb[4],
@@ -1693,6 +1804,27 @@ static int quad_rollout_range(obca_quad_batch *bt, const double *u, const double
     }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * RO_OUT, o, sizeof(double) * RO_OUT); });
     return rollout_finish(bt, rc, QX, S, lo, X);
 }
+// the closed-loop rollout of the batch's quadcopter instances (obca_track.h): quad_rollout_range with the modes, the weights and dx0; per instance
+// [ dx0 12 | timeScale (N + 1) | u 4 x N (the last two: host-pointer calls) ] travels up
+static int quad_track_range(obca_quad_batch *bt, const double *u, const double *ts, int S, int feedback, int clamp, const trk::Weights &w, const double *dx0, double need, int lo, double *out, double *X, double *K) {
+    const int B = bt->B, N = bt->N, N1 = N + 1; const QDevBufs &qd = bt->d;
+    quad::QLay l; quad::q_make_layout(N, l);
+    const TrackDims d = track_dims(bt, QX, QU, S);
+    if (int rc = track_reserve(bt, d)) return rc;
+    const size_t W = (size_t)QX + (ts ? (size_t)N1 + (size_t)QU * N : 0);
+    const int rc = run_validate(bt, bt->trk, W, true, TK_OUT, [&](int i, double *a) {
+        if (dx0) memcpy(a, dx0 + ((size_t)lo + i) * QX, sizeof(double) * QX); else memset(a, 0, sizeof(double) * QX);
+        if (ts) { memcpy(a + QX, ts + ((size_t)lo + i) * N1, sizeof(double) * N1); memcpy(a + QX + N1, u + ((size_t)lo + i) * QU * N, sizeof(double) * QU * N); }
+    }, [&] {
+        const double *in = bt->trk.d_in;
+        if (ts) hipLaunchKernelGGL(obca_track_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)qd.prob, qd.s_prob, (const double *)qd.prob + QPH_SIZE, qd.s_prob, in + QX + N1, W, in + QX, W, 1,
+                                   in, W, dx0 ? 1 : 0, S, feedback, clamp, w, need, (double *)bt->trk_w, d.ab, track_poses_at(bt, d), d.pose, track_states_at(bt, d), d.st, (double *)bt->trk_K, d.gain, (double *)bt->trk.d_out);
+        else hipLaunchKernelGGL(obca_track_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)qd.prob, qd.s_prob, (const double *)qd.z + l.x, qd.s_z, (const double *)qd.z + l.u, qd.s_z,
+                                (const double *)qd.z + l.t, qd.s_z, 0, in, W, dx0 ? 1 : 0, S, feedback, clamp, w, need, (double *)bt->trk_w, d.ab, track_poses_at(bt, d), d.pose, track_states_at(bt, d), d.st,
+                                (double *)bt->trk_K, d.gain, (double *)bt->trk.d_out);
+    }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * TK_OUT, o, sizeof(double) * TK_OUT); });
+    return track_finish(bt, rc, d, S, lo, X, K);
+}
 // instances (one wavefront each) resident per CU, as OBCA_RESIDENT_PER_CU for the parking kernel: what pick_chunk sizes a quadcopter chunk by
 static const int QUAD_RESIDENT_PER_CU = (QNT == 64 ? 4 : 2) * OBCA_QUAD_WAVES_PER_EU;
 // parking_chunks for the quadcopter; the slot's cached batch only has to hold the chunk at hand
@@ -1802,6 +1934,27 @@ int obca_quadcopter_rollout_batch(obca_ctx *ctx, int B, int N, const double *Ts,
     const std::vector<double> zero((size_t)B * QX, 0.0), one((size_t)B, 1.0);      // start, goal and timeWS of a solve: the call reads none of them
     const QuadIn in = {Ts, R, zero.data(), zero.data(), ob, x, one.data(), 0, 0};
     return quad_chunks(ctx, B, N, in, [&](obca_quad_batch *bt, int lo) { return quad_rollout_range(bt, u, timeScale, substeps, restart, need, lo, out, X); });
+}
+int obca_quad_batch_track(obca_quad_batch *bt, int substeps, int feedback, int clamp, const double q[12], const double r[4], const double qf[12], const double *dx0, double need, double *out) {
+    if (!bt) return -1;
+    if (!out) { bt->ctx->err = "obca_quad_batch_track: NULL argument"; return -1; }
+    if (const char *bad = trk::track_check_args(substeps, feedback, clamp, q, r, qf, QX, QU, need)) { bt->ctx->err = std::string("obca_quad_batch_track: ") + bad; return -1; }
+    if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_quad_batch_track: nothing has been solved since the last upload or shift"; return -1; }
+    return fin(bt, quad_track_range(bt, nullptr, nullptr, substeps, feedback, clamp, trk::make_weights(q, r, qf, QX, QU), dx0, need, 0, out, nullptr, nullptr));
+}
+int obca_quad_batch_track_ms(obca_quad_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->trk.ev, ms, "obca_quad_batch_track_ms: no track call has run on this batch") : -1; }
+int obca_quad_batch_track_states(obca_quad_batch *bt, double *X) { return bt ? track_fetch(bt, QX, QU, false, X, "obca_quad_batch_track_states") : -1; }
+int obca_quad_batch_track_gains(obca_quad_batch *bt, double *K) { return bt ? track_fetch(bt, QX, QU, true, K, "obca_quad_batch_track_gains") : -1; }
+int obca_quadcopter_track_batch(obca_ctx *ctx, int B, int N, const double *Ts, double R, const double *ob, const double *x, const double *u, const double *timeScale,
+                                int substeps, int feedback, int clamp, const double q[12], const double r[4], const double qf[12], const double *dx0, double need, double *out, double *X, double *K) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 2 || N > OBCA_QUAD_NMAX) { ctx->err = "obca_quadcopter_track_batch: need B>=1, 2<=N<=OBCA_QUAD_NMAX"; return -1; }
+    if (!Ts || !ob || !x || !u || !timeScale || !out) { ctx->err = "obca_quadcopter_track_batch: NULL argument"; return -1; }
+    if (const char *bad = trk::track_check_args(substeps, feedback, clamp, q, r, qf, QX, QU, need)) { ctx->err = std::string("obca_quadcopter_track_batch: ") + bad; return -1; }
+    const std::vector<double> zero((size_t)B * QX, 0.0), one((size_t)B, 1.0);      // start, goal and timeWS of a solve: the call reads none of them
+    const QuadIn in = {Ts, R, zero.data(), zero.data(), ob, x, one.data(), 0, 0};
+    const trk::Weights w = trk::make_weights(q, r, qf, QX, QU);
+    return quad_chunks(ctx, B, N, in, [&](obca_quad_batch *bt, int lo) { return quad_track_range(bt, u, timeScale, substeps, feedback, clamp, w, dx0, need, lo, out, X, K); });
 }
 int obca_quad_batch_download(obca_quad_batch *bt, double *xp, double *up, double *ts, int *exitflag, double *lp, double *slp, double *info) {
     if (!bt) return -1;

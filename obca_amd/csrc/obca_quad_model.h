@@ -76,6 +76,25 @@ OBCA_FN void dyn_g_continuous(const double *x, const double *u, double g[QX]) {
     g[11] = (Q_KM * (u[0] * u[0] - u[1] * u[1] + u[2] * u[2] - u[3] * u[3]) - (Q_I2 - Q_I1) * x[9] * x[10]) / Q_I3;
 }
 
+// The directional derivative of dyn_g_continuous at (x, u) along (dx, du): dg = g_x dx + g_u du, term by term in the order of the terms above, for the linearisation of
+// the interval map (obca_track.h).  Written by hand; tests/test_track_cpu.py holds it against automatic differentiation.  No solve kernel calls this.
+OBCA_FN void dyn_g_continuous_jvp(const double *x, const double *u, const double *dx, const double *du, double dg[QX]) {
+    const double s4 = sin(x[3]), c4 = cos(x[3]), s5 = sin(x[4]), c5 = cos(x[4]), s6 = sin(x[5]), c6 = cos(x[5]);
+    const double usq = u[0] * u[0] + u[1] * u[1] + u[2] * u[2] + u[3] * u[3];
+    const double dusq = 2.0 * (u[0] * du[0] + u[1] * du[1] + u[2] * du[2] + u[3] * du[3]);
+    const double tn = s4 / c4, sc = 1.0 / (c4 * c4);      // tan x[3] and its derivative
+    dg[0] = dx[6]; dg[1] = dx[7]; dg[2] = dx[8];
+    dg[3] = (c5 * x[11] - s5 * x[9]) * dx[4] + c5 * dx[9] + s5 * dx[11];
+    dg[4] = (s5 * x[9] - c5 * x[11]) * sc * dx[3] + (c5 * x[9] + s5 * x[11]) * tn * dx[4] + s5 * tn * dx[9] + dx[10] - c5 * tn * dx[11];
+    dg[5] = (c5 * x[11] - s5 * x[9]) * tn / c4 * dx[3] - (c5 * x[9] + s5 * x[11]) / c4 * dx[4] - s5 / c4 * dx[9] + c5 / c4 * dx[11];
+    dg[6] = Q_KF / Q_MASS * (dusq * (s4 * c5 * s6 + s5 * c6) + usq * (c4 * c5 * s6 * dx[3] + (c5 * c6 - s4 * s5 * s6) * dx[4] + (s4 * c5 * c6 - s5 * s6) * dx[5]));
+    dg[7] = Q_KF / Q_MASS * (dusq * (s5 * s6 - s4 * c5 * c6) + usq * ((s4 * s5 * c6 + c5 * s6) * dx[4] - c4 * c5 * c6 * dx[3] + (s4 * c5 * s6 + s5 * c6) * dx[5]));
+    dg[8] = Q_KF / Q_MASS * (dusq * c4 * c5 - usq * (s4 * c5 * dx[3] + c4 * s5 * dx[4]));
+    dg[9] = (Q_ARM * Q_KF * 2.0 * (u[1] * du[1] - u[3] * du[3]) - (Q_I3 - Q_I2) * (dx[10] * x[11] + x[10] * dx[11])) / Q_I1;
+    dg[10] = (Q_ARM * Q_KF * 2.0 * (u[2] * du[2] - u[0] * du[0]) - (Q_I1 - Q_I3) * (dx[9] * x[11] + x[9] * dx[11])) / Q_I2;
+    dg[11] = (Q_KM * 2.0 * (u[0] * du[0] - u[1] * du[1] + u[2] * du[2] - u[3] * du[3]) - (Q_I2 - Q_I1) * (dx[9] * x[10] + x[9] * dx[10])) / Q_I3;
+}
+
 // value, Jacobian rows 3..11 w.r.t. the QV local variables (dg[i-3][a]) and HG = sum_i w_i Hess g_i (upper triangle, packed 55)
 OBCA_FN int q_pidx(int a, int b) { int i = a < b ? a : b, j = a < b ? b : a; return i * QV - i * (i - 1) / 2 + (j - i); }
 OBCA_FN void dyn_g_derivs(const QConsts &c, const double *x, const double *u, const double *w, double g[QX], double dg[9][QV], double HG[55]) {

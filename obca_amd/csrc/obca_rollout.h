@@ -54,6 +54,12 @@ struct ParkModel {
         d[0] = x[3] * cos(x[2]); d[1] = x[3] * sin(x[2]); d[2] = x[3] * u[0] / L; d[3] = u[1];      // u[0]: tan(delta), taken once per interval (prep)
     }
     RO_MEMBER void prep(double *u) { u[0] = tan(u[0]); }
+    // the tangent of rhs along (dx, du) and of prep (u: prep's result, tan' = 1 + tan^2), for the linearisation of the interval map (obca_track.h)
+    RO_MEMBER void jvp(double L, const double *x, const double *u, const double *dx, const double *du, double *d) {
+        const double sn = sin(x[2]), cs = cos(x[2]);
+        d[0] = dx[3] * cs - x[3] * sn * dx[2]; d[1] = dx[3] * sn + x[3] * cs * dx[2]; d[2] = (dx[3] * u[0] + x[3] * du[0]) / L; d[3] = du[1];
+    }
+    RO_MEMBER void prep_jvp(const double *u, double *du) { du[0] = (1.0 + u[0] * u[0]) * du[0]; }
     RO_MEMBER double pole(const double *x) { return 1.0; }      // the bicycle has no singular state
     // position, attitude, velocity, body-rate deviation of a rolled state X from the solution's node x
     RO_MEMBER void dev(const double *X, const double *x, double d[RD_N]) {
@@ -65,6 +71,8 @@ struct QuadModel {
     enum { NX = QX, NU = QU };
     RO_MEMBER void rhs(double, const double *x, const double *u, double *d) { quad::dyn_g_continuous(x, u, d); }
     RO_MEMBER void prep(double *u) {}
+    RO_MEMBER void jvp(double, const double *x, const double *u, const double *dx, const double *du, double *d) { quad::dyn_g_continuous_jvp(x, u, dx, du, d); }
+    RO_MEMBER void prep_jvp(const double *u, double *du) {}
     // the attitude kinematics divide by cos x[3]: where it changes sign within a step the continuous state has diverged (the integral of tan), though RK4 steps across with finite numbers
     RO_MEMBER double pole(const double *x) { return cos(x[3]); }
     RO_MEMBER void dev(const double *X, const double *x, double d[RD_N]) {
@@ -76,6 +84,18 @@ struct QuadModel {
         d[RD_VEL] = sqrt(e[6] * e[6] + e[7] * e[7] + e[8] * e[8]);
         d[RD_RATE] = val::vmax(val::vmax(fabs(e[9]), fabs(e[10])), fabs(e[11]));
     }
+};
+
+// What a caller may put into the chain (obca_track.h: the feedback): start(X) once, on the first state; input(k, X, uk) at the first state X of interval k returns where
+// the interval's input is read from (uk: the trajectory's own).  The rollout itself does neither: with NoHook every instantiation below compiles to what it was without the parameter.
+#ifdef OBCA_EMU
+#define RO_METHOD inline
+#else
+#define RO_METHOD __device__ __forceinline__
+#endif
+struct NoHook {
+    RO_METHOD void start(double *) {}
+    RO_METHOD const double *input(int, const double *, const double *uk) { return uk; }
 };
 
 // one classical RK4 step of length h, u held: X <- X + h / 6 (k1 + 2 k2 + 2 k3 + k4)
@@ -98,14 +118,15 @@ OBCA_FN void rk4_step(double L, double h, const double *u, double *X) {
 
 // Phase 2.  x: NX x (N + 1), u: NU x N stage-contiguous; hk(k): the length of interval k.  pose: 3 x (N S + 1), Xn: NX x (N + 1) of this instance.  Returns in
 // bad[LI(lane)] whether the lane met a non-finite state.  All loop bounds are known at launch.
-template <class M, class H>
-OBCA_FN void integrate(double L, int N, int S, int restart, const double *x, const double *u, H &&hk, double *pose, double *Xn, double (&bad)[OBCA_NL]) {
+template <class M, class H, class F = NoHook>
+OBCA_FN void integrate(double L, int N, int S, int restart, const double *x, const double *u, H &&hk, double *pose, double *Xn, double (&bad)[OBCA_NL], F &&fb = F()) {
     PAR(lane) {
         double b = 0.0;
         const int k0 = restart ? lane : (lane == 0 ? 0 : N), dk = restart ? OB_NT : 1;
         double X[M::NX];
 #pragma unroll
         for (int i = 0; i < M::NX; i++) X[i] = x[i];
+        fb.start(X);
         if (lane == 0) {
 #pragma unroll
             for (int i = 0; i < M::NX; i++) Xn[i] = X[i];
@@ -116,8 +137,9 @@ OBCA_FN void integrate(double L, int N, int S, int restart, const double *x, con
                 for (int i = 0; i < M::NX; i++) X[i] = x[M::NX * k + i];
             }
             double U[M::NU];
+            const double *uk = fb.input(k, X, u + M::NU * k);
 #pragma unroll
-            for (int i = 0; i < M::NU; i++) U[i] = u[M::NU * k + i];
+            for (int i = 0; i < M::NU; i++) U[i] = uk[i];
             M::prep(U);
             const double h = hk(k) / (double)S;
             for (int s = 0; s < S; s++) {
@@ -197,8 +219,8 @@ OBCA_FN void write_head(int N, int S, int restart, const double *x, const double
 // p: problem header (PH_*: unit-length rows), z: a point in the solver's layout (x, u and t are read); ts: the caller's timeScale per stage (N + 1; nullptr: the point's
 // single t, 1 with fixTime); S: sub-steps, 1 .. CL_SMAX; pose / Xn: this instance's slices of the work buffer; out: RO_OUT doubles.  VM: the row class of the batch's
 // widest obstacle.  Needs 1 <= N <= OB_NMAX.
-template <int VM>
-OBCA_FN void rollout_parking_instance(int N, const double *p, const double *z, const double *ts, int S, int restart, double need, int rev, double *pose, double *Xn, double *out) {
+template <int VM, class F = NoHook>
+OBCA_FN void rollout_parking_instance(int N, const double *p, const double *z, const double *ts, int S, int restart, double need, int rev, double *pose, double *Xn, double *out, F &&fb = F()) {
     CL_LDS unsigned char hit[CL_MAXSAMPLES];
     const int nOb = (int)p[PH_NOB], M = (int)p[PH_M];
     Lay l; make_layout(N, nOb, M, l);
@@ -215,7 +237,7 @@ OBCA_FN void rollout_parking_instance(int N, const double *p, const double *z, c
         for (int q = lane; q < nS; q += OB_NT) hit[q] = 0;
     }
     if (wred_max(acc[CA_BAD]) != 0.0) { write_all_bad(N, 4, S, restart, Xn, out); return; }
-    integrate<ParkModel>(p[PH_L], N, S, restart, z + l.x, z + l.u, [&](int k) { return (ts ? ts[k] : t1) * Ts; }, pose, Xn, acc[CA_BAD]);
+    integrate<ParkModel>(p[PH_L], N, S, restart, z + l.x, z + l.u, [&](int k) { return (ts ? ts[k] : t1) * Ts; }, pose, Xn, acc[CA_BAD], fb);
     if (wred_max(acc[CA_BAD]) != 0.0) { write_all_bad(N, 4, S, restart, Xn, out); return; }
     SYNC();
     PAR(lane) {
@@ -249,9 +271,10 @@ OBCA_FN void rollout_parking_instance(int N, const double *p, const double *z, c
 }
 
 // p: quadcopter problem header (QPH_*: Ts, R, the boxes as [hi; -lo]); x: 12 x (N + 1), u: 4 x N stage-contiguous; ts[k * tstride] is timeScale[k] (tstride 0: one t).
-// Needs 1 <= N <= QNMAX.
+// Needs 1 <= N <= QNMAX.  fb: see NoHook.
+template <class F = NoHook>
 OBCA_FN void rollout_quad_instance(int N, const double *p, const double *x, const double *u, const double *ts, int tstride, int S, int restart, double need, int rev,
-                                   double *pose, double *Xn, double *out) {
+                                   double *pose, double *Xn, double *out, F &&fb = F()) {
     CL_LDS unsigned char hit[CL_MAXSAMPLES];
     const double Ts = p[QPH_TS], R = p[QPH_R];
     const int nS = N * S + 1, nIt = nS * QOB, rounds = (nIt + QNT - 1) / QNT;
@@ -265,7 +288,7 @@ OBCA_FN void rollout_quad_instance(int N, const double *p, const double *x, cons
         for (int q = lane; q < nS; q += QNT) hit[q] = 0;
     }
     if (wred_max(acc[CA_BAD]) != 0.0) { write_all_bad(N, QX, S, restart, Xn, out); return; }
-    integrate<QuadModel>(0.0, N, S, restart, x, u, [&](int k) { return ts[k * tstride] * Ts; }, pose, Xn, acc[CA_BAD]);
+    integrate<QuadModel>(0.0, N, S, restart, x, u, [&](int k) { return ts[k * tstride] * Ts; }, pose, Xn, acc[CA_BAD], fb);
     if (wred_max(acc[CA_BAD]) != 0.0) { write_all_bad(N, QX, S, restart, Xn, out); return; }
     SYNC();
     PAR(lane) {

@@ -18,6 +18,8 @@ refine_parking : the numpy statement of the refinement of a solved parking insta
 refine_quad : the same for a solved quadcopter instance (obca_amd/csrc/obca_quad_subdivide.h, QuadBatch.refine).
 rollout_parking, rollout_quad, rollout_record : the numpy statement of the rollout of a solution on the continuous vehicle models (obca_amd/csrc/obca_rollout.h,
     Batch.rollout, QuadBatch.rollout): held inputs, classical RK4, the rolled node states, the sample poses and the record of deviations and clearances.
+track_gains_parking, track_gains_quad, track_parking, track_quad, track_record : the numpy statement of the closed-loop rollout (obca_amd/csrc/obca_track.h, Batch.track,
+    QuadBatch.track): the interval map's derivatives by forward-mode tangents, the Riccati recursion, the held TVLQR feedback on the continuous models and its record.
 Shapes follow the reference: x (4,N+1), u (2,N), l (M,N+1), n (4nOb,N+1), timeScale (N+1,) .
 """
 import math
@@ -389,4 +391,227 @@ def rollout_record(x, X, c, substeps, restart, need, finite=True):
     else:
         d = np.array([np.sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]), np.abs(e[3:6]).max(axis=0), np.sqrt(e[6] * e[6] + e[7] * e[7] + e[8] * e[8]), np.abs(e[9:12]).max(axis=0)])
     r[1] = d[0].max(); r[2] = 1 + int(np.argmax(d[0])); r[3:6] = d[1:].max(axis=1); r[6:10] = d[:, -1]
+    return r
+
+
+# ---------------------------------------------------------------- closed-loop rollout: TVLQR gains about a trajectory (obca_amd/csrc/obca_track.h)
+TRK_OUT = 48          # doubles of a record: the ROLL_OUT doubles of the chain, feedback, clamp, saturated, du_max, du_node, dx0_pos, 2 x 0
+# Default weights: the values the first prototype ran with.  UNTUNED.
+TRACK_Q_PARKING = (10.0, 10.0, 10.0, 1.0); TRACK_R_PARKING = (1.0, 1.0); TRACK_QF_PARKING = tuple(10.0 * v for v in TRACK_Q_PARKING)
+TRACK_Q_QUAD = (10.0, 10.0, 10.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.1, 0.1, 0.1); TRACK_R_QUAD = (0.1, 0.1, 0.1, 0.1); TRACK_QF_QUAD = tuple(10.0 * v for v in TRACK_Q_QUAD)
+_PARK_UBOX = ((-0.6, 0.6), (-0.4, 0.4)); _QUAD_UBOX = ((1.2, 7.8),) * 4      # the NLP's own input bounds (OB_UL0 .. OB_UU1; Q_ULO, Q_UHI)
+
+
+def _park_jvp(x, u, dx, du, L):
+    """the tangent of _park_rhs along (dx, du): ParkModel::jvp, term by term.  dx, du: one row per component, a row holds all directions"""
+    sn, cs = math.sin(x[2]), math.cos(x[2])
+    return [dx[3] * cs - x[3] * sn * dx[2], dx[3] * sn + x[3] * cs * dx[2], (dx[3] * u[0] + x[3] * du[0]) / L, du[1] + 0.0]
+
+
+def _quad_jvp(x, u, dx, du, _=None):
+    """the tangent of _quad_rhs along (dx, du): quad::dyn_g_continuous_jvp, term by term"""
+    q = _QC; s4, c4, s5, c5, s6, c6 = math.sin(x[3]), math.cos(x[3]), math.sin(x[4]), math.cos(x[4]), math.sin(x[5]), math.cos(x[5])
+    usq = u[0] * u[0] + u[1] * u[1] + u[2] * u[2] + u[3] * u[3]
+    dusq = 2.0 * (u[0] * du[0] + u[1] * du[1] + u[2] * du[2] + u[3] * du[3])
+    tn = s4 / c4; sc = 1.0 / (c4 * c4); a = q["kF"] / q["m"]
+    return [dx[6] + 0.0, dx[7] + 0.0, dx[8] + 0.0,
+            (c5 * x[11] - s5 * x[9]) * dx[4] + c5 * dx[9] + s5 * dx[11],
+            (s5 * x[9] - c5 * x[11]) * sc * dx[3] + (c5 * x[9] + s5 * x[11]) * tn * dx[4] + s5 * tn * dx[9] + dx[10] - c5 * tn * dx[11],
+            (c5 * x[11] - s5 * x[9]) * tn / c4 * dx[3] - (c5 * x[9] + s5 * x[11]) / c4 * dx[4] - s5 / c4 * dx[9] + c5 / c4 * dx[11],
+            a * (dusq * (s4 * c5 * s6 + s5 * c6) + usq * (c4 * c5 * s6 * dx[3] + (c5 * c6 - s4 * s5 * s6) * dx[4] + (s4 * c5 * c6 - s5 * s6) * dx[5])),
+            a * (dusq * (s5 * s6 - s4 * c5 * c6) + usq * ((s4 * s5 * c6 + c5 * s6) * dx[4] - c4 * c5 * c6 * dx[3] + (s4 * c5 * s6 + s5 * c6) * dx[5])),
+            a * (dusq * c4 * c5 - usq * (s4 * c5 * dx[3] + c4 * s5 * dx[4])),
+            (q["arm"] * q["kF"] * 2.0 * (u[1] * du[1] - u[3] * du[3]) - (q["I3"] - q["I2"]) * (dx[10] * x[11] + x[10] * dx[11])) / q["I1"],
+            (q["arm"] * q["kF"] * 2.0 * (u[2] * du[2] - u[0] * du[0]) - (q["I1"] - q["I3"]) * (dx[9] * x[11] + x[9] * dx[11])) / q["I2"],
+            (q["kM"] * 2.0 * (u[0] * du[0] - u[1] * du[1] + u[2] * du[2] - u[3] * du[3]) - (q["I2"] - q["I1"]) * (dx[9] * x[10] + x[9] * dx[10])) / q["I3"]]
+
+
+def _rk4_tan(f, jvp, X, T, u, du, h, L):
+    """one classical RK4 step with its tangent, in the order of trk::rk4_step_tan"""
+    n = len(X)
+    k = f(X, u, L); dk = jvp(X, u, T, du, L); acc = list(k); dacc = list(dk)
+    xt = [X[i] + h / 2 * k[i] for i in range(n)]; dxt = [T[i] + h / 2 * dk[i] for i in range(n)]
+    k = f(xt, u, L); dk = jvp(xt, u, dxt, du, L); acc = [acc[i] + 2 * k[i] for i in range(n)]; dacc = [dacc[i] + 2 * dk[i] for i in range(n)]
+    xt = [X[i] + h / 2 * k[i] for i in range(n)]; dxt = [T[i] + h / 2 * dk[i] for i in range(n)]
+    k = f(xt, u, L); dk = jvp(xt, u, dxt, du, L); acc = [acc[i] + 2 * k[i] for i in range(n)]; dacc = [dacc[i] + 2 * dk[i] for i in range(n)]
+    xt = [X[i] + h * k[i] for i in range(n)]; dxt = [T[i] + h * dk[i] for i in range(n)]
+    k = f(xt, u, L); dk = jvp(xt, u, dxt, du, L)
+    return [X[i] + h / 6 * (acc[i] + k[i]) for i in range(n)], [T[i] + h / 6 * (dacc[i] + dk[i]) for i in range(n)]
+
+
+def _linearise(f, jvp, parking, x, u, timeScale, Ts, L, substeps):
+    """[A_k | B_k] (N, nx, nx + nu): the derivative of the interval map (S RK4 steps of h_k / S, the input held) at (x_k, u_k), by forward-mode tangents through the steps"""
+    x = np.asarray(x, float); u = np.asarray(u, float); nx, N1 = x.shape; N = N1 - 1; nu = u.shape[0]; nd = nx + nu; S = int(substeps); ts = _stage_scale(timeScale, N)
+    AB = np.zeros((N, nx, nd))
+    for k in range(N):
+        X = [float(v) for v in x[:, k]]; U = [float(v) for v in u[:, k]]; E = np.eye(nd)
+        T = [E[i].copy() for i in range(nx)]; dU = [E[nx + a].copy() for a in range(nu)]
+        try:
+            if parking:      # prep: tan(delta) once per interval, and its tangent 1 + tan^2
+                U[0] = math.tan(U[0]); dU[0] = (1.0 + U[0] * U[0]) * dU[0]
+            h = float(ts[k]) * float(Ts) / S
+            for _ in range(S):
+                X, T = _rk4_tan(f, jvp, X, T, U, dU, h, L)
+            AB[k] = np.array(T)
+        except (OverflowError, ValueError, ZeroDivisionError):      # (Python's math raises where C returns inf / NaN)
+            AB[k] = np.nan
+    return AB
+
+
+def _riccati(AB, nx, q, r, qf):
+    """K (N, nu, nx), P_0 and whether every pivot was finite and positive: P_N = diag(qf); G = diag(r) + B'PB = C C' (unpivoted), K_k = -G^-1 B'PA,
+    P <- diag(q) + A'PA + (B'PA)' K_k, P <- (P + P') / 2"""
+    N, _, nd = AB.shape; nu = nd - nx; P = np.diag(np.asarray(qf, float)); K = np.zeros((N, nu, nx)); ok = True
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for k in range(N - 1, -1, -1):
+            M = AB[k].T @ (P @ AB[k]); H = M[nx:, :nx]; C = np.zeros((nu, nu))
+            for a in range(nu):
+                for c in range(a + 1):
+                    s = M[nx + a, nx + c] + (r[a] if a == c else 0.0)
+                    for t in range(c):
+                        s = s - C[a, t] * C[c, t]
+                    if a == c:
+                        ok = ok and bool(s > 0.0 and np.isfinite(s)); C[a, a] = np.sqrt(s)
+                    else:
+                        C[a, c] = s / C[c, c]
+            y = [None] * nu
+            for a in range(nu):
+                s = H[a].copy()
+                for t in range(a):
+                    s = s - C[a, t] * y[t]
+                y[a] = s / C[a, a]
+            for a in range(nu - 1, -1, -1):
+                s = y[a]
+                for t in range(a + 1, nu):
+                    s = s - C[t, a] * y[t]
+                y[a] = s / C[a, a]
+            K[k] = -np.array(y)
+            Pn = (np.diag(np.asarray(q, float)) + M[:nx, :nx]) + H.T @ K[k]
+            P = 0.5 * (Pn + Pn.T)
+    if not ok:
+        K[:] = np.nan
+    return K, P, ok
+
+
+def _weights(nx, Q, R, Qf):
+    park = nx == 4
+    q = np.asarray(TRACK_Q_PARKING if park else TRACK_Q_QUAD, float) if Q is None else np.broadcast_to(np.asarray(Q, float), (nx,)).copy()
+    nu = 2 if park else 4
+    r = np.asarray(TRACK_R_PARKING if park else TRACK_R_QUAD, float) if R is None else np.broadcast_to(np.asarray(R, float), (nu,)).copy()
+    qf = 10.0 * q if Qf is None else np.broadcast_to(np.asarray(Qf, float), (nx,)).copy()
+    return q, r, qf
+
+
+def track_gains_parking(x, u, timeScale, Ts, L, substeps=8, Q=None, R=None, Qf=None):
+    """Time-varying LQR gains about a parking trajectory x (4,N+1), u (2,N): (A (N,4,4), B (N,4,2), K (N,2,4), P_0 (4,4)).  A_k, B_k are the derivatives of the map the
+    plant applies over interval k -- `substeps` RK4 steps of the bicycle with the input held, rollout_parking's step -- at (x_k, u_k), with respect to the state and to
+    (delta, a) (the steering column carries sec^2 delta); K from the backward Riccati recursion with diagonal weights Q (4), R (2), Qf (4) (defaults TRACK_*_PARKING).
+    Convention: u = u_k + K_k (X_k - x_k).  K is NaN if a pivot of R + B'PB was not finite and positive."""
+    q, r, qf = _weights(4, Q, R, Qf)
+    AB = _linearise(_park_rhs, _park_jvp, True, x, u, timeScale, Ts, float(L), substeps)
+    K, P0, _ = _riccati(AB, 4, q, r, qf)
+    return AB[:, :, :4].copy(), AB[:, :, 4:].copy(), K, P0
+
+
+def track_gains_quad(x, u, timeScale, Ts, substeps=8, Q=None, R=None, Qf=None):
+    """The same about a quadcopter trajectory x (12,N+1), u (4,N): (A (N,12,12), B (N,12,4), K (N,4,12), P_0), defaults TRACK_*_QUAD.
+    Gains from the NLP's own node linearisation A = I + h f_x, B = h f_u (forward Euler) are NOT offered: the feedback is held over the interval, 0.5 s on the fixture of
+    make_quad_batch(4, 20), and the attitude loop those gains close is much faster than that -- held over the interval map they make the closed loop of all four fixture
+    instances leave every bound within the horizon (non-finite states), while the gains of the interval map itself track all seven fixture trajectories."""
+    q, r, qf = _weights(12, Q, R, Qf)
+    AB = _linearise(_quad_rhs, _quad_jvp, False, x, u, timeScale, Ts, None, substeps)
+    K, P0, _ = _riccati(AB, 12, q, r, qf)
+    return AB[:, :, :12].copy(), AB[:, :, 12:].copy(), K, P0
+
+
+def _track(f, parking, x, u, timeScale, Ts, L, substeps, K, dx0, feedback, clamp, pole=None):
+    """the chain of _rollout with the input formed per interval: X_0 = x_0 + dx0, U_k = u_k + K_k (X_k - x_k) if feedback, clipped to the input box if clamp"""
+    x = np.asarray(x, float); u = np.asarray(u, float); nx, N1 = x.shape; N = N1 - 1; nu = u.shape[0]; S = int(substeps); ts = _stage_scale(timeScale, N)
+    box = _PARK_UBOX if parking else _QUAD_UBOX
+    X = np.zeros((nx, N + 1)); P = np.zeros((N * S + 1, 3)); Ua = np.zeros((nu, N)); clipped = np.zeros(N, bool)
+    cur = [float(v) for v in x[:, 0]]; bad = False
+    if dx0 is not None:
+        cur = [cur[i] + float(dx0[i]) for i in range(nx)]
+    X[:, 0] = cur
+    for k in range(N):
+        U = [float(v) for v in u[:, k]]
+        if feedback:
+            e = [cur[j] - float(x[j, k]) for j in range(nx)]
+            for a in range(nu):
+                s = 0.0
+                for j in range(nx):
+                    s = s + float(K[k, a, j]) * e[j]
+                U[a] = U[a] + s
+        if clamp:
+            for a in range(nu):
+                c = box[a][0] if U[a] < box[a][0] else (box[a][1] if U[a] > box[a][1] else U[a])
+                clipped[k] |= c != U[a]
+                U[a] = c
+        Ua[:, k] = U
+        h = float(ts[k]) * float(Ts) / S
+        try:
+            if parking:
+                U = [math.tan(U[0]), U[1]]
+        except (OverflowError, ValueError):
+            U = [math.nan, U[1]]
+        for s_ in range(S):
+            P[k * S + s_] = cur[:3]
+            try:
+                new = _rk4(f, cur, U, h, L)
+                if pole is not None and math.cos(cur[pole]) * math.cos(new[pole]) <= 0.0:
+                    bad = True
+            except (OverflowError, ValueError, ZeroDivisionError):
+                new = [math.nan] * nx
+            cur = new
+        X[:, k + 1] = cur
+    P[N * S] = cur[:3]
+    if bad or not np.isfinite(X).all():
+        X[:] = np.nan
+    return X, P, Ua, clipped
+
+
+def _track_model(parking, x, u, timeScale, Ts, L, substeps, dx0, Q, R, Qf, feedback, clamp):
+    x = np.asarray(x, float); u = np.asarray(u, float); nx = x.shape[0]
+    q, r, qf = _weights(nx, Q, R, Qf)
+    AB = _linearise(_park_rhs if parking else _quad_rhs, _park_jvp if parking else _quad_jvp, parking, x, u, timeScale, Ts, L, substeps)
+    K, P0, ok = _riccati(AB, nx, q, r, qf)
+    ok = ok and (dx0 is None or bool(np.isfinite(np.asarray(dx0, float)).all()))
+    if ok:
+        X, P, Ua, clipped = _track(_park_rhs if parking else _quad_rhs, parking, x, u, timeScale, Ts, L, substeps, K, dx0, feedback, clamp, None if parking else 3)
+        ok = bool(np.isfinite(X).all())
+    if not ok:
+        N = u.shape[1]
+        X = np.full(x.shape, np.nan); P = np.full((N * int(substeps) + 1, 3), np.nan); Ua = np.full(u.shape, np.nan); clipped = np.zeros(N, bool); K = np.full(K.shape, np.nan)
+    return X, P, dict(AB=AB, K=K, P0=P0, U=Ua, clipped=clipped, feedback=bool(feedback), clamp=bool(clamp), dx0=None if dx0 is None else np.asarray(dx0, float), finite=ok)
+
+
+def track_parking(x, u, timeScale, Ts, L, substeps=8, dx0=None, Q=None, R=None, Qf=None, feedback=True, clamp=True):
+    """A parking trajectory tracked on the continuous bicycle by the held TVLQR feedback of track_gains_parking: X_0 = x[:, 0] + dx0, per interval
+    U_k = u_k + K_k (X_k - x_k) (feedback), clipped to |delta| <= 0.6, |a| <= 0.4 (clamp), X_{k+1} = `substeps` RK4 steps from X_k with U_k held.  The feedback is
+    evaluated at the nodes and held; state differences are raw, no angle is wrapped.  Returns (X (4,N+1), samples (N S + 1, 3) as rollout_parking, info): info has AB
+    (N,4,6), K, P0, U (2,N) the applied inputs, clipped (N,) bool, feedback, clamp, dx0, finite.  Not finite (a number that is not finite, a bad pivot): X, samples, U, K NaN."""
+    return _track_model(True, x, u, timeScale, Ts, float(L), substeps, dx0, Q, R, Qf, feedback, clamp)
+
+
+def track_quad(x, u, timeScale, Ts, substeps=8, dx0=None, Q=None, R=None, Qf=None, feedback=True, clamp=True):
+    """The same for a quadcopter trajectory on the rigid body of rollout_quad, rotor speeds clipped to 1.2 .. 7.8.  A step across cos x[3] = 0 counts as not finite."""
+    return _track_model(False, x, u, timeScale, Ts, None, substeps, dx0, Q, R, Qf, feedback, clamp)
+
+
+def track_record(x, u, X, c, substeps, need, info):
+    """the TRK_OUT doubles of a tracked trajectory: [0..39] rollout_record of the chain (x the trajectory, X the tracked node states, c (N S + 1, nOb) the clearances of the
+    samples), [40] feedback, [41] clamp, [42] the number of intervals in which an input was clipped, [43] the largest |U_k - u_k| over inputs and intervals, [44] its interval
+    (ties: the smallest), [45] |dx0| of the position part, [46], [47] 0.  Not finite: [42] = [44] = -1, [43] = [45] = NaN."""
+    x = np.asarray(x, float); u = np.asarray(u, float); nx = x.shape[0]
+    r = np.zeros(TRK_OUT); r[40] = int(info["feedback"]); r[41] = int(info["clamp"])
+    finite = bool(info["finite"] and np.isfinite(np.asarray(c, float)).all())
+    r[:ROLL_OUT] = rollout_record(x, X, c, substeps, False, need, finite)
+    if not finite:
+        r[42] = r[44] = -1; r[43] = r[45] = np.nan
+        return r
+    d = np.abs(info["U"] - u).max(axis=0)
+    r[42] = int(info["clipped"].sum()); r[43] = d.max(); r[44] = int(np.argmax(d))
+    if info["dx0"] is not None:
+        p = info["dx0"][:2 if nx == 4 else 3]
+        r[45] = np.sqrt(p[0] * p[0] + p[1] * p[1]) if nx == 4 else np.sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2])
     return r
