@@ -22,7 +22,7 @@ import numpy as np
 from . import buildflags, cabi, planner
 from .cabi import Opts      # `typedef struct obca_opts` of include/obca_hip.h, read from the header
 from .validate import (VIOL_NAMES, QUAD_VIOL_NAMES, DMIN, CLR_OUT, ROLL_OUT, TRK_OUT, TRACK_Q_PARKING, TRACK_R_PARKING, TRACK_QF_PARKING, TRACK_Q_QUAD, TRACK_R_QUAD,
-                       TRACK_QF_QUAD)
+                       TRACK_QF_QUAD, ENS_MEM, ENS_OUT, ENS_MMAX)
 
 _LIBPATH = os.environ.get("OBCA_HIP_LIBRARY") or buildflags.PIECES["hip"].out   # override: diagnostic builds
 _lib = None
@@ -64,6 +64,7 @@ def _load():
     cabi.bind(_lib, "obca_quad_plan_resident.h")          # the quadcopter's grid planner from the records of an uploaded batch
     cabi.bind(_lib, "obca_rollout.h")                     # solved batches applied to the continuous vehicle models
     cabi.bind(_lib, "obca_track.h")                       # ... and tracked on them by a time-varying LQR
+    cabi.bind(_lib, "obca_ensemble.h")                    # ... from a spread of start offsets and input biases at once
     return _lib
 
 
@@ -110,6 +111,10 @@ ROLLOUT_EXPORTS = ["obca_batch_rollout", "obca_batch_rollout_ms", "obca_batch_ro
 # track_gains, track_ms, parking_track_batch, quadcopter_track_batch)
 TRACK_EXPORTS = ["obca_batch_track", "obca_batch_track_ms", "obca_batch_track_states", "obca_batch_track_gains", "obca_parking_track_batch", "obca_quad_batch_track",
                  "obca_quad_batch_track_ms", "obca_quad_batch_track_states", "obca_quad_batch_track_gains", "obca_quadcopter_track_batch"]
+# include/obca_ensemble.h: up to 64 disturbed closed loops about every solution or trajectory at once, one member per lane (Batch.ensemble, QuadBatch.ensemble,
+# ensemble_members, ensemble_final, ensemble_ms, parking_ensemble_batch, quadcopter_ensemble_batch)
+ENSEMBLE_EXPORTS = ["obca_batch_ensemble", "obca_batch_ensemble_ms", "obca_batch_ensemble_members", "obca_batch_ensemble_final", "obca_parking_ensemble_batch",
+                    "obca_quad_batch_ensemble", "obca_quad_batch_ensemble_ms", "obca_quad_batch_ensemble_members", "obca_quad_batch_ensemble_final", "obca_quadcopter_ensemble_batch"]
 QUAD_PLAN_STATUS = {0: "no path", -1: "more way-points than cap", -2: "the start or goal point is blocked, or a coordinate of the record is not finite",
                     -3: "the relaxation hit its sweep bound", -4: "not selected"}
 QUAD_REFINE_STATUS = {0: "refined from the solution", 1: "interpolated from the uploaded warm start (the last solve failed, or its iterate is not finite)",
@@ -257,6 +262,41 @@ def _track(B, substeps, nOb, call):
     call(rec)
     return dict(_rollout_dict(rec[:, :ROLL_OUT], substeps, nOb), saturated=rec[:, 42].astype(np.int64), du_max=rec[:, 43], du_node=rec[:, 44].astype(np.int64), dx0_pos=rec[:, 45],
                 feedback=rec[:, 40] != 0, clamp=rec[:, 41] != 0)
+
+
+def _ensemble(B, call):
+    """the records of an ensemble entry point, `call(out)` with out (B, ENS_OUT), and the dict they are returned in: finite (B,) bool -- False: what track() marks for the
+    whole instance, every member is bad and the values are NaN / -1 --; members, substeps, feedback, clamp as the call had them; members_bad, members_hit (good members
+    with a sample whose clearance is < need), members_sat (good members with a clipped interval); min the smallest clearance over the good members, min_member,
+    min_sample, min_obstacle where; dev_pos the largest position deviation from the nominal nodes 1..N, dev_pos_member, dev_node; end_pos the largest at node N,
+    end_pos_member; dev_att, dev_vel, dev_rate; du_max the largest |U_k - u_k|, du_member, du_node; end_pos_mean and min_mean over the good members; below the samples
+    under need, summed over the good members.  Ties go to the smaller member."""
+    rec = np.zeros((B, ENS_OUT))
+    call(rec)
+    i = lambda c: rec[:, c].astype(np.int64)      # noqa: E731
+    return dict(finite=rec[:, 0] == 0, members=i(1), substeps=i(2), feedback=rec[:, 3] != 0, clamp=rec[:, 4] != 0, members_bad=i(5), members_hit=i(6), members_sat=i(7),
+                min=rec[:, 8], min_member=i(9), min_sample=i(10), min_obstacle=i(11), dev_pos=rec[:, 12], dev_pos_member=i(13), dev_node=i(14), end_pos=rec[:, 15],
+                end_pos_member=i(16), dev_att=rec[:, 17], dev_vel=rec[:, 18], dev_rate=rec[:, 19], du_max=rec[:, 20], du_member=i(21), du_node=i(22), end_pos_mean=rec[:, 23],
+                min_mean=rec[:, 24], below=i(25))
+
+
+def _ensemble_rows(a, B, M, n, what):
+    """None, (M, n) for every instance or (B, M, n): the ABI's n x M x B, each member's n contiguous"""
+    if a is None:
+        return None
+    a = np.asarray(a, float)
+    if a.shape not in ((M, n), (B, M, n)):
+        raise ObcaError(f"{what} must be ({M},{n}) or ({B},{M},{n}); got {a.shape}")
+    return _in(np.broadcast_to(a, (B, M, n)))
+
+
+def ensemble_offsets(B, M, sigma, seed=0):
+    """(B, M, len(sigma)) rows drawn from N(0, diag(sigma^2)) with numpy's default_rng(seed) -- there is no random number generator on the device --, member 0 exactly
+    zero: member 0 of an ensemble() is then the nominal closed loop.  For the dx0 (sigma of length nx) or the dub (length nu) of ensemble()."""
+    sigma = np.atleast_1d(np.asarray(sigma, float))
+    d = np.random.default_rng(seed).standard_normal((int(B), int(M), sigma.size)) * sigma
+    d[:, 0] = 0.0
+    return d
 
 
 def _track_weights(nx, nu, Q, R, Qf, defaults):
@@ -488,6 +528,32 @@ class _DeviceBatch(_Handle):
         """HIP-event duration of the last track kernel"""
         return self._floats("track_ms")
 
+    def _ensemble(self, defaults, members, substeps, dx0, dub, Q, R, Qf, feedback, clamp, need):
+        q, r, qf = _track_weights(self._nx, self._nu, Q, R, Qf, defaults); M = int(members)
+        if not 1 <= M <= ENS_MMAX:
+            raise ObcaError(f"need 1 <= members <= {ENS_MMAX}")
+        d0 = _ensemble_rows(dx0, self.B, M, self._nx, "dx0"); db = _ensemble_rows(dub, self.B, M, self._nu, "dub")
+        r_ = _ensemble(self.B, lambda out: self._call("ensemble", int(substeps), M, int(feedback), int(clamp), q, r, qf, d0, db, float(need), out))
+        self._ens_members = M
+        return r_
+
+    def ensemble_members(self):
+        """The member records of the last ensemble(), fetched from the device: (B, M, 16) -- bad, dev_pos, its node, end_pos, dev_att, dev_vel, dev_rate, min clearance,
+        its sample, its obstacle, below, saturated intervals, du_max, its interval, |dx0| of the position part, 0; a bad member's real fields are NaN, its indices -1."""
+        mem = np.zeros((self.B, getattr(self, "_ens_members", 1), ENS_MEM))
+        self._call("ensemble_members", mem)
+        return mem
+
+    def ensemble_final(self):
+        """The final states X_N of the members of the last ensemble(), fetched from the device: (B, M, nx); NaN for a bad member."""
+        fin = np.zeros((self.B, getattr(self, "_ens_members", 1), self._nx))
+        self._call("ensemble_final", fin)
+        return fin
+
+    def ensemble_ms(self):
+        """HIP-event duration of the last ensemble kernel"""
+        return self._floats("ensemble_ms")
+
     def _refine_into(self, entry, limit, extra, select, factor, into):
         """What Batch.refine and QuadBatch.refine share: the selection (None: all) checked against the batch, the factor against `limit`, the destination (`into`, or a new
         batch of this kind, closed again if the call fails) and the call of `entry` with its one own argument `extra`.  Returns (destination, selection, status)."""
@@ -625,6 +691,16 @@ class Batch(_DeviceBatch):
         gains stay on the device: track_states(), track_gains()."""
         return self._track(int(self.nObs.max()), (TRACK_Q_PARKING, TRACK_R_PARKING, TRACK_QF_PARKING), substeps, dx0, Q, R, Qf, feedback, clamp, need)
 
+    def ensemble(self, members=64, substeps=8, dx0=None, dub=None, Q=None, R=None, Qf=None, feedback=True, clamp=True, need=DMIN):
+        """`members` (1 .. 64) disturbed closed loops about the last solution at once, ON THE DEVICE (obca_batch_ensemble; the numpy statement is
+        obca_amd.validate.ensemble_parking + ensemble_record): the gains of track() -- computed once per instance --, member m started at the solution's first state +
+        dx0[m] (dx0 (M,4) for every instance or (B,M,4); None: zeros) and driven by clip(u_k + K_k (X_k - x_k) + dub[m]) (dub (M,2) or (B,M,2), a constant actuator bias
+        per member; None: zeros).  One member per lane of the instance's wavefront: 64 members cost one launch, where 64 track() calls recompute the same gains 64 times
+        with 63 lanes idle.  Every sample a member passes is measured against the obstacles as rollout() measures it.  Returns the dict of _ensemble: over the members of an
+        instance, how far the vehicle strays and how close it comes -- the distribution a refine(margin=...) is chosen from.  ensemble_offsets() draws dx0 / dub.  Member
+        records and final states stay on the device: ensemble_members(), ensemble_final()."""
+        return self._ensemble((TRACK_Q_PARKING, TRACK_R_PARKING, TRACK_QF_PARKING), members, substeps, dx0, dub, Q, R, Qf, feedback, clamp, need)
+
     def clearance(self, substeps=8, need=DMIN):
         """Clearance of the last solution BETWEEN its nodes, ON THE DEVICE (obca_batch_clearance; the numpy statement is obca_amd.validate.parking_samples + a DualMultWS
         distance per pose): every interval is sampled `substeps` times with the discretisation's own partial step and the car's distance to every obstacle computed anew,
@@ -687,6 +763,31 @@ def parking_track_batch(N, Ts, L, ego, vOb, A, b, x, u, timeScale=None, substeps
     X = np.zeros((B, N + 1, 4)) if states else None; K = np.zeros((B, N, 2, 4)) if gains else None
     t = _track(B, substeps, int(nObs.max()), lambda out: ctx._check(_load().obca_parking_track_batch(ctx._h, B, N, *ins, out, X, K), "obca_parking_track_batch"))
     return dict(t, **({"states": X} if states else {}), **({"gains": K} if gains else {}))
+
+
+def _ensemble_host(B, M, nx, call, members, final):
+    """what the two host-pointer ensemble calls share: the outputs, `call(out, mem, fin)`, and the dict"""
+    mem = np.zeros((B, M, ENS_MEM)) if members else None; fin = np.zeros((B, M, nx)) if final else None
+    r = _ensemble(B, lambda out: call(out, mem, fin))
+    return dict(r, **({"member_records": mem} if members else {}), **({"final": fin} if final else {}))
+
+
+def parking_ensemble_batch(N, Ts, L, ego, vOb, A, b, x, u, timeScale=None, members=64, substeps=8, dx0=None, dub=None, Q=None, R=None, Qf=None, feedback=True, clamp=True,
+                           need=DMIN, device=0, member_records=True, final=True):
+    """Batch.ensemble for arbitrary trajectories (obca_parking_ensemble_batch): the arguments of parking_track_batch up to timeScale, then those of Batch.ensemble.  Returns
+    the dict of Batch.ensemble, with `member_records` (B, M, 16) and `final` (B, M, 4) unless switched off."""
+    x = np.asarray(x, float); u = np.asarray(u, float); N = int(N); B = x.shape[0]; M = int(members)
+    if x.shape != (B, 4, N + 1) or u.shape != (B, 2, N):
+        raise ObcaError(f"x must be (B,4,N+1) and u (B,2,N); got {x.shape}, {u.shape}")
+    ctx = _ctx(device)
+    nObs, vflat, Aflat, bflat = _norm_obstacles(B, vOb, A, b)
+    q, r, qf = _track_weights(4, 2, Q, R, Qf, (TRACK_Q_PARKING, TRACK_R_PARKING, TRACK_QF_PARKING))
+    Mc = min(max(M, 1), ENS_MMAX)      # (a count the library refuses still needs arrays of some shape)
+    ins = (_per_instance(Ts, B), L, _in(ego), _in(nObs, np.int32), _in(vflat, np.int32), _in(Aflat), _in(bflat), _in(np.transpose(x, (0, 2, 1))), _in(np.transpose(u, (0, 2, 1))),
+           None if timeScale is None else _time_scale(timeScale, B, N + 1), int(substeps), M, int(feedback), int(clamp), q, r, qf, _ensemble_rows(dx0, B, Mc, 4, "dx0"),
+           _ensemble_rows(dub, B, Mc, 2, "dub"), float(need))
+    return _ensemble_host(B, Mc, 4, lambda out, mem, fin: ctx._check(_load().obca_parking_ensemble_batch(ctx._h, B, N, *ins, out, mem, fin), "obca_parking_ensemble_batch"),
+                          member_records, final)
 
 
 def _context_ms(entry, device):
@@ -1002,6 +1103,11 @@ class QuadBatch(_DeviceBatch):
         one: what remains is of the size of one interval's defect (rollout(restart=True)).  Returns the dict of Batch.track, 5 obstacles."""
         return self._track(5, (TRACK_Q_QUAD, TRACK_R_QUAD, TRACK_QF_QUAD), substeps, dx0, Q, R, Qf, feedback, clamp, need)
 
+    def ensemble(self, members=64, substeps=8, dx0=None, dub=None, Q=None, R=None, Qf=None, feedback=True, clamp=True, need=0.0):
+        """`members` disturbed closed loops about the last solution at once, on the device (obca_quad_batch_ensemble; numpy: obca_amd.validate.ensemble_quad +
+        ensemble_record): Batch.ensemble with dx0 (M,12) or (B,M,12), dub (M,4) or (B,M,4) rotor-speed biases, the weights of QuadBatch.track."""
+        return self._ensemble((TRACK_Q_QUAD, TRACK_R_QUAD, TRACK_QF_QUAD), members, substeps, dx0, dub, Q, R, Qf, feedback, clamp, need)
+
     def clearance(self, substeps=8, need=0.0):
         """Clearance of the last solution between its nodes, on the device (obca_quad_batch_clearance; numpy: obca_amd.validate.quad_clearance): the straight segment of every
         interval is sampled `substeps` times, clearance = distance of the point to a box - R (-R inside the box).  Returns the dict of Batch.clearance, 5 obstacles."""
@@ -1110,6 +1216,22 @@ def quadcopter_track_batch(x, u, timeScale, Ts, ob, R, substeps=8, dx0=None, Q=N
     X = np.zeros((B, N1, 12)) if states else None; K = np.zeros((B, N1 - 1, 4, 12)) if gains else None
     t = _track(B, substeps, 5, lambda out: ctx._check(_load().obca_quadcopter_track_batch(ctx._h, B, N1 - 1, *ins, out, X, K), "obca_quadcopter_track_batch"))
     return dict(t, **({"states": X} if states else {}), **({"gains": K} if gains else {}))
+
+
+def quadcopter_ensemble_batch(x, u, timeScale, Ts, ob, R, members=64, substeps=8, dx0=None, dub=None, Q=None, R_=None, Qf=None, feedback=True, clamp=True, need=0.0, device=0,
+                              member_records=True, final=True):
+    """QuadBatch.ensemble for arbitrary trajectories (obca_quadcopter_ensemble_batch): the arguments of quadcopter_track_batch up to timeScale (R: the vehicle's radius), then
+    those of QuadBatch.ensemble with the input weights as R_.  Returns the dict of QuadBatch.ensemble, with `member_records` (B, M, 16) and `final` (B, M, 12) unless switched off."""
+    x = np.asarray(x, float); u = np.asarray(u, float); B, _, N1 = x.shape; M = int(members)
+    if x.shape != (B, 12, N1) or u.shape != (B, 4, N1 - 1):
+        raise ObcaError(f"x must be (B,12,N+1) and u (B,4,N); got {x.shape}, {u.shape}")
+    ctx = _ctx(device)
+    q, r, qf = _track_weights(12, 4, Q, R_, Qf, (TRACK_Q_QUAD, TRACK_R_QUAD, TRACK_QF_QUAD))
+    Mc = min(max(M, 1), ENS_MMAX)
+    ins = (_per_instance(Ts, B), R, _boxes(ob, B), _in(np.transpose(x, (0, 2, 1))), _in(np.transpose(u, (0, 2, 1))), _time_scale(1.0 if timeScale is None else timeScale, B, N1),
+           int(substeps), M, int(feedback), int(clamp), q, r, qf, _ensemble_rows(dx0, B, Mc, 12, "dx0"), _ensemble_rows(dub, B, Mc, 4, "dub"), float(need))
+    return _ensemble_host(B, Mc, 12, lambda out, mem, fin: ctx._check(_load().obca_quadcopter_ensemble_batch(ctx._h, B, N1 - 1, *ins, out, mem, fin), "obca_quadcopter_ensemble_batch"),
+                          member_records, final)
 
 
 def constrSatisfaction(x, u, timeScale, x0, xF, Ts, lam, ob1, ob2, ob3, ob4, ob5, R, device=0):

@@ -9,6 +9,7 @@
 //   obca_clearance_*_kernel : one wavefront per instance, the clearance of a solution or of a caller's trajectory between its nodes (obca_clearance.h).
 //   obca_rollout_*_kernel   : one wavefront per instance, a solution or a caller's trajectory applied to the continuous vehicle model: deviations, clearance of the rolled samples (obca_rollout.h).
 //   obca_track_*_kernel     : one wavefront per instance, TVLQR gains about a solution or a caller's trajectory and the closed loop rolled on the continuous model (obca_track.h).
+//   obca_ensemble_*_kernel  : one wavefront per instance, one member per lane: up to 64 disturbed closed loops about a solution or a caller's trajectory, the gains computed once (obca_ensemble.h).
 //   obca_refine_*_kernel    : one wavefront per destination instance, a solved parking instance on a finer horizon (obca_refine.h): into a second resident batch or host-bound arrays.
 //   obca_quad_subdivide_*_kernel : the same for a solved quadcopter instance (obca_quad_subdivide.h): it rewrites a problem record.
 //   obca_path_ws_*_kernel   : one wavefront per instance, the parking warm start from a planner path (obca_path_ws.h): into host-bound arrays or into a resident batch.
@@ -43,6 +44,7 @@
 #include "obca_quad_subdivide.h"
 #include "obca_rollout.h"
 #include "obca_track.h"
+#include "obca_ensemble.h"
 #include "../../include/obca_hip.h"
 #include "../../include/obca_path_ws.h"
 #include "../../include/obca_clearance.h"
@@ -50,6 +52,7 @@
 #include "../../include/obca_quad_subdivide.h"
 #include "../../include/obca_rollout.h"
 #include "../../include/obca_track.h"
+#include "../../include/obca_ensemble.h"
 
 using namespace obca;
 #ifdef OBCA_POISON
@@ -370,6 +373,31 @@ __global__ __launch_bounds__(QNT) void obca_track_quad_kernel(int B, int N, cons
                              K + (size_t)inst * s_K, out + (size_t)inst * TK_OUT);
 }
 
+// closed-loop ensemble (obca_ensemble.h): one wavefront per instance, one member per lane; the arguments of the track kernels with the number of members M; `aux` (s_aux
+// doubles per instance) holds [ dx0 nx x M | dub nu x M | what a host-pointer call adds ]; AB and K as the track kernels take them, then the member records (M x EN_MEM per
+// instance) and the final states (M x nx)
+template <int VM>
+__global__ __launch_bounds__(OB_NT) void obca_ensemble_parking_kernel(int B, int N, const double *prob, size_t s_prob, const double *z, size_t s_z, const double *aux, size_t s_aux, int has_ts,
+                                                                      int S, int M, int feedback, int clamp, trk::Weights w, double need, double *AB, size_t s_AB, double *K, size_t s_K,
+                                                                      double *mem, double *fin, double *out) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    const double *a = aux + (size_t)inst * s_aux;
+    ens::ensemble_parking_instance<VM>(N, prob + (size_t)inst * s_prob, z + (size_t)inst * s_z, has_ts ? a + 6 * M : nullptr, S, M, feedback, clamp, w, a, a + 4 * M, need, 0,
+                                       AB + (size_t)inst * s_AB, K + (size_t)inst * s_K, mem + (size_t)inst * ens::ensemble_mem_len(M), fin + (size_t)inst * ens::ensemble_fin_len(M, 4),
+                                       out + (size_t)inst * EN_OUT);
+}
+__global__ __launch_bounds__(QNT) void obca_ensemble_quad_kernel(int B, int N, const double *prob, size_t s_prob, const double *x, size_t s_x, const double *u, size_t s_u, const double *ts, size_t s_ts,
+                                                                 int tstride, const double *aux, size_t s_aux, int S, int M, int feedback, int clamp, trk::Weights w, double need,
+                                                                 double *AB, size_t s_AB, double *K, size_t s_K, double *mem, double *fin, double *out) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    const double *a = aux + (size_t)inst * s_aux;
+    ens::ensemble_quad_instance(N, prob + (size_t)inst * s_prob, x + (size_t)inst * s_x, u + (size_t)inst * s_u, ts + (size_t)inst * s_ts, tstride, S, M, feedback, clamp, w, a, a + QX * M,
+                                need, 0, AB + (size_t)inst * s_AB, K + (size_t)inst * s_K, mem + (size_t)inst * ens::ensemble_mem_len(M), fin + (size_t)inst * ens::ensemble_fin_len(M, QX),
+                                out + (size_t)inst * EN_OUT);
+}
+
 // warm starts from planner paths (obca_path_ws.h): one wavefront per instance.  paths / dirs: B x rows (x 3) dense on the device -- the rows below the longest count of the
 // call --, `cap` the rows of the caller's arrays (what a count is checked against).  Host-pointer call: outputs per instance, zeros where the status is negative.
 __global__ __launch_bounds__(OB_NT) void obca_path_ws_host_kernel(int B, int N, const double *paths, const int *dirs, const int *counts, int rows, int cap, const double *xF /* 4 x B or NULL */,
@@ -572,6 +600,9 @@ struct BatchCore {
     ValBufs trk;                                            // ... and for the track calls (obca_track.h), with a work buffer of their own: a rollout's node states stay valid
     DevBuf trk_w, trk_K;                                    // [ [A|B] N nx (nx + nu) + applied inputs N nu | sample poses | node states ] x B; the gains N nu nx x B
     int trk_B = 0, trk_N = 0, trk_S = 0;                    // as rol_B, rol_N, rol_S
+    ValBufs ens;                                            // ... and for the ensemble calls (obca_ensemble.h), again with buffers of their own
+    DevBuf ens_w, ens_K, ens_mem, ens_fin;                  // [A|B] N nx (nx + nu) x B; the gains; the member records M x EN_MEM x B; the final states M x nx x B
+    int ens_B = 0, ens_N = 0, ens_M = 0;                    // the instances, horizon and members of the last ensemble call (0: none yet)
     BatchCore(obca_ctx *c, int dev, hipStream_t s, int B_, int N_) : ctx(c), device(dev), stream(s), B(B_), cap(B_), N(N_) {}
 };
 struct obca_quad_batch : BatchCore {
@@ -634,7 +665,8 @@ static int core_phase_cycles(BatchCore *bt, const double *prof, double *out /* B
 // everything of the core that a batch's destroy releases, except `stage` (it goes with the family's device buffers); the batch's device is selected
 static void core_release(BatchCore *bt) {
     bt->rol_w.release(); bt->trk_w.release(); bt->trk_K.release();
-    for (ValBufs *pv : {&bt->val, &bt->clr, &bt->rol, &bt->trk}) {
+    bt->ens_w.release(); bt->ens_K.release(); bt->ens_mem.release(); bt->ens_fin.release();
+    for (ValBufs *pv : {&bt->val, &bt->clr, &bt->rol, &bt->trk, &bt->ens}) {
         ValBufs &v = *pv;
         v.d_in.release(); v.d_out.release(); v.h_in.release(); v.h_out.release(); v.ev.release();
     }
@@ -1172,6 +1204,67 @@ static int batch_track_range(obca_batch *bt, bool host, const double *ts, int S,
     return track_finish(bt, rc, d, S, lo, X, K);
 }
 
+// What the two ensemble routes share (obca_ensemble.h), as the track routes': the buffers for B instances of M members before the kernel; after it the bookkeeping of the
+// *_members / *_final calls and, for a host-pointer call, the chunk's member records and final states into the caller's mem and fin.
+struct EnsDims { int nx, nu, M; size_t ab, gain, mem, fin; };
+static EnsDims ensemble_dims(const BatchCore *bt, int nx, int nu, int M) {
+    return {nx, nu, M, ens::ensemble_ab_len(bt->N, nx, nu), trk::track_gain_len(bt->N, nx, nu), ens::ensemble_mem_len(M), ens::ensemble_fin_len(M, nx)};
+}
+static int ensemble_reserve(BatchCore *bt, const EnsDims &d) {
+    use_device(bt->device);
+    if (bt->ens_w.reserve((size_t)bt->B * d.ab, bt->stream) != hipSuccess || bt->ens_K.reserve((size_t)bt->B * d.gain, bt->stream) != hipSuccess ||
+        bt->ens_mem.reserve((size_t)bt->B * d.mem, bt->stream) != hipSuccess || bt->ens_fin.reserve((size_t)bt->B * d.fin, bt->stream) != hipSuccess) {
+        bt->err = "hipMalloc(ensemble work buffer) failed"; return -2;
+    }
+    return 0;
+}
+// per instance [ dx0 nx x M | dub nu x M ] of a call's arrays (nullptr: zeros), instance g of the call
+static void ensemble_pack(const EnsDims &d, const double *dx0, const double *dub, size_t g, double *a) {
+    const size_t nd = (size_t)d.nx * d.M, nb = (size_t)d.nu * d.M;
+    if (dx0) memcpy(a, dx0 + g * nd, sizeof(double) * nd); else memset(a, 0, sizeof(double) * nd);
+    if (dub) memcpy(a + nd, dub + g * nb, sizeof(double) * nb); else memset(a + nd, 0, sizeof(double) * nb);
+}
+static int ensemble_finish(BatchCore *bt, int rc, const EnsDims &d, int lo, double *mem, double *fin) {
+    bt->ens_B = bt->ens_N = bt->ens_M = 0;
+    if (rc) return rc;
+    bt->ens_B = bt->B; bt->ens_N = bt->N; bt->ens_M = d.M;
+    if (mem) HIPCHK(bt, hipMemcpy(mem + (size_t)lo * d.mem, (const double *)bt->ens_mem, (size_t)bt->B * d.mem * sizeof(double), hipMemcpyDeviceToHost));      // (run_validate has synchronised the stream)
+    if (fin) HIPCHK(bt, hipMemcpy(fin + (size_t)lo * d.fin, (const double *)bt->ens_fin, (size_t)bt->B * d.fin * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+static int ensemble_fetch(BatchCore *bt, int nx, bool final_states, double *dst, const char *entry) {
+    if (!dst) { bt->ctx->err = std::string(entry) + ": NULL argument"; return -1; }
+    if (!bt->ens_B || bt->ens_B != bt->B || bt->ens_N != bt->N) { bt->ctx->err = std::string(entry) + ": no ensemble call has run on this batch since it was last filled"; return -1; }
+    const size_t n = (size_t)bt->B * (final_states ? ens::ensemble_fin_len(bt->ens_M, nx) : ens::ensemble_mem_len(bt->ens_M));
+    use_device(bt->device);
+    if (hipStreamSynchronize(bt->stream) != hipSuccess ||
+        hipMemcpy(dst, final_states ? (const double *)bt->ens_fin : (const double *)bt->ens_mem, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+        bt->ctx->err = std::string(entry) + ": D2H failed"; return -2;
+    }
+    return 0;
+}
+// The ensemble about the batch's parking instances: the arguments of batch_track_range with the members, dx0 (4 x M per instance of the call, or nullptr) and dub (2 x M);
+// per instance [ dx0 4 M | dub 2 M | timeScale N + 1 (host-pointer calls) ] travels up
+static int batch_ensemble_range(obca_batch *bt, bool host, const double *ts, int S, int M, int feedback, int clamp, const trk::Weights &w, const double *dx0, const double *dub, double need, int lo,
+                                double *out, double *mem, double *fin) {
+    const int B = bt->B, N = bt->N, N1 = N + 1;
+    const EnsDims d = ensemble_dims(bt, 4, 2, M);
+    if (int rc = ensemble_reserve(bt, d)) return rc;
+    const size_t W = (size_t)6 * M + (ts ? (size_t)N1 : 0);
+    const int rc = run_validate(bt, bt->ens, W, true, EN_OUT, [&](int i, double *a) {
+        ensemble_pack(d, dx0, dub, (size_t)lo + i, a);
+        if (ts) memcpy(a + 6 * M, ts + ((size_t)lo + i) * N1, sizeof(double) * N1);
+    }, [&] {
+        const double *z = host ? bt->d.z0 : bt->d.z;
+#define ENS_LAUNCH(VM) hipLaunchKernelGGL(obca_ensemble_parking_kernel<VM>, dim3(B), dim3(OB_NT), 0, bt->stream, B, N, (const double *)bt->d.prob, bt->d.s_prob, z, bt->d.s_z, (const double *)bt->ens.d_in, W, \
+                                          ts ? 1 : 0, S, M, feedback, clamp, w, need, (double *)bt->ens_w, d.ab, (double *)bt->ens_K, d.gain, (double *)bt->ens_mem, (double *)bt->ens_fin, \
+                                          (double *)bt->ens.d_out)
+        if (bt->vmax <= 2) ENS_LAUNCH(2); else if (bt->vmax <= OB_VMID) ENS_LAUNCH(OB_VMID); else ENS_LAUNCH(OB_VMAX);      // (the row class of launch_dualws)
+#undef ENS_LAUNCH
+    }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * EN_OUT, o, sizeof(double) * EN_OUT); });
+    return ensemble_finish(bt, rc, d, lo, mem, fin);
+}
+
 // ---- chunked execution of a host-pointer call over the slots of the context (work queue)
 template <typename F>
 static int run_chunks(obca_ctx *ctx, int B, int chunk, F &&fn /* int(Slot &, int lo, int n, std::string &err) */) {
@@ -1418,6 +1511,33 @@ int obca_parking_track_batch(obca_ctx *ctx, int B, int N, const double *Ts, doub
     if (int rc = park_prefix(ctx->err, B, nOb, vOb, in)) return rc;
     const trk::Weights w = trk::make_weights(q, r, qf, 4, 2);
     return parking_chunks(ctx, 0, B, N, in, [&](obca_batch *bt, int lo) { return batch_track_range(bt, true, timeScale, substeps, feedback, clamp, w, dx0, need, lo, out, X, K); });
+}
+
+int obca_batch_ensemble(obca_batch *bt, int substeps, int members, int feedback, int clamp, const double q[4], const double r[2], const double qf[4], const double *dx0, const double *dub, double need,
+                        double *out) {
+    if (!bt) return -1;
+    if (!out) { bt->ctx->err = "obca_batch_ensemble: NULL argument"; return -1; }
+    if (const char *bad = ens::ensemble_check_args(substeps, members, feedback, clamp, q, r, qf, 4, 2, need)) { bt->ctx->err = std::string("obca_batch_ensemble: ") + bad; return -1; }
+    if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_batch_ensemble: nothing has been solved since the last upload or shift"; return -1; }
+    if (bt->N < 1) { bt->ctx->err = "obca_batch_ensemble: needs a horizon N>=1"; return -1; }
+    return fin(bt, batch_ensemble_range(bt, false, nullptr, substeps, members, feedback, clamp, trk::make_weights(q, r, qf, 4, 2), dx0, dub, need, 0, out, nullptr, nullptr));
+}
+int obca_batch_ensemble_ms(obca_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->ens.ev, ms, "obca_batch_ensemble_ms: no ensemble call has run on this batch") : -1; }
+int obca_batch_ensemble_members(obca_batch *bt, double *mem) { return bt ? ensemble_fetch(bt, 4, false, mem, "obca_batch_ensemble_members") : -1; }
+int obca_batch_ensemble_final(obca_batch *bt, double *fin) { return bt ? ensemble_fetch(bt, 4, true, fin, "obca_batch_ensemble_final") : -1; }
+int obca_parking_ensemble_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const int *nOb, const int *vOb, const double *A, const double *b,
+                                const double *x, const double *u, const double *timeScale, int substeps, int members, int feedback, int clamp, const double q[4], const double r[2], const double qf[4],
+                                const double *dx0, const double *dub, double need, double *out, double *mem, double *fin) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 1 || N > OBCA_NMAX) { ctx->err = "obca_parking_ensemble_batch: need B>=1, 1<=N<=OBCA_NMAX"; return -1; }
+    if (!Ts || !ego || !nOb || !vOb || !A || !b || !x || !u || !out) { ctx->err = "obca_parking_ensemble_batch: NULL argument"; return -1; }
+    if (const char *bad = ens::ensemble_check_args(substeps, members, feedback, clamp, q, r, qf, 4, 2, need)) { ctx->err = std::string("obca_parking_ensemble_batch: ") + bad; return -1; }
+    const std::vector<double> zero((size_t)B * (N + 1), 0.0);      // the tracking reference of a solve: the call does not read it (nor the bounds, the start and the goal)
+    const double XYb[4] = {0, 0, 0, 0};
+    ParkIn in = {Ts, L, ego, XYb, 0, nullptr, nullptr, nOb, vOb, A, b, zero.data(), zero.data(), zero.data(), x, u, nullptr, nullptr, {}, {}};
+    if (int rc = park_prefix(ctx->err, B, nOb, vOb, in)) return rc;
+    const trk::Weights w = trk::make_weights(q, r, qf, 4, 2);
+    return parking_chunks(ctx, 0, B, N, in, [&](obca_batch *bt, int lo) { return batch_ensemble_range(bt, true, timeScale, substeps, members, feedback, clamp, w, dx0, dub, need, lo, out, mem, fin); });
 }
 
 int obca_parking_signed_dist_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const double XYb[4],
@@ -1825,6 +1945,28 @@ static int quad_track_range(obca_quad_batch *bt, const double *u, const double *
     }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * TK_OUT, o, sizeof(double) * TK_OUT); });
     return track_finish(bt, rc, d, S, lo, X, K);
 }
+// the ensemble about the batch's quadcopter instances (obca_ensemble.h): quad_track_range with the members, dx0 and dub; per instance
+// [ dx0 12 M | dub 4 M | timeScale (N + 1) | u 4 x N (the last two: host-pointer calls) ] travels up
+static int quad_ensemble_range(obca_quad_batch *bt, const double *u, const double *ts, int S, int M, int feedback, int clamp, const trk::Weights &w, const double *dx0, const double *dub, double need,
+                               int lo, double *out, double *mem, double *fin) {
+    const int B = bt->B, N = bt->N, N1 = N + 1; const QDevBufs &qd = bt->d;
+    quad::QLay l; quad::q_make_layout(N, l);
+    const EnsDims d = ensemble_dims(bt, QX, QU, M);
+    if (int rc = ensemble_reserve(bt, d)) return rc;
+    const size_t W0 = (size_t)(QX + QU) * M, W = W0 + (ts ? (size_t)N1 + (size_t)QU * N : 0);
+    const int rc = run_validate(bt, bt->ens, W, true, EN_OUT, [&](int i, double *a) {
+        ensemble_pack(d, dx0, dub, (size_t)lo + i, a);
+        if (ts) { memcpy(a + W0, ts + ((size_t)lo + i) * N1, sizeof(double) * N1); memcpy(a + W0 + N1, u + ((size_t)lo + i) * QU * N, sizeof(double) * QU * N); }
+    }, [&] {
+        const double *in = bt->ens.d_in;
+        if (ts) hipLaunchKernelGGL(obca_ensemble_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)qd.prob, qd.s_prob, (const double *)qd.prob + QPH_SIZE, qd.s_prob, in + W0 + N1, W, in + W0, W, 1,
+                                   in, W, S, M, feedback, clamp, w, need, (double *)bt->ens_w, d.ab, (double *)bt->ens_K, d.gain, (double *)bt->ens_mem, (double *)bt->ens_fin, (double *)bt->ens.d_out);
+        else hipLaunchKernelGGL(obca_ensemble_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)qd.prob, qd.s_prob, (const double *)qd.z + l.x, qd.s_z, (const double *)qd.z + l.u, qd.s_z,
+                                (const double *)qd.z + l.t, qd.s_z, 0, in, W, S, M, feedback, clamp, w, need, (double *)bt->ens_w, d.ab, (double *)bt->ens_K, d.gain, (double *)bt->ens_mem, (double *)bt->ens_fin,
+                                (double *)bt->ens.d_out);
+    }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * EN_OUT, o, sizeof(double) * EN_OUT); });
+    return ensemble_finish(bt, rc, d, lo, mem, fin);
+}
 // instances (one wavefront each) resident per CU, as OBCA_RESIDENT_PER_CU for the parking kernel: what pick_chunk sizes a quadcopter chunk by
 static const int QUAD_RESIDENT_PER_CU = (QNT == 64 ? 4 : 2) * OBCA_QUAD_WAVES_PER_EU;
 // parking_chunks for the quadcopter; the slot's cached batch only has to hold the chunk at hand
@@ -1955,6 +2097,29 @@ int obca_quadcopter_track_batch(obca_ctx *ctx, int B, int N, const double *Ts, d
     const QuadIn in = {Ts, R, zero.data(), zero.data(), ob, x, one.data(), 0, 0};
     const trk::Weights w = trk::make_weights(q, r, qf, QX, QU);
     return quad_chunks(ctx, B, N, in, [&](obca_quad_batch *bt, int lo) { return quad_track_range(bt, u, timeScale, substeps, feedback, clamp, w, dx0, need, lo, out, X, K); });
+}
+int obca_quad_batch_ensemble(obca_quad_batch *bt, int substeps, int members, int feedback, int clamp, const double q[12], const double r[4], const double qf[12], const double *dx0, const double *dub,
+                             double need, double *out) {
+    if (!bt) return -1;
+    if (!out) { bt->ctx->err = "obca_quad_batch_ensemble: NULL argument"; return -1; }
+    if (const char *bad = ens::ensemble_check_args(substeps, members, feedback, clamp, q, r, qf, QX, QU, need)) { bt->ctx->err = std::string("obca_quad_batch_ensemble: ") + bad; return -1; }
+    if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_quad_batch_ensemble: nothing has been solved since the last upload or shift"; return -1; }
+    return fin(bt, quad_ensemble_range(bt, nullptr, nullptr, substeps, members, feedback, clamp, trk::make_weights(q, r, qf, QX, QU), dx0, dub, need, 0, out, nullptr, nullptr));
+}
+int obca_quad_batch_ensemble_ms(obca_quad_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->ens.ev, ms, "obca_quad_batch_ensemble_ms: no ensemble call has run on this batch") : -1; }
+int obca_quad_batch_ensemble_members(obca_quad_batch *bt, double *mem) { return bt ? ensemble_fetch(bt, QX, false, mem, "obca_quad_batch_ensemble_members") : -1; }
+int obca_quad_batch_ensemble_final(obca_quad_batch *bt, double *fin) { return bt ? ensemble_fetch(bt, QX, true, fin, "obca_quad_batch_ensemble_final") : -1; }
+int obca_quadcopter_ensemble_batch(obca_ctx *ctx, int B, int N, const double *Ts, double R, const double *ob, const double *x, const double *u, const double *timeScale,
+                                   int substeps, int members, int feedback, int clamp, const double q[12], const double r[4], const double qf[12], const double *dx0, const double *dub, double need,
+                                   double *out, double *mem, double *fin) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 2 || N > OBCA_QUAD_NMAX) { ctx->err = "obca_quadcopter_ensemble_batch: need B>=1, 2<=N<=OBCA_QUAD_NMAX"; return -1; }
+    if (!Ts || !ob || !x || !u || !timeScale || !out) { ctx->err = "obca_quadcopter_ensemble_batch: NULL argument"; return -1; }
+    if (const char *bad = ens::ensemble_check_args(substeps, members, feedback, clamp, q, r, qf, QX, QU, need)) { ctx->err = std::string("obca_quadcopter_ensemble_batch: ") + bad; return -1; }
+    const std::vector<double> zero((size_t)B * QX, 0.0), one((size_t)B, 1.0);      // start, goal and timeWS of a solve: the call reads none of them
+    const QuadIn in = {Ts, R, zero.data(), zero.data(), ob, x, one.data(), 0, 0};
+    const trk::Weights w = trk::make_weights(q, r, qf, QX, QU);
+    return quad_chunks(ctx, B, N, in, [&](obca_quad_batch *bt, int lo) { return quad_ensemble_range(bt, u, timeScale, substeps, members, feedback, clamp, w, dx0, dub, need, lo, out, mem, fin); });
 }
 int obca_quad_batch_download(obca_quad_batch *bt, double *xp, double *up, double *ts, int *exitflag, double *lp, double *slp, double *info) {
     if (!bt) return -1;

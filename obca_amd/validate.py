@@ -615,3 +615,136 @@ def track_record(x, u, X, c, substeps, need, info):
         p = info["dx0"][:2 if nx == 4 else 3]
         r[45] = np.sqrt(p[0] * p[0] + p[1] * p[1]) if nx == 4 else np.sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2])
     return r
+
+
+# ---------------------------------------------------------------- closed-loop ensemble: disturbed tracked rollouts about one trajectory (obca_amd/csrc/obca_ensemble.h)
+ENS_MEM = 16          # doubles of a member record: bad, dev_pos, its node, end_pos, dev_att, dev_vel, dev_rate, min, its sample, its obstacle, below, saturated, du_max, its interval, dx0_pos, 0
+ENS_OUT = 32          # doubles of an instance record: see ensemble_record
+ENS_MMAX = 64         # most members: one per lane
+
+
+def _ensemble_biased(f, parking, x, u, timeScale, Ts, L, substeps, K, dx0, dub, feedback, clamp, pole=None):
+    """_track with a constant input bias, in the order of ens::member: commanded U_k = u_k + K_k (X_k - x_k) if feedback; applied U_k = commanded + dub, clipped if clamp"""
+    x = np.asarray(x, float); u = np.asarray(u, float); nx, N1 = x.shape; N = N1 - 1; nu = u.shape[0]; S = int(substeps); ts = _stage_scale(timeScale, N)
+    box = _PARK_UBOX if parking else _QUAD_UBOX
+    X = np.zeros((nx, N + 1)); P = np.zeros((N * S + 1, 3)); Ua = np.zeros((nu, N)); clipped = np.zeros(N, bool)
+    cur = [float(x[i, 0]) + float(dx0[i]) for i in range(nx)]; bad = False
+    X[:, 0] = cur
+    for k in range(N):
+        U = [float(v) for v in u[:, k]]
+        if feedback:
+            e = [cur[j] - float(x[j, k]) for j in range(nx)]
+            for a in range(nu):
+                s = 0.0
+                for j in range(nx):
+                    s = s + float(K[k, a, j]) * e[j]
+                U[a] = U[a] + s
+        for a in range(nu):
+            U[a] = U[a] + float(dub[a])
+            if clamp:
+                c = box[a][0] if U[a] < box[a][0] else (box[a][1] if U[a] > box[a][1] else U[a])
+                clipped[k] |= c != U[a]
+                U[a] = c
+        Ua[:, k] = U
+        h = float(ts[k]) * float(Ts) / S
+        try:
+            if parking:
+                U = [math.tan(U[0]), U[1]]
+        except (OverflowError, ValueError):
+            U = [math.nan, U[1]]
+        for s_ in range(S):
+            P[k * S + s_] = cur[:3]
+            try:
+                new = _rk4(f, cur, U, h, L)
+                if pole is not None and math.cos(cur[pole]) * math.cos(new[pole]) <= 0.0:
+                    bad = True
+            except (OverflowError, ValueError, ZeroDivisionError):
+                new = [math.nan] * nx
+            cur = new
+        X[:, k + 1] = cur
+    P[N * S] = cur[:3]
+    if bad or not np.isfinite(X).all():
+        X[:] = np.nan
+    return X, P, Ua, clipped
+
+
+def _ensemble_model(parking, x, u, timeScale, Ts, L, members, substeps, dx0, dub, Q, R, Qf, feedback, clamp):
+    x = np.asarray(x, float); u = np.asarray(u, float); nx = x.shape[0]; nu = u.shape[0]; N = u.shape[1]; M = int(members); S = int(substeps)
+    if not 1 <= M <= ENS_MMAX:
+        raise ValueError("need 1 <= members <= 64")
+    dx0 = np.zeros((M, nx)) if dx0 is None else np.asarray(dx0, float).reshape(M, nx)
+    dub = np.zeros((M, nu)) if dub is None else np.asarray(dub, float).reshape(M, nu)
+    f, jvp = (_park_rhs, _park_jvp) if parking else (_quad_rhs, _quad_jvp)
+    q, r, qf = _weights(nx, Q, R, Qf)
+    AB = _linearise(f, jvp, parking, x, u, timeScale, Ts, L, S)
+    K, _, ok = _riccati(AB, nx, q, r, qf)
+    ok = bool(ok and np.isfinite(x).all() and np.isfinite(u).all() and np.isfinite(_stage_scale(timeScale, N)).all() and np.isfinite(Ts))
+    out = []
+    for m in range(M):
+        if not ok:
+            X = np.full(x.shape, np.nan); P = np.full((N * S + 1, 3), np.nan)
+            info = dict(AB=AB, K=np.full(K.shape, np.nan), U=np.full(u.shape, np.nan), clipped=np.zeros(N, bool), feedback=bool(feedback), clamp=bool(clamp), dx0=dx0[m], finite=False)
+        elif not np.any(dub[m]):      # a zero bias: the track statement itself, with this member's offset
+            X, P, info = (track_parking(x, u, timeScale, Ts, L, S, dx0[m], Q, R, Qf, feedback, clamp) if parking
+                          else track_quad(x, u, timeScale, Ts, S, dx0[m], Q, R, Qf, feedback, clamp))
+        else:
+            fin = bool(np.isfinite(dx0[m]).all() and np.isfinite(dub[m]).all())
+            if fin:
+                X, P, Ua, clipped = _ensemble_biased(f, parking, x, u, timeScale, Ts, L, S, K, dx0[m], dub[m], feedback, clamp, None if parking else 3)
+                fin = bool(np.isfinite(X).all())
+            if not fin:
+                X = np.full(x.shape, np.nan); P = np.full((N * S + 1, 3), np.nan); Ua = np.full(u.shape, np.nan); clipped = np.zeros(N, bool)
+            info = dict(AB=AB, K=K, U=Ua, clipped=clipped, feedback=bool(feedback), clamp=bool(clamp), dx0=dx0[m], finite=fin)
+        out.append((X, P, info))
+    return out, ok
+
+
+def ensemble_parking(x, u, timeScale, Ts, L, members, substeps=8, dx0=None, dub=None, Q=None, R=None, Qf=None, feedback=True, clamp=True):
+    """`members` (1 .. 64) closed loops about a parking trajectory x (4,N+1), u (2,N): member m starts at x[:, 0] + dx0[m] (dx0 (M,4) or None = zeros) and applies
+    clip(u_k + K_k (X_k - x_k) + dub[m]) (dub (M,2) a constant input bias per member, or None = zeros).  With a zero dub[m] member m IS track_parking with dx0[m]; a
+    non-zero bias is restated beside it (_ensemble_biased).  Returns (list of (X (4,N+1), samples (N S + 1, 3), info) per member as track_parking returns them, instance_ok):
+    instance_ok False -- a non-finite number in the trajectory, Ts or the time scale, or a bad Riccati pivot -- makes every member not finite."""
+    return _ensemble_model(True, x, u, timeScale, Ts, float(L), members, substeps, dx0, dub, Q, R, Qf, feedback, clamp)
+
+
+def ensemble_quad(x, u, timeScale, Ts, members, substeps=8, dx0=None, dub=None, Q=None, R=None, Qf=None, feedback=True, clamp=True):
+    """The same about a quadcopter trajectory x (12,N+1), u (4,N): dx0 (M,12), dub (M,4), track_quad for a zero bias."""
+    return _ensemble_model(False, x, u, timeScale, Ts, None, members, substeps, dx0, dub, Q, R, Qf, feedback, clamp)
+
+
+def ensemble_member_record(x, u, X, c, substeps, need, info):
+    """the ENS_MEM doubles of one member from what track_record makes of it (c (N S + 1, nOb) the clearances of its samples): [0] bad, [1] dev_pos, [2] its node, [3] end_pos,
+    [4] dev_att, [5] dev_vel, [6] dev_rate, [7] min, [8] its sample, [9] its obstacle, [10] below, [11] saturated, [12] du_max, [13] its interval, [14] dx0_pos, [15] 0.
+    Not finite: real fields NaN, indices and counts -1."""
+    t = track_record(x, u, X, c, substeps, need, info)
+    if t[0] != 0:
+        return np.array([1, np.nan, -1, np.nan, np.nan, np.nan, np.nan, np.nan, -1, -1, -1, -1, np.nan, -1, np.nan, 0])
+    return np.array([0, t[1], t[2], t[6], t[3], t[4], t[5], t[16], t[18], t[19], t[20], t[42], t[43], t[44], t[45], 0])
+
+
+def ensemble_record(mem, substeps, feedback, clamp, instance_ok=True):
+    """the ENS_OUT doubles of an instance from its member records (M, ENS_MEM), walked in ascending member order as ens::ensemble_reduce walks them: [0] bad, [1] M, [2] S,
+    [3] feedback, [4] clamp, [5] members_bad, [6] members_hit (good members with a sample under need), [7] members_sat, [8] min over the good members, [9] its member,
+    [10] its sample, [11] its obstacle, [12] dev_pos max, [13] its member, [14] its node, [15] end_pos max, [16] its member, [17] dev_att, [18] dev_vel, [19] dev_rate,
+    [20] du_max, [21] its member, [22] its interval, [23] mean of end_pos, [24] mean of min, [25] below summed, [26..31] 0.  Ties go to the smaller member; bad members
+    enter nothing.  instance_ok False: counts -1; no good member: real fields NaN, indices -1."""
+    mem = np.asarray(mem, float).reshape(-1, ENS_MEM); M = len(mem)
+    r = np.zeros(ENS_OUT); r[0] = 0 if instance_ok else 1; r[1] = M; r[2] = int(substeps); r[3] = int(bool(feedback)); r[4] = int(bool(clamp))
+    good = [m for m in range(M) if mem[m, 0] == 0]
+    r[5] = M - len(good); r[6] = sum(1 for m in good if mem[m, 10] > 0); r[7] = sum(1 for m in good if mem[m, 11] > 0); r[25] = sum(mem[m, 10] for m in good)
+    if not instance_ok:
+        r[[5, 6, 7, 25]] = -1
+    if not instance_ok or not good:
+        r[[8, 12, 15, 17, 18, 19, 20, 23, 24]] = np.nan; r[[9, 10, 11, 13, 14, 16, 21, 22]] = -1
+        return r
+    g = mem[good]
+    a = int(np.argmin(g[:, 7])); r[8:12] = [g[a, 7], good[a], g[a, 8], g[a, 9]]      # (argmin / argmax: the first, the smaller member)
+    a = int(np.argmax(g[:, 1])); r[12:15] = [g[a, 1], good[a], g[a, 2]]
+    a = int(np.argmax(g[:, 3])); r[15:17] = [g[a, 3], good[a]]
+    r[17:20] = g[:, 4:7].max(axis=0)
+    a = int(np.argmax(g[:, 12])); r[20:23] = [g[a, 12], good[a], g[a, 13]]
+    se = sm = 0.0
+    for m in good:      # one sum in ascending member order, as the kernel text adds
+        se = se + mem[m, 3]; sm = sm + mem[m, 7]
+    r[23] = se / len(good); r[24] = sm / len(good)
+    return r
