@@ -22,7 +22,7 @@ import numpy as np
 from . import buildflags, cabi, planner
 from .cabi import Opts      # `typedef struct obca_opts` of include/obca_hip.h, read from the header
 from .validate import (VIOL_NAMES, QUAD_VIOL_NAMES, DMIN, CLR_OUT, ROLL_OUT, TRK_OUT, TRACK_Q_PARKING, TRACK_R_PARKING, TRACK_QF_PARKING, TRACK_Q_QUAD, TRACK_R_QUAD,
-                       TRACK_QF_QUAD, ENS_MEM, ENS_OUT, ENS_MMAX)
+                       TRACK_QF_QUAD, ENS_MEM, ENS_OUT, ENS_MMAX, CERT_OUT, CERT_TICKS)
 
 _LIBPATH = os.environ.get("OBCA_HIP_LIBRARY") or buildflags.PIECES["hip"].out   # override: diagnostic builds
 _lib = None
@@ -65,6 +65,7 @@ def _load():
     cabi.bind(_lib, "obca_rollout.h")                     # solved batches applied to the continuous vehicle models
     cabi.bind(_lib, "obca_track.h")                       # ... and tracked on them by a time-varying LQR
     cabi.bind(_lib, "obca_ensemble.h")                    # ... from a spread of start offsets and input biases at once
+    cabi.bind(_lib, "obca_certify.h")                     # the clearance certified along the whole path
     return _lib
 
 
@@ -115,6 +116,10 @@ TRACK_EXPORTS = ["obca_batch_track", "obca_batch_track_ms", "obca_batch_track_st
 # ensemble_members, ensemble_final, ensemble_ms, parking_ensemble_batch, quadcopter_ensemble_batch)
 ENSEMBLE_EXPORTS = ["obca_batch_ensemble", "obca_batch_ensemble_ms", "obca_batch_ensemble_members", "obca_batch_ensemble_final", "obca_parking_ensemble_batch",
                     "obca_quad_batch_ensemble", "obca_quad_batch_ensemble_ms", "obca_quad_batch_ensemble_members", "obca_quad_batch_ensemble_final", "obca_quadcopter_ensemble_batch"]
+# include/obca_certify.h: the clearance of solutions and trajectories certified along the whole path by conservative advancement (Batch.certify, QuadBatch.certify,
+# certify_intervals, certify_ms, parking_certify_batch, quadcopter_certify_batch)
+CERTIFY_EXPORTS = ["obca_batch_certify", "obca_batch_certify_ms", "obca_batch_certify_intervals", "obca_parking_certify_batch", "obca_quad_batch_certify",
+                   "obca_quad_batch_certify_ms", "obca_quad_batch_certify_intervals", "obca_quadcopter_certify_batch"]
 QUAD_PLAN_STATUS = {0: "no path", -1: "more way-points than cap", -2: "the start or goal point is blocked, or a coordinate of the record is not finite",
                     -3: "the relaxation hit its sweep bound", -4: "not selected"}
 QUAD_REFINE_STATUS = {0: "refined from the solution", 1: "interpolated from the uploaded warm start (the last solve failed, or its iterate is not finite)",
@@ -233,6 +238,24 @@ def _clearance_dict(rec, substeps, nOb):
     q = rec[:, 2].astype(np.int64); S = int(substeps)
     return dict(min=rec[:, 0], min_nodes=rec[:, 1], sample=q, stage=np.where(q >= 0, q // S, -1), substep=np.where(q >= 0, q % S, -1), obstacle=rec[:, 3].astype(np.int64),
                 below=rec[:, 4].astype(np.int64), samples=rec[:, 5].astype(np.int64), per_obstacle=rec[:, 8:8 + int(nOb)], finite=rec[:, 6] == 0)
+
+
+def _certify(B, call):
+    """the records of a certify entry point, `call(out)` with out (B, CERT_OUT), and the dict they are returned in: lb (B,) the PROVEN lower bound of the clearance over the
+    whole path (-inf: an item was left undecided), seen the smallest clearance sampled, at `interval`, `tick` (of CERT_TICKS per interval; interval N is node N) and
+    `obstacle`; violated = intervals with a sample under need, first_violation (B, 3) = (interval, tick, obstacle) of the first one, -1 where none; undecided items;
+    samples taken in total and samples_max in one item; lipschitz = the largest speed bound of an interval; certified (B,) bool: clearance >= need - slack everywhere on
+    the path; finite (B,) bool -- False: a non-finite number in the trajectory, the values of that instance are NaN"""
+    rec = np.zeros((B, CERT_OUT))
+    call(rec)
+    return _certify_dict(rec)
+
+
+def _certify_dict(rec):
+    """the dict of _certify from records (B, CERT_OUT)"""
+    i64 = lambda a: a.astype(np.int64)
+    return dict(lb=rec[:, 0], seen=rec[:, 1], interval=i64(rec[:, 2]), tick=i64(rec[:, 3]), obstacle=i64(rec[:, 4]), violated=i64(rec[:, 5]), first_violation=i64(rec[:, 6:9]),
+                undecided=i64(rec[:, 9]), samples=i64(rec[:, 10]), samples_max=i64(rec[:, 11]), lipschitz=rec[:, 12], certified=rec[:, 13] != 0, finite=rec[:, 14] == 0)
 
 
 def _rollout(B, substeps, nOb, call):
@@ -493,6 +516,20 @@ class _DeviceBatch(_Handle):
         """HIP-event duration of the last clearance kernel"""
         return self._floats("clearance_ms")
 
+    def _certify(self, need, slack, max_steps):
+        return _certify(self.B, lambda out: self._call("certify", float(need), float(slack), int(max_steps), out))
+
+    def certify_intervals(self):
+        """[lb_k, seen_k] of the last certify(), fetched from the device: (B, N+1, 2) -- per interval (row N: node N) the proven bound and the smallest sampled clearance over
+        the obstacles; lb_k = -inf where an item of the interval was left undecided, NaN for an instance that was not finite."""
+        iv = np.zeros((self.B, self.N + 1, 2))
+        self._call("certify_intervals", iv)
+        return iv
+
+    def certify_ms(self):
+        """HIP-event duration of the last certify kernel"""
+        return self._floats("certify_ms")
+
     def _rollout(self, nOb, substeps, restart, need):
         return _rollout(self.B, substeps, nOb, lambda out: self._call("rollout", int(substeps), int(restart), float(need), out))
 
@@ -707,6 +744,15 @@ class Batch(_DeviceBatch):
         0 = touches or overlaps.  validate() looks at the nodes only; a solution can pass it and cut a corner in between.  Returns the dict of _clearance; only 24 numbers
         per instance are downloaded."""
         return _clearance(self.B, substeps, int(self.nObs.max()), lambda out: self._call("clearance", int(substeps), float(need), out))
+
+    def certify(self, need=DMIN, slack=0.01, max_steps=CERT_TICKS):
+        """A CERTIFICATE for the clearance of the last solution along its WHOLE path, ON THE DEVICE (obca_batch_certify; the numpy statement is
+        obca_amd.validate.certify_parking + certify_record): clearance() samples `substeps` poses per interval and says nothing about what lies between them.  Here every
+        (interval, obstacle) pair is walked by conservative advancement -- a pose with clearance c clears the stretch on which no point of the car moves farther than c, the
+        next sample goes to its end --, so samples go where the path is close to an obstacle and a far obstacle costs one.  certified: clearance >= need - slack everywhere
+        on the path the discretisation's own partial step draws between the nodes; otherwise a sample under `need` was found (violated, first_violation) or an item ran out
+        of max_steps (undecided).  Returns the dict of _certify; 16 numbers per instance are downloaded, certify_intervals() fetches the per-interval bounds."""
+        return self._certify(need, slack, max_steps)
 
 
     def refine(self, factor=2, select=None, duals=False, into=None):
@@ -941,6 +987,21 @@ def parking_constraints_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, x, u, 
     return _verdict(B, VIOL_NAMES, lambda *out: ctx._check(_load().obca_parking_constraints_batch(ctx._h, B, N, *ins, *out), "obca_parking_constraints_batch"), ref_ok=True)
 
 
+def parking_certify_batch(N, Ts, L, ego, vOb, A, b, x, u, timeScale=None, need=DMIN, slack=0.01, max_steps=CERT_TICKS, device=0, intervals=True):
+    """Batch.certify for arbitrary trajectories (obca_parking_certify_batch): the arguments of parking_clearance_batch up to timeScale, then those of Batch.certify.  Returns
+    the dict of Batch.certify, with `intervals` (B, N+1, 2) unless switched off."""
+    x = np.asarray(x, float); u = np.asarray(u, float); N = int(N); B = x.shape[0]
+    if x.shape != (B, 4, N + 1) or u.shape != (B, 2, N):
+        raise ObcaError(f"x must be (B,4,N+1) and u (B,2,N); got {x.shape}, {u.shape}")
+    ctx = _ctx(device)
+    nObs, vflat, Aflat, bflat = _norm_obstacles(B, vOb, A, b)
+    ins = (_per_instance(Ts, B), L, _in(ego), _in(nObs, np.int32), _in(vflat, np.int32), _in(Aflat), _in(bflat), _in(np.transpose(x, (0, 2, 1))), _in(np.transpose(u, (0, 2, 1))),
+           None if timeScale is None else _time_scale(timeScale, B, N + 1), float(need), float(slack), int(max_steps))
+    iv = np.zeros((B, N + 1, 2)) if intervals else None
+    r = _certify(B, lambda out: ctx._check(_load().obca_parking_certify_batch(ctx._h, B, N, *ins, out, iv), "obca_parking_certify_batch"))
+    return dict(r, intervals=iv) if intervals else r
+
+
 def parking_clearance_batch(N, Ts, L, ego, vOb, A, b, x, u, timeScale=None, substeps=8, need=DMIN, device=0):
     """Batch.clearance for arbitrary trajectories (obca_parking_clearance_batch): x (B,4,N+1), u (B,2,N) -- the shapes the solve calls return --, timeScale scalar, (B,),
     (B,N+1) or None (= 1).  The arguments are those of parking_constraints_batch, in its order, that the check reads: no start, goal, bounds or multipliers.  Obstacles and
@@ -1113,6 +1174,11 @@ class QuadBatch(_DeviceBatch):
         interval is sampled `substeps` times, clearance = distance of the point to a box - R (-R inside the box).  Returns the dict of Batch.clearance, 5 obstacles."""
         return _clearance(self.B, substeps, 5, lambda out: self._call("clearance", int(substeps), float(need), out))
 
+    def certify(self, need=0.0, slack=0.01, max_steps=CERT_TICKS):
+        """A certificate for the clearance of the last solution along its whole path, on the device (obca_quad_batch_certify; numpy: obca_amd.validate.certify_quad +
+        certify_record): Batch.certify on the straight segment of every interval, speed bound |v_k|, clearance = distance of the point to a box - R."""
+        return self._certify(need, slack, max_steps)
+
     def refine(self, factor=2, select=None, margin=0.0, into=None):
         """The solved instances `select` (an index array or a boolean mask over this batch's instances; None: all, duplicates allowed) on the horizon factor * N, ON THE
         DEVICE (obca_quad_batch_subdivide_into; the numpy statement is obca_amd.validate.refine_quad): the same NLP with Ts / factor and the radius R + margin, and as
@@ -1187,6 +1253,19 @@ def quadcopter_clearance_batch(x, timeScale, Ts, ob, R, substeps=8, need=0.0, de
     ctx = _ctx(device)
     ins = (_per_instance(Ts, B), R, _boxes(ob, B), _in(np.transpose(x, (0, 2, 1))), _time_scale(1.0 if timeScale is None else timeScale, B, N1), int(substeps), float(need))
     return _clearance(B, substeps, 5, lambda out: ctx._check(_load().obca_quadcopter_clearance_batch(ctx._h, B, N1 - 1, *ins, out), "obca_quadcopter_clearance_batch"))
+
+
+def quadcopter_certify_batch(x, timeScale, Ts, ob, R, need=0.0, slack=0.01, max_steps=CERT_TICKS, device=0, intervals=True):
+    """QuadBatch.certify for arbitrary trajectories (obca_quadcopter_certify_batch): the arguments of quadcopter_clearance_batch up to R, then those of QuadBatch.certify.
+    Returns the dict of QuadBatch.certify, with `intervals` (B, N+1, 2) unless switched off."""
+    x = np.asarray(x, float); B, _, N1 = x.shape
+    if x.shape != (B, 12, N1):
+        raise ObcaError(f"x must be (B,12,N+1); got {x.shape}")
+    ctx = _ctx(device)
+    ins = (_per_instance(Ts, B), R, _boxes(ob, B), _in(np.transpose(x, (0, 2, 1))), _time_scale(1.0 if timeScale is None else timeScale, B, N1), float(need), float(slack), int(max_steps))
+    iv = np.zeros((B, N1, 2)) if intervals else None
+    r = _certify(B, lambda out: ctx._check(_load().obca_quadcopter_certify_batch(ctx._h, B, N1 - 1, *ins, out, iv), "obca_quadcopter_certify_batch"))
+    return dict(r, intervals=iv) if intervals else r
 
 
 def quadcopter_rollout_batch(x, u, timeScale, Ts, ob, R, substeps=8, restart=False, need=0.0, device=0, states=True):

@@ -10,6 +10,7 @@
 //   obca_rollout_*_kernel   : one wavefront per instance, a solution or a caller's trajectory applied to the continuous vehicle model: deviations, clearance of the rolled samples (obca_rollout.h).
 //   obca_track_*_kernel     : one wavefront per instance, TVLQR gains about a solution or a caller's trajectory and the closed loop rolled on the continuous model (obca_track.h).
 //   obca_ensemble_*_kernel  : one wavefront per instance, one member per lane: up to 64 disturbed closed loops about a solution or a caller's trajectory, the gains computed once (obca_ensemble.h).
+//   obca_certify_*_kernel   : one wavefront per instance, the clearance of a solution or of a caller's trajectory certified along its whole path by conservative advancement (obca_certify.h).
 //   obca_refine_*_kernel    : one wavefront per destination instance, a solved parking instance on a finer horizon (obca_refine.h): into a second resident batch or host-bound arrays.
 //   obca_quad_subdivide_*_kernel : the same for a solved quadcopter instance (obca_quad_subdivide.h): it rewrites a problem record.
 //   obca_path_ws_*_kernel   : one wavefront per instance, the parking warm start from a planner path (obca_path_ws.h): into host-bound arrays or into a resident batch.
@@ -45,6 +46,7 @@
 #include "obca_rollout.h"
 #include "obca_track.h"
 #include "obca_ensemble.h"
+#include "obca_certify.h"
 #include "../../include/obca_hip.h"
 #include "../../include/obca_path_ws.h"
 #include "../../include/obca_clearance.h"
@@ -53,6 +55,7 @@
 #include "../../include/obca_rollout.h"
 #include "../../include/obca_track.h"
 #include "../../include/obca_ensemble.h"
+#include "../../include/obca_certify.h"
 
 using namespace obca;
 #ifdef OBCA_POISON
@@ -68,6 +71,7 @@ static_assert(OBCA_CLR_OUT == CL_OUT && OBCA_CLR_MAXSUB == CL_SMAX && OBCA_CLR_T
 static_assert(OBCA_REFINE_MAXFACTOR == RF_MAXFACTOR, "ABI limits must match the kernels");
 static_assert(OBCA_ROLL_OUT == RO_OUT && OBCA_ROLL_CLR == RO_CLR && OBCA_ROLL_MAXSUB == CL_SMAX, "ABI limits must match the kernels");
 static_assert(OBCA_TRK_OUT == TK_OUT, "ABI limits must match the kernels");
+static_assert(OBCA_CERT_OUT == CT_OUT && OBCA_CERT_TICKS == CT_TICKS, "ABI limits must match the kernels");
 static_assert(OBCA_VMAX == OB_VMAX && OBCA_NOBMAX == OB_NOBMAX && OBCA_NMAX == OB_NMAX && OBCA_MMAX == OB_MMAX, "ABI limits must match the kernels");
 
 struct DevBufs {
@@ -398,6 +402,26 @@ __global__ __launch_bounds__(QNT) void obca_ensemble_quad_kernel(int B, int N, c
                                 out + (size_t)inst * EN_OUT);
 }
 
+// clearance certificate (obca_certify.h): one wavefront per instance; the arguments of the clearance kernels with need, slack and max_steps in place of the sub-steps, then
+// the interval array (2 (N + 1) per instance).  The item table is the launch's dynamic LDS: cert::certify_work_len(N, the batch's most obstacles) doubles
+template <int VM>
+__global__ __launch_bounds__(OB_NT) void obca_certify_parking_kernel(int B, int N, const double *prob, size_t s_prob, const double *z, size_t s_z, const double *ts, double need, double slack, int max_steps,
+                                                                     double *iv, double *out) {
+    extern __shared__ double cert_work[];
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    cert::certify_parking_instance<VM>(N, prob + (size_t)inst * s_prob, z + (size_t)inst * s_z, ts ? ts + (size_t)inst * (N + 1) : nullptr, need, slack, max_steps, 0, cert_work,
+                                       iv + (size_t)inst * cert::certify_iv_len(N), out + (size_t)inst * CT_OUT);
+}
+__global__ __launch_bounds__(QNT) void obca_certify_quad_kernel(int B, int N, const double *prob, size_t s_prob, const double *x, size_t s_x, const double *ts, size_t s_ts, int tstride,
+                                                                double need, double slack, int max_steps, double *iv, double *out) {
+    extern __shared__ double cert_work[];
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    cert::certify_quad_instance(N, prob + (size_t)inst * s_prob, x + (size_t)inst * s_x, ts + (size_t)inst * s_ts, tstride, need, slack, max_steps, 0, cert_work,
+                                iv + (size_t)inst * cert::certify_iv_len(N), out + (size_t)inst * CT_OUT);
+}
+
 // warm starts from planner paths (obca_path_ws.h): one wavefront per instance.  paths / dirs: B x rows (x 3) dense on the device -- the rows below the longest count of the
 // call --, `cap` the rows of the caller's arrays (what a count is checked against).  Host-pointer call: outputs per instance, zeros where the status is negative.
 __global__ __launch_bounds__(OB_NT) void obca_path_ws_host_kernel(int B, int N, const double *paths, const int *dirs, const int *counts, int rows, int cap, const double *xF /* 4 x B or NULL */,
@@ -603,6 +627,9 @@ struct BatchCore {
     ValBufs ens;                                            // ... and for the ensemble calls (obca_ensemble.h), again with buffers of their own
     DevBuf ens_w, ens_K, ens_mem, ens_fin;                  // [A|B] N nx (nx + nu) x B; the gains; the member records M x EN_MEM x B; the final states M x nx x B
     int ens_B = 0, ens_N = 0, ens_M = 0;                    // the instances, horizon and members of the last ensemble call (0: none yet)
+    ValBufs cer;                                            // ... and for the certify calls (obca_certify.h)
+    DevBuf cer_iv;                                          // their interval arrays, 2 (N + 1) x B
+    int cer_B = 0, cer_N = 0;                               // the instances and horizon of the last certify call (0: none yet)
     BatchCore(obca_ctx *c, int dev, hipStream_t s, int B_, int N_) : ctx(c), device(dev), stream(s), B(B_), cap(B_), N(N_) {}
 };
 struct obca_quad_batch : BatchCore {
@@ -665,8 +692,8 @@ static int core_phase_cycles(BatchCore *bt, const double *prof, double *out /* B
 // everything of the core that a batch's destroy releases, except `stage` (it goes with the family's device buffers); the batch's device is selected
 static void core_release(BatchCore *bt) {
     bt->rol_w.release(); bt->trk_w.release(); bt->trk_K.release();
-    bt->ens_w.release(); bt->ens_K.release(); bt->ens_mem.release(); bt->ens_fin.release();
-    for (ValBufs *pv : {&bt->val, &bt->clr, &bt->rol, &bt->trk, &bt->ens}) {
+    bt->ens_w.release(); bt->ens_K.release(); bt->ens_mem.release(); bt->ens_fin.release(); bt->cer_iv.release();
+    for (ValBufs *pv : {&bt->val, &bt->clr, &bt->rol, &bt->trk, &bt->ens, &bt->cer}) {
         ValBufs &v = *pv;
         v.d_in.release(); v.d_out.release(); v.h_in.release(); v.h_out.release(); v.ev.release();
     }
@@ -1265,6 +1292,49 @@ static int batch_ensemble_range(obca_batch *bt, bool host, const double *ts, int
     return ensemble_finish(bt, rc, d, lo, mem, fin);
 }
 
+// What the two certify routes share (obca_certify.h): the interval arrays for B instances before the kernel; after it the bookkeeping of the *_intervals calls and, for a
+// host-pointer call, the chunk's interval arrays into the caller's iv.
+static int certify_reserve(BatchCore *bt) {
+    use_device(bt->device);
+    if (bt->cer_iv.reserve((size_t)bt->B * cert::certify_iv_len(bt->N), bt->stream) != hipSuccess) { bt->err = "hipMalloc(certify interval array) failed"; return -2; }
+    return 0;
+}
+static int certify_finish(BatchCore *bt, int rc, int lo, double *iv) {
+    bt->cer_B = bt->cer_N = 0;
+    if (rc) return rc;
+    bt->cer_B = bt->B; bt->cer_N = bt->N;
+    const size_t n = cert::certify_iv_len(bt->N);
+    if (iv) HIPCHK(bt, hipMemcpy(iv + (size_t)lo * n, (const double *)bt->cer_iv, (size_t)bt->B * n * sizeof(double), hipMemcpyDeviceToHost));      // (run_validate has synchronised the stream)
+    return 0;
+}
+static int certify_fetch(BatchCore *bt, double *iv, const char *entry) {
+    if (!iv) { bt->ctx->err = std::string(entry) + ": NULL argument"; return -1; }
+    if (!bt->cer_B || bt->cer_B != bt->B || bt->cer_N != bt->N) { bt->ctx->err = std::string(entry) + ": no certify call has run on this batch since it was last filled"; return -1; }
+    use_device(bt->device);
+    if (hipStreamSynchronize(bt->stream) != hipSuccess ||
+        hipMemcpy(iv, (const double *)bt->cer_iv, (size_t)bt->B * cert::certify_iv_len(bt->N) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+        bt->ctx->err = std::string(entry) + ": D2H failed"; return -2;
+    }
+    return 0;
+}
+// The certificate of the batch's parking instances: the arguments of batch_clearance_range with need, slack and max_steps, then the caller's iv (host-pointer calls; nullptr:
+// the interval arrays stay on the device)
+static int batch_certify_range(obca_batch *bt, bool host, const double *ts, double need, double slack, int max_steps, int lo, double *out, double *iv) {
+    const int B = bt->B, N = bt->N, N1 = N + 1;
+    if (int rc = certify_reserve(bt)) return rc;
+    const size_t lds = cert::certify_work_len(N, bt->nObMax) * sizeof(double);      // (at most 3 x 129 x 16 doubles = 49.5 KB: below the 64 KB a launch may ask for)
+    const int rc = run_validate(bt, bt->cer, ts ? (size_t)N1 : 0, ts != nullptr, CT_OUT, [&](int i, double *a) {
+        memcpy(a, ts + ((size_t)lo + i) * N1, sizeof(double) * N1);
+    }, [&] {
+        const double *z = host ? bt->d.z0 : bt->d.z, *dts = ts ? (const double *)bt->cer.d_in : nullptr;
+#define CERT_LAUNCH(VM) hipLaunchKernelGGL(obca_certify_parking_kernel<VM>, dim3(B), dim3(OB_NT), lds, bt->stream, B, N, (const double *)bt->d.prob, bt->d.s_prob, z, bt->d.s_z, dts, need, slack, max_steps, \
+                                           (double *)bt->cer_iv, (double *)bt->cer.d_out)
+        if (bt->vmax <= 2) CERT_LAUNCH(2); else if (bt->vmax <= OB_VMID) CERT_LAUNCH(OB_VMID); else CERT_LAUNCH(OB_VMAX);      // (the row class of launch_dualws)
+#undef CERT_LAUNCH
+    }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * CT_OUT, o, sizeof(double) * CT_OUT); });
+    return certify_finish(bt, rc, lo, iv);
+}
+
 // ---- chunked execution of a host-pointer call over the slots of the context (work queue)
 template <typename F>
 static int run_chunks(obca_ctx *ctx, int B, int chunk, F &&fn /* int(Slot &, int lo, int n, std::string &err) */) {
@@ -1538,6 +1608,29 @@ int obca_parking_ensemble_batch(obca_ctx *ctx, int B, int N, const double *Ts, d
     if (int rc = park_prefix(ctx->err, B, nOb, vOb, in)) return rc;
     const trk::Weights w = trk::make_weights(q, r, qf, 4, 2);
     return parking_chunks(ctx, 0, B, N, in, [&](obca_batch *bt, int lo) { return batch_ensemble_range(bt, true, timeScale, substeps, members, feedback, clamp, w, dx0, dub, need, lo, out, mem, fin); });
+}
+
+int obca_batch_certify(obca_batch *bt, double need, double slack, int max_steps, double *out) {
+    if (!bt) return -1;
+    if (!out) { bt->ctx->err = "obca_batch_certify: NULL argument"; return -1; }
+    if (const char *bad = cert::certify_check_args(need, slack, max_steps)) { bt->ctx->err = std::string("obca_batch_certify: ") + bad; return -1; }
+    if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_batch_certify: nothing has been solved since the last upload or shift"; return -1; }
+    if (bt->N < 1) { bt->ctx->err = "obca_batch_certify: needs a horizon N>=1"; return -1; }
+    return fin(bt, batch_certify_range(bt, false, nullptr, need, slack, max_steps, 0, out, nullptr));
+}
+int obca_batch_certify_ms(obca_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->cer.ev, ms, "obca_batch_certify_ms: no certify call has run on this batch") : -1; }
+int obca_batch_certify_intervals(obca_batch *bt, double *iv) { return bt ? certify_fetch(bt, iv, "obca_batch_certify_intervals") : -1; }
+int obca_parking_certify_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const int *nOb, const int *vOb, const double *A, const double *b,
+                               const double *x, const double *u, const double *timeScale, double need, double slack, int max_steps, double *out, double *iv) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 1 || N > OBCA_NMAX) { ctx->err = "obca_parking_certify_batch: need B>=1, 1<=N<=OBCA_NMAX"; return -1; }
+    if (!Ts || !ego || !nOb || !vOb || !A || !b || !x || !u || !out) { ctx->err = "obca_parking_certify_batch: NULL argument"; return -1; }
+    if (const char *bad = cert::certify_check_args(need, slack, max_steps)) { ctx->err = std::string("obca_parking_certify_batch: ") + bad; return -1; }
+    const std::vector<double> zero((size_t)B * (N + 1), 0.0);      // the tracking reference of a solve: the call does not read it (nor the bounds, the start and the goal)
+    const double XYb[4] = {0, 0, 0, 0};
+    ParkIn in = {Ts, L, ego, XYb, 0, nullptr, nullptr, nOb, vOb, A, b, zero.data(), zero.data(), zero.data(), x, u, nullptr, nullptr, {}, {}};
+    if (int rc = park_prefix(ctx->err, B, nOb, vOb, in)) return rc;
+    return parking_chunks(ctx, 0, B, N, in, [&](obca_batch *bt, int lo) { return batch_certify_range(bt, true, timeScale, need, slack, max_steps, lo, out, iv); });
 }
 
 int obca_parking_signed_dist_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const double XYb[4],
@@ -1967,6 +2060,22 @@ static int quad_ensemble_range(obca_quad_batch *bt, const double *u, const doubl
     }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * EN_OUT, o, sizeof(double) * EN_OUT); });
     return ensemble_finish(bt, rc, d, lo, mem, fin);
 }
+// the certificate of the batch's quadcopter instances (obca_certify.h): quad_clearance_range with need, slack and max_steps, then the caller's iv
+static int quad_certify_range(obca_quad_batch *bt, const double *ts, double need, double slack, int max_steps, int lo, double *out, double *iv) {
+    const int B = bt->B, N = bt->N, N1 = N + 1; const QDevBufs &d = bt->d;
+    quad::QLay l; quad::q_make_layout(N, l);
+    if (int rc = certify_reserve(bt)) return rc;
+    const size_t lds = cert::certify_work_len(N, QOB) * sizeof(double);
+    const int rc = run_validate(bt, bt->cer, ts ? (size_t)N1 : 0, ts != nullptr, CT_OUT, [&](int i, double *a) {
+        memcpy(a, ts + ((size_t)lo + i) * N1, sizeof(double) * N1);
+    }, [&] {
+        if (ts) hipLaunchKernelGGL(obca_certify_quad_kernel, dim3(B), dim3(QNT), lds, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)d.prob + QPH_SIZE, d.s_prob, (const double *)bt->cer.d_in, (size_t)N1, 1,
+                                   need, slack, max_steps, (double *)bt->cer_iv, (double *)bt->cer.d_out);
+        else hipLaunchKernelGGL(obca_certify_quad_kernel, dim3(B), dim3(QNT), lds, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)d.z + l.x, d.s_z, (const double *)d.z + l.t, d.s_z, 0,
+                                need, slack, max_steps, (double *)bt->cer_iv, (double *)bt->cer.d_out);
+    }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * CT_OUT, o, sizeof(double) * CT_OUT); });
+    return certify_finish(bt, rc, lo, iv);
+}
 // instances (one wavefront each) resident per CU, as OBCA_RESIDENT_PER_CU for the parking kernel: what pick_chunk sizes a quadcopter chunk by
 static const int QUAD_RESIDENT_PER_CU = (QNT == 64 ? 4 : 2) * OBCA_QUAD_WAVES_PER_EU;
 // parking_chunks for the quadcopter; the slot's cached batch only has to hold the chunk at hand
@@ -2120,6 +2229,25 @@ int obca_quadcopter_ensemble_batch(obca_ctx *ctx, int B, int N, const double *Ts
     const QuadIn in = {Ts, R, zero.data(), zero.data(), ob, x, one.data(), 0, 0};
     const trk::Weights w = trk::make_weights(q, r, qf, QX, QU);
     return quad_chunks(ctx, B, N, in, [&](obca_quad_batch *bt, int lo) { return quad_ensemble_range(bt, u, timeScale, substeps, members, feedback, clamp, w, dx0, dub, need, lo, out, mem, fin); });
+}
+int obca_quad_batch_certify(obca_quad_batch *bt, double need, double slack, int max_steps, double *out) {
+    if (!bt) return -1;
+    if (!out) { bt->ctx->err = "obca_quad_batch_certify: NULL argument"; return -1; }
+    if (const char *bad = cert::certify_check_args(need, slack, max_steps)) { bt->ctx->err = std::string("obca_quad_batch_certify: ") + bad; return -1; }
+    if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_quad_batch_certify: nothing has been solved since the last upload or shift"; return -1; }
+    return fin(bt, quad_certify_range(bt, nullptr, need, slack, max_steps, 0, out, nullptr));
+}
+int obca_quad_batch_certify_ms(obca_quad_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->cer.ev, ms, "obca_quad_batch_certify_ms: no certify call has run on this batch") : -1; }
+int obca_quad_batch_certify_intervals(obca_quad_batch *bt, double *iv) { return bt ? certify_fetch(bt, iv, "obca_quad_batch_certify_intervals") : -1; }
+int obca_quadcopter_certify_batch(obca_ctx *ctx, int B, int N, const double *Ts, double R, const double *ob, const double *x, const double *timeScale, double need, double slack, int max_steps,
+                                  double *out, double *iv) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 2 || N > OBCA_QUAD_NMAX) { ctx->err = "obca_quadcopter_certify_batch: need B>=1, 2<=N<=OBCA_QUAD_NMAX"; return -1; }
+    if (!Ts || !ob || !x || !timeScale || !out) { ctx->err = "obca_quadcopter_certify_batch: NULL argument"; return -1; }
+    if (const char *bad = cert::certify_check_args(need, slack, max_steps)) { ctx->err = std::string("obca_quadcopter_certify_batch: ") + bad; return -1; }
+    const std::vector<double> zero((size_t)B * QX, 0.0), one((size_t)B, 1.0);      // start, goal and timeWS of a solve: the call reads none of them
+    const QuadIn in = {Ts, R, zero.data(), zero.data(), ob, x, one.data(), 0, 0};
+    return quad_chunks(ctx, B, N, in, [&](obca_quad_batch *bt, int lo) { return quad_certify_range(bt, timeScale, need, slack, max_steps, lo, out, iv); });
 }
 int obca_quad_batch_download(obca_quad_batch *bt, double *xp, double *up, double *ts, int *exitflag, double *lp, double *slp, double *info) {
     if (!bt) return -1;

@@ -20,6 +20,8 @@ rollout_parking, rollout_quad, rollout_record : the numpy statement of the rollo
     Batch.rollout, QuadBatch.rollout): held inputs, classical RK4, the rolled node states, the sample poses and the record of deviations and clearances.
 track_gains_parking, track_gains_quad, track_parking, track_quad, track_record : the numpy statement of the closed-loop rollout (obca_amd/csrc/obca_track.h, Batch.track,
     QuadBatch.track): the interval map's derivatives by forward-mode tangents, the Riccati recursion, the held TVLQR feedback on the continuous models and its record.
+certify_lipschitz_parking, certify_lipschitz_quad, certify_parking, certify_quad, certify_record : the numpy statement of the clearance certificate (obca_amd/csrc/obca_certify.h,
+    Batch.certify, QuadBatch.certify): the speed bound of an interval, conservative advancement of every (interval, obstacle) item with a distance the caller passes, and the record.
 Shapes follow the reference: x (4,N+1), u (2,N), l (M,N+1), n (4nOb,N+1), timeScale (N+1,) .
 """
 import math
@@ -748,3 +750,112 @@ def ensemble_record(mem, substeps, feedback, clamp, instance_ok=True):
         se = se + mem[m, 3]; sm = sm + mem[m, 7]
     r[23] = se / len(good); r[24] = sm / len(good)
     return r
+
+
+# ---------------------------------------------------------------- clearance certified along the whole path (obca_amd/csrc/obca_certify.h)
+CERT_OUT = 16         # doubles of a record: see certify_record
+CERT_TICKS = 4096     # G: an interval is tau = h_k m / G, m = 0 .. G
+
+
+def certify_lipschitz_parking(xk, uk, h, L, ego):
+    """Lambda of one parking interval [m per unit tau]: no point of the car moves faster along park_step from node xk (4,) with uk (2,) over tau in [0, h].  With v = xk[3],
+    a = uk[1], tn = |tan uk[0]|: V = max(|v|, |v + h a|), Sm = max(|v|, |v + h a / 2|), rho the car point farthest from the reference point;
+    Lambda = V + |h| Sm |v| tn / (2 L) + rho V tn / L (|d(X, Y) / dtau| <= the first two terms, rho |dpsi / dtau| <= the third)."""
+    g, off = _geom(ego)
+    a0 = abs(off) + g[0]; rho = np.sqrt(a0 * a0 + g[1] * g[1])
+    v = float(xk[3]); av = abs(v); tn = abs(np.tan(float(uk[0]))); ha = h * float(uk[1])
+    V = max(av, abs(v + ha)); Sm = max(av, abs(v + ha / 2))
+    return (V + abs(h) * Sm * av * tn / (2 * L)) + rho * V * tn / L
+
+
+def certify_lipschitz_quad(xk):
+    """Lambda of one quadcopter interval: |v_k|, the Euclidean norm of xk[6:9]"""
+    return float(np.sqrt((xk[6] * xk[6] + xk[7] * xk[7]) + xk[8] * xk[8]))
+
+
+def _certify_walk(clear, Lh, need, slack, max_steps):
+    """conservative advancement of one (interval, obstacle) item: clear(m) is the clearance at tick m, Lh = Lambda |h|.  Returns (lb, seen, tick of seen, tick of the first
+    violation or G, samples): every sample c proves c - Lh dm / G on the dm ticks it advances by; an item still running after max_steps samples has lb = -inf."""
+    G = CERT_TICKS; m = 0; lb = seen = np.inf; tseen = 0; tviol = G; steps = 0
+    while True:
+        c = float(clear(m)); steps += 1
+        if not np.isfinite(c):
+            return np.nan, np.nan, -1, -1, steps
+        rem = G - m
+        if c < need and tviol == G:
+            tviol = m
+        if c < seen:
+            seen, tseen = c, m
+        e = (c - need) + slack if c >= need else slack
+        if Lh == 0.0 or e >= Lh * rem / G:
+            dm = rem
+        else:
+            f = math.floor(G * e / Lh)
+            dm = min(f, rem) if f >= 1 else 1
+        lb = min(lb, c - Lh * dm / G)
+        m += dm
+        if m == G:
+            return lb, seen, tseen, tviol, steps
+        if steps == max_steps:
+            return -np.inf, seen, tseen, tviol, steps
+
+
+def certify_parking(x, u, timeScale, Ts, L, ego, nOb, dist, need=DMIN, slack=0.01, max_steps=CERT_TICKS):
+    """The item table of a parking trajectory x (4,N+1), u (2,N): items (N+1, nOb, 5) = (lb, seen, tick of seen, tick of the first violation or G, samples) per
+    (interval, obstacle) -- interval N is node N, one sample --, and lam (N,) the Lambda_k.  dist(pose, j): the distance of the car at pose (x, y, yaw) to obstacle j (the
+    oracle's DualMultWS, an exact polygon distance, the host build's own); below CLR_TOUCH it counts as 0.  The pose at tick m of interval k is `_dyn` from node k with u_k
+    over (m / G) timeScale[k] of Ts, the node itself at m = 0."""
+    x = np.asarray(x, float); u = np.asarray(u, float); N = x.shape[1] - 1; ts = _stage_scale(timeScale, N); G = CERT_TICKS
+    items = np.zeros((N + 1, nOb, 5)); lam = np.zeros(N)
+    for k in range(N + 1):
+        Lh = 0.0
+        if k < N:
+            h = ts[k] * Ts
+            lam[k] = certify_lipschitz_parking(x[:, k], u[:, k], h, L, ego); Lh = lam[k] * abs(h)
+        for j in range(nOb):
+            def clear(m, k=k, j=j):
+                pose = _dyn(x[:, k], u[:, k], m / G * ts[k], Ts, L)[:3] if m else x[:3, k]
+                d = dist(pose, j)
+                return 0.0 if d < CLR_TOUCH else d
+            items[k, j] = _certify_walk(clear, Lh, need, slack, max_steps) if np.isfinite(Lh) else (np.nan, np.nan, -1, -1, 0)
+    return items, lam
+
+
+def certify_quad(x, timeScale, Ts, ob, R, need=0.0, slack=0.01, max_steps=CERT_TICKS):
+    """the same for a quadcopter trajectory x (12,N+1): the point at tick m of interval k is p_k + (m / G) timeScale[k] Ts v_k, its clearance to box j (ob (5,6) as [hi; -lo])
+    the Euclidean distance to the box (0 inside) minus R.  Returns items (N+1, 5, 5), lam (N,)."""
+    x = np.asarray(x, float); N = x.shape[1] - 1; ts = _stage_scale(timeScale, N); ob = np.asarray(ob, float).reshape(5, 6); G = CERT_TICKS
+    items = np.zeros((N + 1, 5, 5)); lam = np.zeros(N)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(N + 1):
+            Lh = 0.0
+            if k < N:
+                lam[k] = certify_lipschitz_quad(x[:, k]); Lh = lam[k] * abs(ts[k] * Ts)
+            for j in range(5):
+                def clear(m, k=k, j=j):
+                    pt = x[:3, k] + m / G * ts[k] * Ts * x[6:9, k] if m else x[:3, k]
+                    e = np.maximum(np.maximum(-ob[j, 3:] - pt, pt - ob[j, :3]), 0.0)
+                    return np.sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]) - R
+                items[k, j] = _certify_walk(clear, Lh, need, slack, max_steps) if np.isfinite(Lh) else (np.nan, np.nan, -1, -1, 0)
+    return items, lam
+
+
+def certify_record(items, lam, finite=True):
+    """(record (CERT_OUT,), intervals (N+1, 2)) of an item table: intervals[k] = (the smallest lb, the smallest seen) over the obstacles.  Record: [0] lb, [1] seen, [2-4]
+    interval, tick, obstacle of seen (ties: the smallest interval, then tick, then obstacle), [5] violated = intervals with a sample under need (node N counts as one), [6-8]
+    interval, tick, obstacle of the first violation in that order (-1: none), [9] undecided items, [10] samples taken, [11] most samples of one item, [12] the largest
+    Lambda_k, [13] certified, [14] bad, [15] 0.  Not finite (an input, a clearance or a Lambda_k |h| was not): NaN / -1, violated = N + 1, undecided = the items, counts 0."""
+    items = np.asarray(items, float); N1, nOb, _ = items.shape; G = CERT_TICKS
+    r = np.zeros(CERT_OUT)
+    if not (finite and np.isfinite(lam).all() and not np.isnan(items[:, :, :2]).any()):
+        r[[0, 1, 12]] = np.nan; r[[2, 3, 4, 6, 7, 8]] = -1; r[5] = N1; r[9] = N1 * nOb; r[14] = 1
+        return r, np.full((N1, 2), np.nan)
+    iv = np.stack([items[:, :, 0].min(axis=1), items[:, :, 1].min(axis=1)], axis=1)
+    seen = items[:, :, 1].min()
+    skey = min((k, int(items[k, j, 2]), j) for k in range(N1) for j in range(nOb) if items[k, j, 1] == seen)
+    vkeys = [(k, int(items[k, j, 3]), j) for k in range(N1) for j in range(nOb) if items[k, j, 3] < G]
+    r[0] = iv[:, 0].min(); r[1] = seen; r[2:5] = skey
+    r[5] = len({k for k, _, _ in vkeys}); r[6:9] = min(vkeys) if vkeys else (-1, -1, -1)
+    r[9] = int((items[:, :, 0] == -np.inf).sum()); r[10] = items[:, :, 4].sum(); r[11] = items[:, :, 4].max(); r[12] = max(0.0, float(np.max(lam))) if len(lam) else 0.0
+    r[13] = 1.0 if r[5] == 0 and r[9] == 0 else 0.0
+    return r, iv
