@@ -1513,6 +1513,18 @@ int obca_oracle_parking_signed_dist_full(int N, double Ts, double L, const doubl
     g_zfull = NULL;
     return rc;
 }
+/* ParkingDist with the full iterate: zs1 holds the multipliers of the norm-row slacks' bounds */
+int obca_oracle_parking_dist_full(int N, double Ts, double L, const double ego[4], const double XYb[4], int fixTime,
+                                  const double *x0, const double *xF, int nOb, const int *vOb, const double *A,
+                                  const double *b, const double *rx, const double *ry, const double *ryaw,
+                                  const double *xWS, const double *uWS, const double *lWS, const double *nWS,
+                                  const opts_t *opt, double *xp, double *up, double *tsp, double *lp, double *np,
+                                  double *slp, int *exitflag, double *info, double *zfull) {
+    g_zfull = zfull;
+    int rc = parking_solve(1, N, Ts, L, ego, XYb, fixTime, x0, xF, nOb, vOb, A, b, rx, ry, ryaw, xWS, uWS, lWS, nWS, opt, xp, up, tsp, lp, np, slp, exitflag, info);
+    g_zfull = NULL;
+    return rc;
+}
 int obca_oracle_parking_signed_dist(int N, double Ts, double L, const double ego[4], const double XYb[4], int fixTime,
                                     const double *x0, const double *xF, int nOb, const int *vOb, const double *A,
                                     const double *b, const double *rx, const double *ry, const double *ryaw,

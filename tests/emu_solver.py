@@ -60,7 +60,7 @@ def parking_signed_dist_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, rx, ry
         eo.max_iter = int(max_iter)
     Tsv = np.broadcast_to(np.asarray(Ts, float), (B,))
     xp = np.zeros((B, 4, N + 1)); up = np.zeros((B, 2, N)); ts = np.zeros((B, N + 1)); ef = np.zeros(B, np.int32); info = np.zeros((B, 8))
-    lps, nps, sls = [], [], []
+    lps, nps, sls, zs, lws = [], [], [], [], []
     for i in range(B):
         rxi, ryi, rwi = np.ravel(rx[i])[:N + 1], np.ravel(ry[i])[:N + 1], np.ravel(ryaw[i])[:N + 1]
         lWS = np.zeros((N + 1, M)); nWS = np.zeros((N + 1, 4 * nOb))
@@ -78,8 +78,9 @@ def parking_signed_dist_batch(x0, xF, N, Ts, L, ego, XYbounds, vOb, A, b, rx, ry
         emu.emu_solve(C.c_int(N), dp(prob), dp(z0), C.c_int(Lz["len"]), C.byref(eo), dp(zo), dp(info[i]))
         acc_ = C.c_int(0); nsoc[i, 0] = emu.emu_last_soc(C.byref(acc_)); nsoc[i, 1] = acc_.value; nsoc[i, 2] = emu.emu_last_recalc()
         x_, u_, t_, lp_, np_, sl_ = P.unpack_solution(zo, N, nOb, M, A=A)
-        xp[i] = x_; up[i] = u_; ts[i] = 1.0 if fixTime else t_; ef[i] = int(info[i, 7]); lps.append(lp_); nps.append(np_); sls.append(sl_)
-    return dict(xp=xp, up=up, timeScale=ts, exitflag=ef, lp=lps, np=nps, sl=sls, info=info, iters=info[:, 1].astype(int), obj=info[:, 2], status=info[:, 0].astype(int), nsoc=nsoc)
+        xp[i] = x_; up[i] = u_; ts[i] = 1.0 if fixTime else t_; ef[i] = int(info[i, 7]); lps.append(lp_); nps.append(np_); sls.append(sl_); zs.append(zo); lws.append(lWS)
+    return dict(xp=xp, up=up, timeScale=ts, exitflag=ef, lp=lps, np=nps, sl=sls, info=info, iters=info[:, 1].astype(int), obj=info[:, 2], status=info[:, 0].astype(int), nsoc=nsoc,
+                z=zs, lWS=lws)      # the full primal-dual iterates (packing.layout; lambda of unit rows) and the DualMultWS starts they began from
 
 
 def quadcopter_signed_dist_batch(x0, xF, N, Ts, R, ob, xWS, timeWS, dual_ws=True, dist=False, max_soc=0, lsq_init=0, obj_scaling=0, max_iter=3000, **_):
@@ -87,12 +88,13 @@ def quadcopter_signed_dist_batch(x0, xF, N, Ts, R, ob, xWS, timeWS, dual_ws=True
     emu = load()
     x0 = np.reshape(x0, (-1, 12)); B = x0.shape[0]; xF = np.reshape(xF, (-1, 12)); L = P.quad_layout(N); N1 = N + 1
     Tsv = np.broadcast_to(np.asarray(Ts, float), (B,)); tw = np.broadcast_to(np.asarray(timeWS, float), (B,))
-    xp = np.zeros((B, 12, N1)); up = np.zeros((B, 4, N)); ts = np.zeros((B, N1)); ef = np.zeros(B, np.int32); info = np.zeros((B, 8)); lp = np.zeros((B, 30, N1)); sl = np.zeros((B, 5, N1))
+    xp = np.zeros((B, 12, N1)); up = np.zeros((B, 4, N)); ts = np.zeros((B, N1)); ef = np.zeros(B, np.int32); info = np.zeros((B, 8)); lp = np.zeros((B, 30, N1)); sl = np.zeros((B, 5, N1)); zs = []
     eo = default_opts(); eo.max_iter = int(max_iter); eo.dw_min = 1e-10; eo.max_soc = int(max_soc); eo.lsq_init = int(lsq_init); eo.obj_scaling = int(obj_scaling)            # QuadcopterSignedDist.jl:28-31 (obca_quadcopter_default_opts)
     for i in range(B):
         prob = P.pack_quad_problem(x0[i], xF[i], N, Tsv[i], R, ob, np.asarray(xWS[i], float).reshape(N1, 12), tw[i], dual_ws=int(bool(dual_ws)), dist=int(bool(dist)))
         z = np.zeros(L["len"])
         emu.emu_quad_solve(C.c_int(N), dp(prob), C.byref(eo), dp(z), dp(info[i]))
         xp[i] = z[L["x"]:L["u"]].reshape(N1, 12).T; up[i] = z[L["u"]:L["t"]].reshape(N, 4).T; ts[i] = z[L["t"]]; ef[i] = int(info[i, 7])
-        lp[i] = z[L["lam"]:L["s"]].reshape(N1, 30).T; sl[i] = z[L["s"]:L["so"]].reshape(N1, 5).T
-    return dict(xp=xp, up=up, timeScale=ts, exitflag=ef, lp=lp, slack=sl, info=info, iters=info[:, 1].astype(int), obj=info[:, 2], status=info[:, 0].astype(int))
+        lp[i] = z[L["lam"]:L["s"]].reshape(N1, 30).T; sl[i] = z[L["s"]:L["so"]].reshape(N1, 5).T; zs.append(z)
+    return dict(xp=xp, up=up, timeScale=ts, exitflag=ef, lp=lp, slack=sl, info=info, iters=info[:, 1].astype(int), obj=info[:, 2], status=info[:, 0].astype(int),
+                z=zs)      # the full primal-dual iterates v | y | zL | zU (packing.quad_layout)

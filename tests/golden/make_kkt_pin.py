@@ -23,34 +23,10 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 OUT = os.path.dirname(os.path.abspath(__file__))
 
-
-def certificate(nlp, v, y, zL, zU):
-    """v, y: primal point and equality multipliers in the ordering of `nlp`; zL, zU: bound multipliers per variable (0 where there is no bound),
-    already multiplied by the bound's multiplicity (timeScale stands for N+1 copies)"""
-    import torch
-    g = torch.autograd.functional.jacobian(nlp.f, torch.tensor(v)).numpy()
-    cval = nlp.c(torch.tensor(v)).numpy()
-    J = torch.autograd.functional.jacobian(nlp.c, torch.tensor(v), vectorize=True).numpy()
-    lb, ub = nlp.lb, nlp.ub; n = len(v); mult = getattr(nlp, "mult", np.ones(n))
-    r = g + J.T @ y - zL + zU
-    hasL = np.isfinite(lb) & (ub > lb); hasU = np.isfinite(ub) & (ub > lb)
-    dL = np.where(hasL, v - lb, np.inf); dU = np.where(hasU, ub - v, np.inf)
-    compl = max(np.where(hasL, zL * dL / mult, 0).max(), np.where(hasU, zU * dU / mult, 0).max())
-    act = np.flatnonzero((hasL & (zL / mult > dL)) | (hasU & (zU / mult > dU)))
-    yt = torch.tensor(y)
-    H = torch.autograd.functional.hessian(lambda w: nlp.f(w) + (yt * nlp.c(w)).sum(), torch.tensor(v), vectorize=True).numpy()
-    Ea = np.zeros((len(act), n)); Ea[np.arange(len(act)), act] = 1.0
-    Jall = np.vstack([J, Ea])
-    U, s, Vt = np.linalg.svd(Jall, full_matrices=True)
-    rank = int((s > 1e-9 * s[0]).sum())
-    Z = Vt[rank:].T
-    ev = np.linalg.eigvalsh(Z.T @ H @ Z)
-    return dict(obj=float(nlp.f(torch.tensor(v)).item()), cviol=float(np.abs(cval).max()), kkt=float(np.abs(r).max()), y_inf=float(np.abs(y).max()),
-                z_min=float(min(zL[hasL].min(), zU[hasU].min() if hasU.any() else np.inf)), compl_max=float(compl), bound_viol=float(max((-dL[hasL]).max(), (-dU[hasU]).max() if hasU.any() else -1)),
-                n=n, m=int(J.shape[0]), n_active=int(len(act)), rank=rank, redhess_min=float(ev.min()), redhess_max=float(ev.max()))
+from kkt_certificate import certificate, parking_point, quad_point      # noqa: E402 -- tests/kkt_certificate.py: the certificate and the layout maps, stated once
 
 
 def parking_job(args):
@@ -62,19 +38,8 @@ def parking_job(args):
     t0 = time.time()
     r = O.parking_signed_dist(x0, xF, N, Ts, L, ego, XYb, v, A, b, xWS[:, 0], xWS[:, 1], xWS[:, 2], 0, xWS, uWS, full=True)
     assert r["exitflag"] == 1
-    z = r["zfull"]; Lz = O.layout(N, v); nOb = len(np.ravel(v)); M = int(np.sum(v)); N1 = N + 1
     nlp = ParkingNLP(x0, xF, N, Ts, L, ego, XYb, v, A, b, xWS[:, 0], xWS[:, 1], xWS[:, 2])
-    vs = np.zeros(nlp.n); zL = np.zeros(nlp.n); zU = np.zeros(nlp.n)
-    seg = lambda k, cnt: z[Lz[k]:Lz[k] + cnt]
-    vs[nlp.ix] = seg("x", 4 * N1)[4:]; vs[nlp.it] = z[Lz["t"]]; vs[nlp.iu] = seg("u", 2 * N); vs[nlp.il] = seg("lam", M * N1); vs[nlp.im] = seg("mu", 4 * nOb * N1)
-    vs[nlp.isl] = seg("sl", nOb * N1); vs[nlp.iss] = seg("ss", N); vs[nlp.iso] = seg("so", nOb * N1)
-    zL[nlp.ix] = seg("zxL", 4 * N1)[4:]; zU[nlp.ix] = seg("zxU", 4 * N1)[4:]
-    zL[nlp.ix][2::4] = 0; zU[nlp.ix][2::4] = 0                                   # psi is unbounded
-    zxl = zL[nlp.ix].copy(); zxl[2::4] = 0; zL[nlp.ix] = zxl; zxu = zU[nlp.ix].copy(); zxu[2::4] = 0; zU[nlp.ix] = zxu
-    zL[nlp.it] = (N + 1) * z[Lz["ztL"]]; zU[nlp.it] = (N + 1) * z[Lz["ztU"]]        # N+1 copies of the timeScale bounds
-    zL[nlp.iu] = seg("zuL", 2 * N); zU[nlp.iu] = seg("zuU", 2 * N); zL[nlp.il] = seg("zlam", M * N1); zL[nlp.im] = seg("zmu", 4 * nOb * N1)
-    zL[nlp.iss] = seg("zssL", N); zU[nlp.iss] = seg("zssU", N); zL[nlp.iso] = seg("zso", nOb * N1)
-    y = np.concatenate([seg("pi", 4 * N), seg("nu", 4), seg("yg", N), seg("yo", 4 * nOb * N1)])
+    vs, y, zL, zU = parking_point(r["zfull"], N, v, nlp, 0)
     c = certificate(nlp, vs, y, zL, zU)
     print(tag, i, {k: (float("%.3g" % v_) if isinstance(v_, float) else v_) for k, v_ in c.items()}, "oracle obj", r["obj"], "iters", r["iters"], "mu", r["mu"], "%.0fs" % (time.time() - t0), flush=True)
     return dict(tag=tag, idx=i, x0=x0, xF=xF, Ts=Ts, xWS=xWS, uWS=uWS, xp=r["xp"], up=r["up"], t=r["t"], lp=r["lp"], np_=r["np"], sl=r["sl"], oracle_obj=r["obj"], iters=r["iters"], **c)
@@ -90,12 +55,8 @@ def quad_job(args):
     r = Q.quadcopter_signed_dist_full(x0, xF, N, Ts, R, ob, xWS, 1.0)
     assert r["exitflag"] == 1
     nlp = QuadNLP(x0, xF, N, Ts, R, ob)
-    # the oracle's v is x (12 (N+1), x_0 first) | u | t | lam | s | so; nlp_ref_quad drops x_0
-    keep = np.arange(12, len(r["v"]))
-    vs = r["v"][keep]; zL = r["zL"][keep].copy(); zU = r["zU"][keep].copy()
-    zL[nlp.it] *= (N + 1); zU[nlp.it] *= (N + 1)                         # N+1 copies of the timeScale bounds
-    zL[~np.isfinite(nlp.lb)] = 0; zU[~np.isfinite(nlp.ub)] = 0
-    c = certificate(nlp, vs, r["y"], zL, zU)
+    vs, y, zL, zU = quad_point(r["full"], N, nlp)      # the oracle's v | y | zL | zU is the layout of packing.quad_layout
+    c = certificate(nlp, vs, y, zL, zU)
     print("quad", i, {k: (float("%.3g" % v_) if isinstance(v_, float) else v_) for k, v_ in c.items()}, "oracle obj", r["obj"], "iters", r["iters"], "%.0fs" % (time.time() - t0), flush=True)
     return dict(tag="quad", idx=i, x0=x0, xF=xF, Ts=Ts, xWS=xWS, xp=r["xp"], up=r["up"], t=r["t"], lp=r["lp"], slack=r["slack"], oracle_obj=r["obj"], iters=r["iters"], R=R, ob=ob, **c)
 

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 from obca_amd import scenarios as S
 import packing as P
+from kkt_certificate import direction_obstacles
 
 D = C.POINTER(C.c_double)
 dp = lambda a: a.ctypes.data_as(D)
@@ -34,11 +35,14 @@ def test_layouts_agree(oracle):
 import pytest
 
 
-@pytest.mark.parametrize("dist", [0, 1], ids=["signed_dist", "dist"])
-def test_emu_newton_direction_matches_oracle(oracle, emu, backwards, dist):
+@pytest.mark.parametrize("dist,case", [pytest.param(d, c, id=("dist" if d else "signed_dist") + ("" if c == "shipped" else "-" + c))
+                                       for c in ("shipped", "rows_5_to_8", "16_obstacles") for d in (0, 1)])
+def test_emu_newton_direction_matches_oracle(oracle, emu, dist, case):
+    """(obstacle sets of kkt_certificate.direction_obstacles: one per instantiation of the obstacle block, 2-row / 5-8-row / sixteen 3-4-row obstacles -- up to 160 block
+    items at N = 9; tests/test_oracle_cpu.py holds both sides against the dense autograd system on the same sets)"""
     rng = np.random.default_rng(3)
     for N in (2, 3, 9):
-        sc = S.BACKWARDS; A, b, v = backwards["A"], backwards["b"], backwards["vOb"]; nOb = len(v); M = int(v.sum())
+        sc = S.BACKWARDS; v, A, b = direction_obstacles(case); nOb = len(v); M = int(v.sum())
         x0 = np.array([-5, 9.0, -0.1, 0.]); Ts, xWS, uWS = S.warm_start_backwards(x0, sc["xF"], N); Ts = 0.7
         L = P.layout(N, nOb, M)
         z = np.zeros(L["len"])

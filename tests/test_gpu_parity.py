@@ -597,6 +597,42 @@ def test_hip_reproduces_the_independently_certified_solutions(OA):
         assert np.abs(out["up"][i] - r["up"]).max() < 1e-5 and abs(out["timeScale"][i, 0] - r["t"]) < 1e-8 and np.abs(out["xp"][i] - r["xp"]).max() < 1e-3
 
 
+def test_hip_reproduces_the_certified_solutions_of_the_kernel_text(OA):
+    """tests/golden/kkt_classes.npz: the final iterates of the host build of the kernel text at N = 20, certified with independent (autograd) derivatives by
+    tests/test_kkt_classes_cpu.py -- ParkingSignedDist and ParkingDist, obstacles of up to 7 rows, both option sets, solves in which the block restoration fired.  The HIP path
+    must return the same arrays without the oracle at run time: records grouped by formulation and option set into ragged batches, exit flag, iteration count and the point
+    (TOL_X / TOL_F).  For the restoration records the iteration count is printed, not asserted, and the solve with restoration = 0 must be another run, longer or shorter as
+    the fixture says."""
+    import kkt_classes_common as K
+    recs = [r for r in golden("kkt_classes.npz")["records"] if not K.is_quad(r)]
+    groups = {}
+    for r in recs:
+        groups.setdefault((r["dist"], r["ref"], r["restoration"]), []).append(r)
+    assert len(recs) == 15 and max(len(g) for g in groups.values()) <= 8
+    lines = []
+    for (dist, ref, rest), rs in sorted(groups.items()):
+        bt = dict(x0=np.stack([r["x0"] for r in rs]), xF=np.stack([r["xF"] for r in rs]), Ts=np.array([float(r["Ts"]) for r in rs]), xWS=np.stack([r["xWS"] for r in rs]),
+                  uWS=np.stack([r["uWS"] for r in rs]), A=[r["A"] for r in rs], b=[r["b"] for r in rs], vOb=[r["vOb"] for r in rs], N=K.N, L=S.L_WHEELBASE, ego=S.EGO, XYbounds=S.XYBOUNDS)
+        o = OA.ipopt_opts() if ref else OA.default_opts(); o.restoration = rest
+        out, _ = _solve_batch(OA, bt, opts=o, dist=bool(dist))
+        if rest:
+            o0 = OA.ipopt_opts(); o0.restoration = 0
+            out0, _ = _solve_batch(OA, bt, opts=o0, dist=bool(dist))
+        for i, r in enumerate(rs):
+            tag = K.name(r); fired = r["tag"] == "corridor"
+            dx = max(np.abs(out["xp"][i] - r["xp"]).max(), np.abs(out["up"][i] - r["up"]).max()); df = abs(out["obj"][i] - r["solver_obj"]) / max(1, abs(r["solver_obj"]))
+            lines.append("%s: exit flag %d, %d iterations (fixture %d), largest deviation of states / inputs %.1e, objective %.1e relative%s"
+                         % (tag, out["exitflag"][i], out["iters"][i], r["iters"], dx, df, ", %d iterations with restoration = 0 (fixture %d)" % (out0["iters"][i], r["rest0_iters"]) if fired else ""))
+            print(lines[-1])
+            assert out["exitflag"][i] == r["exitflag"] == 1, tag
+            if fired:
+                assert out0["iters"][i] != out["iters"][i] and (out0["iters"][i] > out["iters"][i]) == (r["rest0_iters"] > r["iters"]), tag
+            else:
+                assert out["iters"][i] == r["iters"], tag
+            assert df <= TOL_F and dx < TOL_X and abs(out["timeScale"][i, 0] - r["t"]) < 1e-9, tag
+    _census("kkt_classes_parking", "\n".join(lines))
+
+
 @pytest.mark.timeout(900)
 def test_every_instance_of_the_config5_bench_batch_matches_oracle(OA):
     """BASELINE config 5 at size -- rank 0's batch of `bench.py --config 5`: 4 096 instances with 1-10 obstacles of 1-4 rows each (per-instance H-rep packing, the three
@@ -972,17 +1008,22 @@ def _first_iterate_cases(N):
         i16 = [i for i, v in enumerate(bt["vOb"]) if len(v) == 16][:1]
         assert i16, N
         cases.append(_sub(dict(bt, N=N), i16))
+    if N == 20:      # obstacles of 5-8 rows: the widest instantiation of the obstacle block (the instance of tests/golden/kkt_classes.npz)
+        bt = S.make_mixed_batch(24, N, seed=11, rows=(5, 8), max_extra=4)
+        assert np.ravel(bt["vOb"][3]).tolist() == [2, 2, 1, 5, 6, 7, 7]
+        cases.append(_sub(dict(bt, N=N), [3]))
     return cases
 
 
 _WORST_FIRST = {}
 
 
-@pytest.mark.parametrize("N", [3, 64, 65, 127, 128])
+@pytest.mark.parametrize("N", [3, 20, 64, 65, 127, 128])
 def test_parking_first_iterates_match_the_oracle_tightly(OA, oracle, N):
     """max_iter = k (k = 0 .. 5): both attempts stop after k iterations and the retry resumes from the last iterate, so the point handed back is the start (k = 0) or the
     iterate after 2k Newton steps -- where a slightly wrong direction shows before the interior point corrects it.  Every returned quantity against the oracle run with the
-    same options, relative to max(1, |oracle|): 1e-9 (the host emulation of the same source agrees to a few 1e-12); the regularisation count exactly."""
+    same options, relative to max(1, |oracle|): 1e-9 (the host emulation of the same source agrees to a few 1e-12); the regularisation count exactly.  The cases reach every
+    instantiation of the obstacle block: 2-row obstacles at every N, sixteen 3-4-row obstacles at N = 64 / 65, rows 2, 2, 1, 5, 6, 7, 7 at N = 20."""
     worst = {}
     for dist in (0, 1):
         for ref in (0, 1):

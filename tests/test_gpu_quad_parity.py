@@ -148,6 +148,34 @@ def test_quad_matches_golden_fixture_config4():
     assert (out["iters"] == g["iters"]).sum() >= B - 1        # round-off may flip one inertia test
 
 
+def test_quad_hip_reproduces_the_certified_solutions_of_the_kernel_text():
+    """tests/golden/kkt_classes.npz: the final iterates of the host build of the quadcopter kernel text at N = 20 -- QuadcopterSignedDist and QuadcopterDist, throughput options
+    and the reference options (obj_scaling: multipliers of sigma f) -- certified with independent (autograd) derivatives by tests/test_kkt_classes_cpu.py.  The HIP path must
+    return the same arrays without the oracle at run time: one batch per formulation and option set, exit flag, iteration count, and the point within the tolerances of
+    test_hip_reproduces_the_independently_certified_solutions"""
+    import obca_amd
+    import kkt_classes_common as K
+    from conftest import golden
+    recs = [r for r in golden("kkt_classes.npz")["records"] if K.is_quad(r)]
+    assert len(recs) == 8
+    lines = []
+    for dist in (0, 1):
+        for ref in (0, 1):
+            rs = [r for r in recs if (r["dist"], r["ref"]) == (dist, ref)]
+            assert len(rs) == 2 and len({(float(r["Ts"]), float(r["R"])) for r in rs}) == 1 and np.array_equal(rs[0]["ob"], rs[1]["ob"])
+            o = obca_amd.quadcopter_ipopt_opts() if ref else obca_amd.quadcopter_default_opts()
+            out = obca_amd.quadcopter_signed_dist_batch(np.stack([r["x0"] for r in rs]), np.stack([r["xF"] for r in rs]), K.N, float(rs[0]["Ts"]), float(rs[0]["R"]), rs[0]["ob"],
+                                                        np.stack([r["xWS"] for r in rs]), np.ones(len(rs)), opts=o, dist=bool(dist))
+            for i, r in enumerate(rs):
+                tag = K.name(r); dx = np.abs(out["xp"][i] - r["xp"]).max(); du = np.abs(out["up"][i] - r["up"]).max(); df = abs(out["obj"][i] - r["solver_obj"]) / abs(r["solver_obj"])
+                lines.append("%s: exit flag %d, %d iterations (fixture %d), largest deviation of the states %.1e, inputs %.1e, time scale %.1e, objective %.1e relative"
+                             % (tag, out["exitflag"][i], out["iters"][i], r["iters"], dx, du, abs(out["timeScale"][i, 0] - r["t"]), df))
+                print(lines[-1])
+                assert out["exitflag"][i] == r["exitflag"] == 1 and out["iters"][i] == r["iters"], tag
+                assert df <= 1e-8 and du < 1e-5 and abs(out["timeScale"][i, 0] - r["t"]) < 1e-8 and dx < 1e-3, tag
+    _census("kkt_classes_quad", "\n".join(lines))
+
+
 @pytest.mark.timeout(900)
 def test_all_1024_quadcopter_bench_instances_match_oracle(Q):
     """every instance of the config-4 bench batch (N = 60, random end points, A* warm starts) against the oracle run on all host cores: exit flags equal everywhere;

@@ -1,7 +1,11 @@
 """CPU tests of the oracle: known answers, golden fixtures, derivative / linear-algebra cross-checks (no GPU)."""
+import ctypes as C
+import types
 import numpy as np
 import pytest
+import packing as P
 from conftest import golden
+from kkt_certificate import DIRECTION_CASES, direction_obstacles, parking_point
 from obca_amd import scenarios as S
 
 
@@ -116,137 +120,169 @@ def test_oracle_config3_parallel_parking_golden_and_reference_checker(oracle):
         assert r["sl"].max() < 0.02                                            # penetration below 2 cm: the bay is 1.3 m longer than the car
 
 
-@pytest.mark.parametrize("dist", [0, 1], ids=["signed_dist", "dist"])
-def test_newton_direction_vs_dense_autograd(oracle, emu, backwards, dist):
-    """closed-form derivatives + condensation + Riccati + border == dense solve of the autograd KKT system
-    (both formulations: ParkingSignedDist and the next-1 sibling ParkingDist)"""
-    torch = pytest.importorskip("torch")
-    from nlp_ref import ParkingNLP
-    rng = np.random.default_rng(1)
-    N = 4; sc = S.BACKWARDS; A, b, v = backwards["A"], backwards["b"], backwards["vOb"]; nOb = len(v); M = int(v.sum())
+# ---------------------------------------------------------------- directions of every obstacle-block class against the dense autograd KKT system
+# (formulation, obstacle set of kkt_certificate.direction_obstacles); the shipped scenario keeps the ids it always had
+_DIRECTION_PARAMS = [pytest.param(d, c, id=("dist" if d else "signed_dist") + ("" if c == "shipped" else "-" + c)) for c in DIRECTION_CASES for d in (0, 1)]
+_DX, _DY, _DLSQ = 1e-9, 1e-8, 1e-9      # relative bounds on the primal part, the multiplier part, the least-squares multipliers
+D_ = C.POINTER(C.c_double)
+_dp = lambda a: a.ctypes.data_as(D_)
+
+
+def _direction_problem(case, dist, N, seed):
+    """a random interior primal-dual point, far from a solution, of the backwards scenario's start with the obstacle set `case` (rng draws in the order the shipped case always had)"""
+    rng = np.random.default_rng(seed)
+    v, A, b = direction_obstacles(case); nOb = len(v); M = int(v.sum()); sc = S.BACKWARDS
     x0 = np.array([-6, 9.5, 0.1, 0.]); Ts, xWS, uWS = S.warm_start_backwards(x0, sc["xF"], N); Ts = 0.6
-    nlp = ParkingNLP(x0, sc["xF"], N, Ts, S.L_WHEELBASE, S.EGO, S.XYBOUNDS, v, A, b, xWS[:, 0], xWS[:, 1], xWS[:, 2], dist=dist)
-    L = oracle.layout(N, v)
+    L = P.layout(N, nOb, M)
     z = np.zeros(L["len"])
     X = xWS.copy(); X[1:] += 0.05 * rng.standard_normal((N, 4)); X[0] = x0
     z[L["x"]:L["x"] + 4 * (N + 1)] = X.reshape(-1)
     z[L["u"]:L["u"] + 2 * N] = np.clip(uWS + 0.05 * rng.standard_normal((N, 2)), -0.3, 0.3).reshape(-1)
     z[L["t"]] = 1.05
     for k, lo, hi in (("lam", 0.1, 1), ("mu", 0.1, 1), ("so", 0.1, 1), ("ss", -0.3, 0.3)):
-        n = L[oracle.LAYOUT_FIELDS[oracle.LAYOUT_FIELDS.index(k) + 1]] - L[k]
+        n = L[P.LAYOUT_FIELDS[P.LAYOUT_FIELDS.index(k) + 1]] - L[k]
         z[L[k]:L[k] + n] = rng.uniform(lo, hi, n)
     z[L["sl"]:L["so"]] = rng.uniform(0.1, 1, L["so"] - L["sl"]) if dist else 0.01 * rng.standard_normal(L["so"] - L["sl"])
     z[L["pi"]:L["zxL"]] = rng.standard_normal(L["zxL"] - L["pi"])
     z[L["zxL"]:] = rng.uniform(0.1, 2, L["len"] - L["zxL"])
-    mu, dw, dc = 0.1, 3.0, 1e-6
-    ok, d, errs = oracle.newton(N, Ts, S.L_WHEELBASE, S.EGO, S.XYBOUNDS, 0, x0, sc["xF"], v, A, b, xWS[:, 0], xWS[:, 1], xWS[:, 2], z, mu, dw, dc, dist=dist)
-    assert ok == 1
+    geo = (N, Ts, S.L_WHEELBASE, S.EGO, S.XYBOUNDS, 0, x0, sc["xF"], v, A, b, xWS[:, 0], xWS[:, 1], xWS[:, 2])      # the argument list of the oracle's hooks
+    return types.SimpleNamespace(case=case, dist=dist, N=N, rng=rng, v=v, A=A, b=b, nOb=nOb, M=M, x0=x0, xF=sc["xF"], Ts=Ts, xWS=xWS, L=L, z=z, geo=geo,
+                                 emu=not case.endswith("as_emitted"))      # (the host build packs unit rows: its lambda is the iterate's only for those)
 
-    def to_ref(w):
-        vv = np.zeros(nlp.n)
-        vv[nlp.ix] = w[L["x"] + 4:L["x"] + 4 * (N + 1)]; vv[nlp.it] = w[L["t"]]; vv[nlp.iu] = w[L["u"]:L["u"] + 2 * N]
-        vv[nlp.il] = w[L["lam"]:L["lam"] + M * (N + 1)]; vv[nlp.im] = w[L["mu"]:L["mu"] + 4 * nOb * (N + 1)]
-        vv[nlp.isl] = w[L["sl"]:L["sl"] + nOb * (N + 1)]; vv[nlp.iss] = w[L["ss"]:L["ss"] + N]; vv[nlp.iso] = w[L["so"]:L["so"] + nOb * (N + 1)]
-        return vv
-    ym = lambda w: np.concatenate([w[L["pi"]:L["pi"] + 4 * N], w[L["nu"]:L["nu"] + 4], w[L["yg"]:L["yg"] + N], w[L["yo"]:L["yo"] + 4 * nOb * (N + 1)]])
-    vv, y = to_ref(z), ym(z)
-    f, g, c, J, H = nlp.eval_all(vv, y)
-    n, m = nlp.n, nlp.m
-    zL = np.zeros(n); zU = np.zeros(n)
-    zL[nlp.ix] = z[L["zxL"]:L["zxL"] + 4 * (N + 1)].reshape(N + 1, 4)[1:].reshape(-1)
-    zU[nlp.ix] = z[L["zxU"]:L["zxU"] + 4 * (N + 1)].reshape(N + 1, 4)[1:].reshape(-1)
-    zL[nlp.it] = z[L["ztL"]]; zU[nlp.it] = z[L["ztU"]]
-    zL[nlp.iu] = z[L["zuL"]:L["zuL"] + 2 * N]; zU[nlp.iu] = z[L["zuU"]:L["zuU"] + 2 * N]
-    zL[nlp.il] = z[L["zlam"]:L["zlam"] + M * (N + 1)]; zL[nlp.im] = z[L["zmu"]:L["zmu"] + 4 * nOb * (N + 1)]
-    zL[nlp.iso] = z[L["zso"]:L["zso"] + nOb * (N + 1)]
-    zL[nlp.isl] = z[L["zs1"]:L["zs1"] + nOb * (N + 1)]              # only bounded (hence used) in the ParkingDist formulation
-    zL[nlp.iss] = z[L["zssL"]:L["zssL"] + N]; zU[nlp.iss] = z[L["zssU"]:L["zssU"] + N]
-    IL = np.isfinite(nlp.lb); IU = np.isfinite(nlp.ub); zL[~IL] = 0; zU[~IU] = 0
+
+def _dense_parts(q, A=None, hessian=True):
+    """the flat restatement at q.z with autograd derivatives (obstacle rows A instead of q.A for the mutation checks): nlp, the maps of iterates / directions to its
+    variable and row order, (v, y, zL, zU) with the time scale's multipliers per copy, and f, g, c, J, H"""
+    from nlp_ref import ParkingNLP
+    xWS = q.xWS
+    nlp = ParkingNLP(q.x0, q.xF, q.N, q.Ts, S.L_WHEELBASE, S.EGO, S.XYBOUNDS, q.v, q.A if A is None else A, q.b, xWS[:, 0], xWS[:, 1], xWS[:, 2], dist=q.dist)
+    point = lambda w: parking_point(w, q.N, q.v, nlp, q.dist, multiplicity=False)
+    vv, y, zL, zU = point(q.z)
+    import torch
+    vt, yt = torch.tensor(vv), torch.tensor(y); F = torch.autograd.functional      # (vectorised: the 16-obstacle set has 900 variables)
+    H = F.hessian(lambda w: nlp.f(w) + (yt * nlp.c(w)).sum(), vt, vectorize=True).numpy() if hessian else None
+    d = (nlp.f(vt).item(), F.jacobian(nlp.f, vt).numpy(), nlp.c(vt).numpy(), F.jacobian(nlp.c, vt, vectorize=True).numpy(), H)
+    return nlp, (lambda w: point(w)[0]), (lambda w: point(w)[1]), vv, y, zL, zU, d
+
+
+def _newton_system(q, nlp, vv, y, zL, zU, g, c, J, H, mu, dw, dc):
+    """the regularised primal-dual system of Waechter & Biegler (13) at q.z, dense: matrix, right-hand-side gradient part"""
+    N, nOb = q.N, q.nOb
+    IL = np.isfinite(nlp.lb); IU = np.isfinite(nlp.ub)
     dL = np.where(IL, vv - nlp.lb, 1.0); dU = np.where(IU, nlp.ub - vv, 1.0)
     Sig = nlp.mult * (np.where(IL, zL / dL, 0) + np.where(IU, zU / dU, 0))
     gphi = g - mu * nlp.mult * np.where(IL, 1 / dL, 0) + mu * nlp.mult * np.where(IU, 1 / dU, 0)
     dcv = np.concatenate([np.zeros(4 * N + 4), dc * np.ones(N + 4 * nOb * (N + 1))])   # delta_c only on steering/obstacle rows
-    K = np.block([[H + np.diag(Sig + dw), J.T], [J, -np.diag(dcv)]])
-    sol = np.linalg.solve(K, -np.concatenate([gphi + J.T @ y, c]))
+    return np.block([[H + np.diag(Sig + dw), J.T], [J, -np.diag(dcv)]]), gphi + J.T @ y
+
+
+def _emu_newton(emu, q, mu, dw, dc, csoc=None):
+    prob = P.pack_problem(q.x0, q.xF, q.N, q.Ts, S.L_WHEELBASE, S.EGO, S.XYBOUNDS, q.v, q.A, q.b, q.xWS[:, 0], q.xWS[:, 1], q.xWS[:, 2], 0, dist=q.dist)
+    d = np.zeros_like(q.z); head = (C.c_int(q.N), _dp(prob), _dp(q.z), C.c_int(q.L["len"]), C.c_double(mu), C.c_double(dw), C.c_double(dc), C.c_double(1e3), C.c_double(0.99))
+    if csoc is None:
+        aux = np.zeros(10)
+        return emu.emu_newton(*head, _dp(d), _dp(aux)), d
+    return emu.emu_newton_soc(*head, _dp(csoc), _dp(d)), d
+
+
+@pytest.mark.parametrize("dist,case", _DIRECTION_PARAMS)
+def test_newton_direction_vs_dense_autograd(oracle, emu, dist, case):
+    """closed-form derivatives + condensation + Riccati + border == dense solve of the autograd KKT system
+    (both formulations: ParkingSignedDist and the next-1 sibling ParkingDist), for the oracle AND the kernels' phases (host build), on an obstacle set of every
+    instantiation of the obstacle block: 2-row, 3-4-row (two lane rounds of block items) and 5-8-row obstacles"""
+    pytest.importorskip("torch")
+    q = _direction_problem(case, dist, 4, 1); z, L, rng = q.z, q.L, q.rng
+    mu, dw, dc = 0.1, 3.0, 1e-6
+    ok, d, errs = oracle.newton(*q.geo, z, mu, dw, dc, dist=dist)
+    assert ok == 1
+    nlp, to_ref, ym, vv, y, zL, zU, (f, g, c, J, H) = _dense_parts(q)
+    n, m = nlp.n, nlp.m
+    K, rhs = _newton_system(q, nlp, vv, y, zL, zU, g, c, J, H, mu, dw, dc)
+    sol = np.linalg.solve(K, -np.concatenate([rhs, c]))
     ev = np.linalg.eigvalsh(K)
     assert (ev > 0).sum() == n and (ev < 0).sum() == m          # oracle says inertia ok -> dense inertia must be (n,m,0)
-    assert np.abs(to_ref(d) - sol[:n]).max() < 1e-9 * max(1, np.abs(sol[:n]).max())
-    assert np.abs(ym(d) - sol[n:]).max() < 1e-8 * max(1, np.abs(sol[n:]).max())
+    sx, sy = max(1, np.abs(sol[:n]).max()), max(1, np.abs(sol[n:]).max())
+    worst = {"oracle": (np.abs(to_ref(d) - sol[:n]).max() / sx, np.abs(ym(d) - sol[n:]).max() / sy)}
+    assert worst["oracle"][0] < _DX and worst["oracle"][1] < _DY
     rd = g + J.T @ y - nlp.mult * zL + nlp.mult * zU
     assert abs(errs[0] - np.abs(rd).max()) < 1e-9 * np.abs(rd).max() and abs(errs[1] - np.abs(c).max()) < 1e-12
     # second-order correction: the same matrix, GIVEN constraint values on the right-hand side (c_soc = alpha c(z) + c(trial) in the solver) -- oracle and kernel phases
     csoc = 0.3 * c + 0.05 * rng.standard_normal(m)
     cfull = np.zeros(L["zxL"] - L["pi"]); cfull[:] = csoc          # (pi | nu | yg | yo are contiguous in the layout, in the order of the dense rows)
-    sol2 = np.linalg.solve(K, -np.concatenate([gphi + J.T @ y, csoc]))
-    ok2, d2 = oracle.newton_soc(N, Ts, S.L_WHEELBASE, S.EGO, S.XYBOUNDS, 0, x0, sc["xF"], v, A, b, xWS[:, 0], xWS[:, 1], xWS[:, 2], z, mu, dw, dc, cfull, dist=dist)
-    assert ok2 == 1 and np.abs(to_ref(d2) - sol2[:n]).max() < 1e-9 * max(1, np.abs(sol2[:n]).max()) and np.abs(ym(d2) - sol2[n:]).max() < 1e-8 * max(1, np.abs(sol2[n:]).max())
+    sol2 = np.linalg.solve(K, -np.concatenate([rhs, csoc]))
+    sx2, sy2 = max(1, np.abs(sol2[:n]).max()), max(1, np.abs(sol2[n:]).max())
+    ok2, d2 = oracle.newton_soc(*q.geo, z, mu, dw, dc, cfull, dist=dist)
+    worst["oracle soc"] = (np.abs(to_ref(d2) - sol2[:n]).max() / sx2, np.abs(ym(d2) - sol2[n:]).max() / sy2)
+    assert ok2 == 1 and worst["oracle soc"][0] < _DX and worst["oracle soc"][1] < _DY
     assert np.abs(sol2[:n] - sol[:n]).max() > 1e-3                 # it is a different step
-    import ctypes as C, packing as P
-    D_ = C.POINTER(C.c_double)
-    prob = P.pack_problem(x0, sc["xF"], N, Ts, S.L_WHEELBASE, S.EGO, S.XYBOUNDS, v, A, b, xWS[:, 0], xWS[:, 1], xWS[:, 2], 0, dist=dist)
-    d3 = np.zeros_like(z)
-    assert emu.emu_newton_soc(C.c_int(N), prob.ctypes.data_as(D_), z.ctypes.data_as(D_), C.c_int(L["len"]), C.c_double(mu), C.c_double(dw), C.c_double(dc), C.c_double(1e3),
-                              C.c_double(0.99), cfull.ctypes.data_as(D_), d3.ctypes.data_as(D_)) == 1
-    assert np.abs(to_ref(d3) - sol2[:n]).max() < 1e-9 * max(1, np.abs(sol2[:n]).max()) and np.abs(ym(d3) - sol2[n:]).max() < 1e-8 * max(1, np.abs(sol2[n:]).max())
+    if q.emu:
+        ok3, d3 = _emu_newton(emu, q, mu, dw, dc, cfull)
+        worst["host build soc"] = (np.abs(to_ref(d3) - sol2[:n]).max() / sx2, np.abs(ym(d3) - sol2[n:]).max() / sy2)
+        assert ok3 == 1 and worst["host build soc"][0] < _DX and worst["host build soc"][1] < _DY
+        ok4, d4 = _emu_newton(emu, q, mu, dw, dc)
+        worst["host build"] = (np.abs(to_ref(d4) - sol[:n]).max() / sx, np.abs(ym(d4) - sol[n:]).max() / sy)
+        assert ok4 == 1 and worst["host build"][0] < _DX and worst["host build"][1] < _DY
+    print("\nNewton direction, %s, dist %d: n %d, m %d, %d block items, inertia (%d, %d, 0); relative deviation from the dense autograd solve (primal, multipliers): %s"
+          % (case, dist, n, m, (q.N + 1) * q.nOb, n, m, ", ".join("%s %.1e %.1e" % (k, a, b_) for k, (a, b_) in worst.items())))
+
+
+@pytest.mark.parametrize("dist,case", _DIRECTION_PARAMS)
+def test_least_squares_multipliers_vs_dense_autograd(oracle, emu, dist, case):
+    """recalc_y / lsq_init: the least-squares multiplier estimate through the structured solve (unit Hessian on every variable of the reference's model, z-form gradients, zero constraint right-hand
+    side) == the dense solve of [I J'; J 0](w, y) = (-(grad f - zL + zU), 0) with autograd derivatives -- for the oracle AND for the kernels' phases (host emulation), at a random
+    interior point far from a solution, on an obstacle set of every instantiation of the obstacle block"""
+    pytest.importorskip("torch")
+    q = _direction_problem(case, dist, 5, 5); z, L = q.z, q.L
+    nlp, to_ref, ym, vv, y, zL, zU, (f, g, c, J, H) = _dense_parts(q, hessian=False)      # (the least-squares system has the identity in the Hessian's place)
+    n, m = nlp.n, nlp.m
+    K = np.block([[np.diag(nlp.mult.astype(float)), J.T], [J, np.zeros((m, m))]])      # identity on every variable of the reference's model: its N + 1 timeScale variables are one t here
+    sol = np.linalg.solve(K, -np.concatenate([g - nlp.mult * zL + nlp.mult * zU, np.zeros(m)]))       # y_new = sol[n:] (absolute); the structured solves return y_new - y
+    ev = np.linalg.eigvalsh(K)
+    ok, d = oracle.lsq_multipliers(*q.geo, z, dist=dist)
+    assert ok == 1 and (ev > 0).sum() == n and (ev < 0).sum() == m
+    scale = max(1.0, np.abs(sol[n:]).max())
+    worst = {"oracle": np.abs(y + ym(d) - sol[n:]).max() / scale}
+    assert worst["oracle"] < _DLSQ
+    assert np.abs(sol[n:] - y).max() > 0.1                       # far from a solution: the estimate is not the multiplier at hand
+    if q.emu:
+        prob = P.pack_problem(q.x0, q.xF, q.N, q.Ts, S.L_WHEELBASE, S.EGO, S.XYBOUNDS, q.v, q.A, q.b, q.xWS[:, 0], q.xWS[:, 1], q.xWS[:, 2], 0, dist=dist)
+        d2 = np.zeros_like(z)
+        assert emu.emu_lsq(C.c_int(q.N), _dp(prob), _dp(z), C.c_int(L["len"]), _dp(d2)) == 1
+        worst["host build"] = np.abs(y + ym(d2) - sol[n:]).max() / scale
+        assert worst["host build"] < _DLSQ and np.abs(d2[:L["pi"]]).max() == 0 and np.abs(d2[L["zxL"]:]).max() == 0
+    print("\nleast-squares multipliers, %s, dist %d: n %d, m %d, inertia (%d, %d, 0); relative deviation from the dense autograd solve: %s"
+          % (case, dist, n, m, n, m, ", ".join("%s %.1e" % kv for kv in worst.items())))
 
 
 @pytest.mark.parametrize("dist", [0, 1], ids=["signed_dist", "dist"])
-def test_least_squares_multipliers_vs_dense_autograd(oracle, emu, backwards, dist):
-    """recalc_y / lsq_init: the least-squares multiplier estimate through the structured solve (unit Hessian on every variable of the reference's model, z-form gradients, zero constraint right-hand
-    side) == the dense solve of [I J'; J 0](w, y) = (-(grad f - zL + zU), 0) with autograd derivatives -- for the oracle AND for the kernels' phases (host emulation), at a random
-    interior point far from a solution"""
-    torch = pytest.importorskip("torch")
-    import ctypes as C
-    from nlp_ref import ParkingNLP
-    import packing as P
-    rng = np.random.default_rng(5)
-    N = 5; sc = S.BACKWARDS; A, b, v = backwards["A"], backwards["b"], backwards["vOb"]; nOb = len(v); M = int(v.sum())
-    x0 = np.array([-6, 9.5, 0.1, 0.]); Ts, xWS, uWS = S.warm_start_backwards(x0, sc["xF"], N); Ts = 0.6
-    nlp = ParkingNLP(x0, sc["xF"], N, Ts, S.L_WHEELBASE, S.EGO, S.XYBOUNDS, v, A, b, xWS[:, 0], xWS[:, 1], xWS[:, 2], dist=dist)
-    L = oracle.layout(N, v)
-    z = np.zeros(L["len"])
-    X = xWS.copy(); X[1:] += 0.05 * rng.standard_normal((N, 4)); X[0] = x0
-    z[L["x"]:L["x"] + 4 * (N + 1)] = X.reshape(-1)
-    z[L["u"]:L["u"] + 2 * N] = np.clip(uWS + 0.05 * rng.standard_normal((N, 2)), -0.3, 0.3).reshape(-1)
-    z[L["t"]] = 1.05
-    for k, lo, hi in (("lam", 0.1, 1), ("mu", 0.1, 1), ("so", 0.1, 1), ("ss", -0.3, 0.3)):
-        n_ = L[oracle.LAYOUT_FIELDS[oracle.LAYOUT_FIELDS.index(k) + 1]] - L[k]
-        z[L[k]:L[k] + n_] = rng.uniform(lo, hi, n_)
-    z[L["sl"]:L["so"]] = rng.uniform(0.1, 1, L["so"] - L["sl"]) if dist else 0.01 * rng.standard_normal(L["so"] - L["sl"])
-    z[L["pi"]:L["zxL"]] = rng.standard_normal(L["zxL"] - L["pi"])
-    z[L["zxL"]:] = rng.uniform(0.1, 2, L["len"] - L["zxL"])
-
-    def to_ref(w):
-        vv = np.zeros(nlp.n)
-        vv[nlp.ix] = w[L["x"] + 4:L["x"] + 4 * (N + 1)]; vv[nlp.it] = w[L["t"]]; vv[nlp.iu] = w[L["u"]:L["u"] + 2 * N]
-        vv[nlp.il] = w[L["lam"]:L["lam"] + M * (N + 1)]; vv[nlp.im] = w[L["mu"]:L["mu"] + 4 * nOb * (N + 1)]
-        vv[nlp.isl] = w[L["sl"]:L["sl"] + nOb * (N + 1)]; vv[nlp.iss] = w[L["ss"]:L["ss"] + N]; vv[nlp.iso] = w[L["so"]:L["so"] + nOb * (N + 1)]
-        return vv
-    ym = lambda w: np.concatenate([w[L["pi"]:L["pi"] + 4 * N], w[L["nu"]:L["nu"] + 4], w[L["yg"]:L["yg"] + N], w[L["yo"]:L["yo"] + 4 * nOb * (N + 1)]])
-    vv, y = to_ref(z), ym(z)
-    f, g, c, J, H = nlp.eval_all(vv, y)
-    n, m = nlp.n, nlp.m
-    zL = np.zeros(n); zU = np.zeros(n)
-    zL[nlp.ix] = z[L["zxL"]:L["zxL"] + 4 * (N + 1)].reshape(N + 1, 4)[1:].reshape(-1)
-    zU[nlp.ix] = z[L["zxU"]:L["zxU"] + 4 * (N + 1)].reshape(N + 1, 4)[1:].reshape(-1)
-    zL[nlp.it] = z[L["ztL"]]; zU[nlp.it] = z[L["ztU"]]
-    zL[nlp.iu] = z[L["zuL"]:L["zuL"] + 2 * N]; zU[nlp.iu] = z[L["zuU"]:L["zuU"] + 2 * N]
-    zL[nlp.il] = z[L["zlam"]:L["zlam"] + M * (N + 1)]; zL[nlp.im] = z[L["zmu"]:L["zmu"] + 4 * nOb * (N + 1)]
-    zL[nlp.iso] = z[L["zso"]:L["zso"] + nOb * (N + 1)]
-    zL[nlp.isl] = z[L["zs1"]:L["zs1"] + nOb * (N + 1)]
-    zL[nlp.iss] = z[L["zssL"]:L["zssL"] + N]; zU[nlp.iss] = z[L["zssU"]:L["zssU"] + N]
-    IL = np.isfinite(nlp.lb); IU = np.isfinite(nlp.ub); zL[~IL] = 0; zU[~IU] = 0
-    K = np.block([[np.diag(nlp.mult.astype(float)), J.T], [J, np.zeros((m, m))]])      # identity on every variable of the reference's model: its N + 1 timeScale variables are one t here
-    sol = np.linalg.solve(K, -np.concatenate([g - nlp.mult * zL + nlp.mult * zU, np.zeros(m)]))       # y_new = sol[n:] (absolute); the structured solves return y_new - y
-    ok, d = oracle.lsq_multipliers(N, Ts, S.L_WHEELBASE, S.EGO, S.XYBOUNDS, 0, x0, sc["xF"], v, A, b, xWS[:, 0], xWS[:, 1], xWS[:, 2], z, dist=dist)
-    assert ok == 1
-    scale = max(1.0, np.abs(sol[n:]).max())
-    assert np.abs(y + ym(d) - sol[n:]).max() < 1e-9 * scale
-    assert np.abs(sol[n:] - y).max() > 0.1                       # far from a solution: the estimate is not the multiplier at hand
-    prob = P.pack_problem(x0, sc["xF"], N, Ts, S.L_WHEELBASE, S.EGO, S.XYBOUNDS, v, A, b, xWS[:, 0], xWS[:, 1], xWS[:, 2], 0, dist=dist)
-    d2 = np.zeros_like(z); D_ = C.POINTER(C.c_double)
-    assert emu.emu_lsq(C.c_int(N), prob.ctypes.data_as(D_), z.ctypes.data_as(D_), C.c_int(L["len"]), d2.ctypes.data_as(D_)) == 1
-    assert np.abs(y + ym(d2) - sol[n:]).max() < 1e-9 * scale and np.abs(d2[:L["pi"]]).max() == 0 and np.abs(d2[L["zxL"]:]).max() == 0
+def test_direction_tests_notice_one_row_entry_off_by_1e_6(oracle, emu, dist):
+    """what shows that the two tests above can fail: the dense system with ONE entry of A of a 7-row obstacle changed by 1e-6 -- the structured directions (oracle and host
+    build, on the true rows) then miss that dense solution by more than the bounds asserted above"""
+    pytest.importorskip("torch")
+    mu, dw, dc = 0.1, 3.0, 1e-6
+    for N, seed, lsq in ((4, 1, False), (5, 5, True)):
+        q = _direction_problem("rows_5_to_8", dist, N, seed)
+        r0 = int(np.sum(q.v[:5])); assert q.v[5] == 7
+        A = q.A.copy(); A[r0 + 3, 1] += 1e-6
+        nlp, to_ref, ym, vv, y, zL, zU, (f, g, c, J, H) = _dense_parts(q, A, hessian=not lsq)
+        n, m = nlp.n, nlp.m
+        if lsq:
+            K = np.block([[np.diag(nlp.mult.astype(float)), J.T], [J, np.zeros((m, m))]])
+            sol = np.linalg.solve(K, -np.concatenate([g - nlp.mult * zL + nlp.mult * zU, np.zeros(m)]))
+            ok, d = oracle.lsq_multipliers(*q.geo, q.z, dist=dist)
+            prob = P.pack_problem(q.x0, q.xF, q.N, q.Ts, S.L_WHEELBASE, S.EGO, S.XYBOUNDS, q.v, q.A, q.b, q.xWS[:, 0], q.xWS[:, 1], q.xWS[:, 2], 0, dist=dist)
+            d2 = np.zeros_like(q.z); ok2 = emu.emu_lsq(C.c_int(q.N), _dp(prob), _dp(q.z), C.c_int(q.L["len"]), _dp(d2))
+            dev = [np.abs(y + ym(w) - sol[n:]).max() / max(1.0, np.abs(sol[n:]).max()) for w in (d, d2)]
+            print("\nleast-squares multipliers against the dense solve with one row entry off by 1e-6, dist %d: oracle %.1e, host build %.1e (bound %.0e)" % (dist, dev[0], dev[1], _DLSQ))
+            assert ok == 1 and ok2 == 1 and min(dev) > _DLSQ
+        else:
+            K, rhs = _newton_system(q, nlp, vv, y, zL, zU, g, c, J, H, mu, dw, dc)
+            sol = np.linalg.solve(K, -np.concatenate([rhs, c]))
+            ok, d, _ = oracle.newton(*q.geo, q.z, mu, dw, dc, dist=dist); ok2, d2 = _emu_newton(emu, q, mu, dw, dc)
+            dev = [(np.abs(to_ref(w) - sol[:n]).max() / max(1, np.abs(sol[:n]).max()), np.abs(ym(w) - sol[n:]).max() / max(1, np.abs(sol[n:]).max())) for w in (d, d2)]
+            print("\nNewton direction against the dense solve with one row entry off by 1e-6, dist %d (primal, multipliers): oracle %.1e %.1e, host build %.1e %.1e (bounds %.0e, %.0e)"
+                  % (dist, dev[0][0], dev[0][1], dev[1][0], dev[1][1], _DX, _DY))
+            assert ok == 1 and ok2 == 1 and all(a > _DX or b_ > _DY for a, b_ in dev)
 
 
 def test_oracle_fixtime_and_retry_paths(oracle, backwards):
