@@ -153,9 +153,13 @@ int obca_batch_upload(obca_batch *bt, const double *Ts, double L, const double e
                       const double *lWS, const double *nWS);
 int obca_batch_solve(obca_batch *bt, const obca_opts *opts);   /* asynchronous on the context's stream: warm start -> (DualMultWS) -> IPM */
 int obca_batch_sync(obca_batch *bt);
-/* receding-horizon restart (not in the reference): replace the uploaded warm start by the last solution advanced by `shift`
- * stages (x, u, lambda, mu and the tracking reference move up, the tail repeats the goal stage; t = 1, sl = 0), entirely on the device; the new
- * initial state is x0_new (4 x B host, measured state) or, if NULL, stage `shift` of the solution.  The next obca_batch_solve starts from it. */
+/* receding-horizon restart (not in the reference; the text is obca_amd/csrc/obca_shift.h): replace the uploaded warm start by the last solution advanced
+ * by `shift` stages (x, u, lambda, mu and the tracking reference move up, the tail repeats the goal stage: an interval past the end keeps the last steering angle with
+ * acceleration 0; t = 1, sl = 0, every other primal word 0), entirely on the device; the new initial state is x0_new (4 x B host, measured state) or, if NULL, stage `shift`
+ * of the solution, and stage 0 of the warm start holds it.  The next obca_batch_solve starts from it (DualMultWS is skipped: the shifted multipliers are the dual start).
+ * The exit flag of the last solve is not consulted: an unconverged, finite iterate is a legitimate restart.  Returns -1 if nothing is uploaded, if shift is outside 0..N,
+ * if nothing has been solved since the last upload or shift (two shifts in a row would advance the reference twice and the iterate once), or if x0_new holds a non-finite
+ * entry; a refused call leaves the batch as it was. */
 int obca_batch_shift_warm_start(obca_batch *bt, int shift, const double *x0_new);
 int obca_batch_kernel_ms(obca_batch *bt, float *ipm_ms, float *dualws_ms);   /* HIP-event durations of the last solve */
 /* how the last obca_batch_solve ran the interior-point kernel: 1 launch, or the two-launch schedule (a slice of `slice_passes` factorisation

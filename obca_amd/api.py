@@ -684,7 +684,9 @@ class Batch(_DeviceBatch):
         return block.view(np.uint8), dict(B=int(d[0]), nObMax=int(d[1]), MMax=int(d[2]), slot_allocs=int(d[4]), io_allocs=int(d[5]))
 
     def shift_warm_start(self, shift, x0_new=None):
-        """receding-horizon restart: the next solve starts from the last solution advanced by `shift` stages (kept on the device)."""
+        """receding-horizon restart: the next solve starts from the last solution advanced by `shift` stages (kept on the device), from x0_new (B,4; the measured state;
+        None: stage `shift` of the solution).  The exit flag of the last solve is not consulted.  ObcaError if nothing has been solved since the last upload or shift, if shift
+        is outside 0..N, or if x0_new holds a non-finite entry; the batch is then as it was."""
         self._call("shift_warm_start", int(shift), _in(np.reshape(x0_new, (self.B, 4))) if x0_new is not None else None)
 
     def kernel_ms(self):

@@ -18,7 +18,7 @@
 //   obca_quad_plan_resident_kernel : one workgroup per selected instance, the quadcopter's 3-D grid search from the problem record of a resident batch, the resampled path
 //                             written into the record's warm start (obca_quad_plan_resident.h over obca_plan3d.h).
 //   obca_shift_kernel, obca_quad_shift_kernel : receding-horizon restarts, one workgroup per instance: the warm start of the next solve from the last solution
-//                             (parking: below; quadcopter: obca_quad_shift.h).
+//                             (parking: obca_shift.h; quadcopter: obca_quad_shift.h).
 // Host helpers the entry points are built from (below "host side"): EventPair, KernelStage (staging types); run_validate, launch_timed (a kernel between two events, results down);
 //   run_chunks with parking_chunks / quad_chunks (host-pointer calls over the slots); into_call (refine / subdivide into a second batch); hybrid_call (both planner entry points) over hybrid_reserve / hybrid_launch (shared with the resident route).
 // Memory (per instance, fp64, all in HBM; sizes for N=80, 3 obstacles / 5 rows in brackets):
@@ -38,6 +38,7 @@
 #include "obca_solver.h"
 #include "obca_quad_solver.h"
 #include "obca_validate.h"
+#include "obca_shift.h"
 #include "obca_quad_shift.h"
 #include "obca_path_ws.h"
 #include "obca_clearance.h"
@@ -231,26 +232,13 @@ __global__ __launch_bounds__(256) void obca_dualws_kernel(int B, int N, int nObM
     if (b.dws) b.dws[(size_t)inst * per + rem] = dv;
 }
 
-// receding-horizon restart (not in the reference): the warm start of the next solve is the previous solution advanced by
-// `shift` stages -- x, lambda, mu, the tracking reference (rx, ry, ryaw) and u move up, the tail repeats the terminal stage (standing at the
-// goal: acceleration 0), t = 1 and sl = 0 as in ParkingSignedDist.jl:213-222 -- entirely on the device.  One workgroup per instance.
-__global__ __launch_bounds__(128) void obca_shift_kernel(int B, int N, int shift, DevBufs b, const double *x0_new /* 4 x B or NULL */) {
-    const int inst = blockIdx.x; if (inst >= B) return;
-    double *p = b.prob + (size_t)inst * b.s_prob; const double *z = b.z + (size_t)inst * b.s_z; double *w = b.z0 + (size_t)inst * b.s_z;
-    double *tmp = b.d + (size_t)inst * b.s_z;                      // the direction buffer is free between solves
-    const int nOb = (int)p[PH_NOB], M = (int)p[PH_M], N1 = N + 1;
-    Lay l; make_layout(N, nOb, M, l);
-    for (int i = threadIdx.x; i < 3 * N1; i += blockDim.x) { const int a = i / N1, k = i % N1, ks = min(k + shift, N); tmp[i] = p[OB_HDR + a * N1 + ks]; }
-    for (int i = threadIdx.x; i < l.nprimal; i += blockDim.x) w[i] = 0.0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < 3 * N1; i += blockDim.x) p[OB_HDR + i] = tmp[i];
-    for (int i = threadIdx.x; i < 4 * N1; i += blockDim.x) { const int k = i / 4, c = i % 4, ks = min(k + shift, N); w[l.x + i] = z[l.x + 4 * ks + c]; }
-    for (int i = threadIdx.x; i < 2 * N; i += blockDim.x) { const int k = i / 2, c = i % 2, ks = min(k + shift, N - 1); w[l.u + i] = (c == 1 && k + shift > N - 1) ? 0.0 : z[l.u + 2 * ks + c]; }
-    for (int i = threadIdx.x; i < M * N1; i += blockDim.x) { const int k = i / M, c = i % M, ks = min(k + shift, N); w[l.lam + i] = z[l.lam + ks * M + c]; }
-    for (int i = threadIdx.x; i < 4 * nOb * N1; i += blockDim.x) { const int k = i / (4 * nOb), c = i % (4 * nOb), ks = min(k + shift, N); w[l.mu + i] = z[l.mu + ks * 4 * nOb + c]; }
-    __syncthreads();
-    if (threadIdx.x < 4) { const double v = x0_new ? x0_new[4 * inst + threadIdx.x] : z[l.x + 4 * min(shift, N) + threadIdx.x]; p[PH_X0 + threadIdx.x] = v; w[l.x + threadIdx.x] = v; }
-    if (threadIdx.x == 4) w[l.t] = 1.0;
+// receding-horizon restart of the parking batch (obca_shift.h): one wavefront per instance writes the start iterate of the next solve from the resident solution and advances
+// X0 and the tracking reference of its problem record; the direction buffer (free between solves) is the scratch of the in-place move; x0_new: 4 x B on the device, or NULL
+__global__ __launch_bounds__(OB_NT) void obca_shift_kernel(int B, int N, int shift, DevBufs b, const double *x0_new) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    shf::shift_instance(N, shift, b.prob + (size_t)inst * b.s_prob, b.z + (size_t)inst * b.s_z, b.z0 + (size_t)inst * b.s_z, b.d + (size_t)inst * b.s_z,
+                        x0_new ? x0_new + (size_t)inst * 4 : nullptr, 0);
 }
 
 // quadcopter path: one 128-thread workgroup per instance, persistent over the interior-point solve (obca_quad_solver.h)
@@ -1455,6 +1443,9 @@ int obca_batch_shift_warm_start(obca_batch *bt, int shift, const double *x0_new)
     obca_ctx *ctx = bt->ctx;
     if (!bt->uploaded) { ctx->err = "obca_batch_shift_warm_start: nothing uploaded"; return -1; }
     if (shift < 0 || shift > bt->N) { ctx->err = "obca_batch_shift_warm_start: shift out of range 0..N"; return -1; }
+    if (!bt->solved) { ctx->err = "obca_batch_shift_warm_start: nothing has been solved since the last upload or shift"; return -1; }
+    for (size_t i = 0; x0_new && i < (size_t)bt->B * 4; i++)
+        if (!(x0_new[i] - x0_new[i] == 0.0)) { ctx->err = "obca_batch_shift_warm_start: non-finite entry in x0_new"; return -1; }
     use_device(bt->device);
     double *dx0 = nullptr;
     if (x0_new) {   // staged through the (idle) device staging buffer of the batch: nothing to free on the error paths
@@ -1463,7 +1454,7 @@ int obca_batch_shift_warm_start(obca_batch *bt, int shift, const double *x0_new)
         dx0 = bt->stage;
         if (hipMemcpyAsync(dx0, bt->h_info, (size_t)bt->B * 4 * sizeof(double), hipMemcpyHostToDevice, bt->stream) != hipSuccess) { ctx->err = "obca_batch_shift_warm_start: H2D failed"; return -2; }
     }
-    hipLaunchKernelGGL(obca_shift_kernel, dim3(bt->B), dim3(128), 0, bt->stream, bt->B, bt->N, shift, bt->d, (const double *)dx0);
+    hipLaunchKernelGGL(obca_shift_kernel, dim3(bt->B), dim3(OB_NT), 0, bt->stream, bt->B, bt->N, shift, bt->d, (const double *)dx0);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(bt->stream) != hipSuccess) { ctx->err = "obca_batch_shift_warm_start: kernel failed"; return -2; }
     bt->solved = 0;                                     // d.z still holds the previous solution, but the problem (x0, reference) has moved on
     bt->have_duals = 1;                                 // the shifted multipliers are the dual warm start: DualMultWS is skipped
