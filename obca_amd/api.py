@@ -22,7 +22,7 @@ import numpy as np
 from . import buildflags, cabi, planner
 from .cabi import Opts      # `typedef struct obca_opts` of include/obca_hip.h, read from the header
 from .validate import (VIOL_NAMES, QUAD_VIOL_NAMES, DMIN, CLR_OUT, ROLL_OUT, TRK_OUT, TRACK_Q_PARKING, TRACK_R_PARKING, TRACK_QF_PARKING, TRACK_Q_QUAD, TRACK_R_QUAD,
-                       TRACK_QF_QUAD, ENS_MEM, ENS_OUT, ENS_MMAX, CERT_OUT, CERT_TICKS)
+                       TRACK_QF_QUAD, ENS_MEM, ENS_OUT, ENS_MMAX, CERT_OUT, CERT_TICKS, ADV_OUT)
 
 _LIBPATH = os.environ.get("OBCA_HIP_LIBRARY") or buildflags.PIECES["hip"].out   # override: diagnostic builds
 _lib = None
@@ -65,6 +65,7 @@ def _load():
     cabi.bind(_lib, "obca_rollout.h")                     # solved batches applied to the continuous vehicle models
     cabi.bind(_lib, "obca_track.h")                       # ... and tracked on them by a time-varying LQR
     cabi.bind(_lib, "obca_ensemble.h")                    # ... from a spread of start offsets and input biases at once
+    cabi.bind(_lib, "obca_advance.h")                     # the closed loop: the plant advanced under a solution and the next solve restarted from where it got
     cabi.bind(_lib, "obca_certify.h")                     # the clearance certified along the whole path
     return _lib
 
@@ -116,6 +117,10 @@ TRACK_EXPORTS = ["obca_batch_track", "obca_batch_track_ms", "obca_batch_track_st
 # ensemble_members, ensemble_final, ensemble_ms, parking_ensemble_batch, quadcopter_ensemble_batch)
 ENSEMBLE_EXPORTS = ["obca_batch_ensemble", "obca_batch_ensemble_ms", "obca_batch_ensemble_members", "obca_batch_ensemble_final", "obca_parking_ensemble_batch",
                     "obca_quad_batch_ensemble", "obca_quad_batch_ensemble_ms", "obca_quad_batch_ensemble_members", "obca_quad_batch_ensemble_final", "obca_quadcopter_ensemble_batch"]
+# include/obca_advance.h: one step of the closed receding-horizon loop on the device (Batch.advance, QuadBatch.advance, advance_state, advance_log, advance_log_states,
+# advance_ms)
+ADVANCE_EXPORTS = ["obca_batch_advance", "obca_batch_advance_ms", "obca_batch_advance_state", "obca_batch_advance_log", "obca_batch_advance_log_states",
+                   "obca_quad_batch_advance", "obca_quad_batch_advance_ms", "obca_quad_batch_advance_state", "obca_quad_batch_advance_log", "obca_quad_batch_advance_log_states"]
 # include/obca_certify.h: the clearance of solutions and trajectories certified along the whole path by conservative advancement (Batch.certify, QuadBatch.certify,
 # certify_intervals, certify_ms, parking_certify_batch, quadcopter_certify_batch)
 CERTIFY_EXPORTS = ["obca_batch_certify", "obca_batch_certify_ms", "obca_batch_certify_intervals", "obca_parking_certify_batch", "obca_quad_batch_certify",
@@ -273,6 +278,16 @@ def _rollout_dict(rec, substeps, nOb):
     return dict(dev_pos=rec[:, 1], dev_node=rec[:, 2].astype(np.int64), dev_att=rec[:, 3], dev_vel=rec[:, 4], dev_rate=rec[:, 5], end_pos=rec[:, 6], end_att=rec[:, 7],
                 end_vel=rec[:, 8], end_rate=rec[:, 9], restart=rec[:, 10] != 0, substeps=rec[:, 11].astype(np.int64), finite=rec[:, 0] == 0,
                 clearance=_clearance_dict(rec[:, 16:], substeps, nOb))
+
+
+def _advance(B, substeps, nOb, call):
+    """the records of an advance entry point, `call(out)` with out (B, ADV_OUT), and the dict they are returned in: the dict of _rollout for the driven intervals --
+    dev_* the deviations of the plant from the solution's own nodes 1..shift (the model mismatch the next solve absorbs), end_* at node `shift`, `clearance` of the driven
+    samples; finite False marks an instance that was NOT advanced and not restarted (its values are NaN) -- and shift, driven_time (sum t_k Ts), goal_dist (the position
+    distance of the new plant state to the goal of the next solve), logged (the nodes in the log after the call, -1 without one)"""
+    rec = np.zeros((B, ADV_OUT))
+    call(rec)
+    return dict(_rollout_dict(rec, substeps, nOb), shift=rec[:, 12].astype(np.int64), driven_time=rec[:, 13], goal_dist=rec[:, 14], logged=rec[:, 15].astype(np.int64))
 
 
 def _track(B, substeps, nOb, call):
@@ -544,6 +559,37 @@ class _DeviceBatch(_Handle):
         """HIP-event duration of the last rollout kernel"""
         return self._floats("rollout_ms")
 
+    def _advance(self, nOb, shift, substeps, need, *rows):
+        """what Batch.advance and QuadBatch.advance share: `rows` (the kick, for the quadcopter xF_new) are None or (B, nx) / (nx,)"""
+        a = [None if r is None else _in(np.broadcast_to(np.asarray(r, float), (self.B, self._nx))) for r in rows]
+        return _advance(self.B, substeps, nOb, lambda out: self._call("advance", int(shift), int(substeps), *a, float(need), out))
+
+    def advance_state(self):
+        """The plant state the last advance() left on the device: (B, nx), after the kick; NaN for an instance that was not finite.  It is X0 of the instance's problem
+        record now: the next advance() starts the plant there."""
+        X = np.zeros((self.B, self._nx))
+        self._call("advance_state", X)
+        return X
+
+    def advance_log(self, capacity):
+        """Keep the node states every advance() drives through ON THE DEVICE: room for `capacity` nodes per instance (0: free the log).  The log starts empty, an upload
+        empties it, and an advance() that would not fit is refused before it does anything."""
+        self._call("advance_log", int(capacity))
+
+    def advance_log_states(self):
+        """The log, fetched from the device: (B, nodes, nx) -- per advance() its `shift` nodes, the last one after the kick; the rows of a step in which an instance was
+        not finite hold what was there before (zeros in a fresh log)."""
+        n = np.zeros(1, np.int32)
+        self._call("advance_log_states", None, n)
+        X = np.zeros((self.B, int(n[0]), self._nx))
+        if n[0]:
+            self._call("advance_log_states", X, n)
+        return X
+
+    def advance_ms(self):
+        """HIP-event duration of the last advance kernel"""
+        return self._floats("advance_ms")
+
     def _track(self, nOb, defaults, substeps, dx0, Q, R, Qf, feedback, clamp, need):
         q, r, qf = _track_weights(self._nx, self._nu, Q, R, Qf, defaults)
         return _track(self.B, substeps, nOb, lambda out: self._call("track", int(substeps), int(feedback), int(clamp), q, r, qf, _track_dx0(dx0, self.B, self._nx), float(need), out))
@@ -720,6 +766,14 @@ class Batch(_DeviceBatch):
         is what the car does.  Returns the dict of _rollout: deviations of the rolled node states from the solution's, and `clearance`, the dict of clearance() for the
         rolled samples (need: its `need`).  The rolled states stay on the device: rollout_states()."""
         return self._rollout(int(self.nObs.max()), substeps, restart, need)
+
+    def advance(self, shift, substeps=8, kick=None, need=DMIN):
+        """One step of the closed receding-horizon loop, ON THE DEVICE in one launch (obca_batch_advance; the numpy statement is obca_amd.validate.advance_parking +
+        advance_record): the continuous bicycle of rollout() is driven from the record's X0 over the first `shift` intervals of the last solution, `kick` ((4,) or (B,4);
+        the process disturbance) is added to the state it reaches, and the next solve is restarted exactly as shift_warm_start(shift, x0_new=<that state>) restarts it --
+        the state never leaves the device.  Returns the dict of _advance.  The batch counts as unsolved afterwards: solve() again, that re-solve is the feedback of this
+        loop (track() is the tool between two re-solves).  advance_state(), advance_log(), advance_log_states(), advance_ms()."""
+        return self._advance(int(self.nObs.max()), shift, substeps, need, kick)
 
     def track(self, substeps=8, dx0=None, Q=None, R=None, Qf=None, feedback=True, clamp=True, need=DMIN):
         """The last solution TRACKED on the continuous kinematic bicycle by a time-varying LQR about it, ON THE DEVICE (obca_batch_track; the numpy statement is
@@ -1158,6 +1212,12 @@ class QuadBatch(_DeviceBatch):
         rotor speeds held over every interval, classical RK4 with `substeps` steps per interval, the gyroscopic products at the current rates.  The NLP's rows are forward
         Euler: restart=True shows what one interval of it is off by, restart=False where the open loop ends up.  Returns the dict of Batch.rollout, 5 obstacles."""
         return self._rollout(5, substeps, restart, need)
+
+    def advance(self, shift, substeps=8, kick=None, xF_new=None, need=0.0):
+        """One step of the closed receding-horizon loop on the device (obca_quad_batch_advance; numpy: obca_amd.validate.advance_quad + advance_record): Batch.advance
+        on the continuous rigid body with kick (12,) or (B,12), restarted as shift_warm_start(shift, x0_new=<the plant state>, xF_new) restarts (xF_new: (12,) or (B,12),
+        a moving goal).  Solve with quad_warm_restart_opts()."""
+        return self._advance(5, shift, substeps, need, kick, xF_new)
 
     def track(self, substeps=8, dx0=None, Q=None, R=None, Qf=None, feedback=True, clamp=True, need=0.0):
         """The last solution tracked on the continuous rigid body by a time-varying LQR about it, on the device (obca_quad_batch_track; numpy:

@@ -10,6 +10,7 @@
 //   obca_rollout_*_kernel   : one wavefront per instance, a solution or a caller's trajectory applied to the continuous vehicle model: deviations, clearance of the rolled samples (obca_rollout.h).
 //   obca_track_*_kernel     : one wavefront per instance, TVLQR gains about a solution or a caller's trajectory and the closed loop rolled on the continuous model (obca_track.h).
 //   obca_ensemble_*_kernel  : one wavefront per instance, one member per lane: up to 64 disturbed closed loops about a solution or a caller's trajectory, the gains computed once (obca_ensemble.h).
+//   obca_advance_*_kernel   : one wavefront per instance, one step of the closed receding-horizon loop: the plant over the first `shift` intervals of the solution, the restart from the state it reached (obca_advance.h).
 //   obca_certify_*_kernel   : one wavefront per instance, the clearance of a solution or of a caller's trajectory certified along its whole path by conservative advancement (obca_certify.h).
 //   obca_refine_*_kernel    : one wavefront per destination instance, a solved parking instance on a finer horizon (obca_refine.h): into a second resident batch or host-bound arrays.
 //   obca_quad_subdivide_*_kernel : the same for a solved quadcopter instance (obca_quad_subdivide.h): it rewrites a problem record.
@@ -47,6 +48,7 @@
 #include "obca_rollout.h"
 #include "obca_track.h"
 #include "obca_ensemble.h"
+#include "obca_advance.h"
 #include "obca_certify.h"
 #include "../../include/obca_hip.h"
 #include "../../include/obca_path_ws.h"
@@ -56,6 +58,7 @@
 #include "../../include/obca_rollout.h"
 #include "../../include/obca_track.h"
 #include "../../include/obca_ensemble.h"
+#include "../../include/obca_advance.h"
 #include "../../include/obca_certify.h"
 
 using namespace obca;
@@ -72,6 +75,7 @@ static_assert(OBCA_CLR_OUT == CL_OUT && OBCA_CLR_MAXSUB == CL_SMAX && OBCA_CLR_T
 static_assert(OBCA_REFINE_MAXFACTOR == RF_MAXFACTOR, "ABI limits must match the kernels");
 static_assert(OBCA_ROLL_OUT == RO_OUT && OBCA_ROLL_CLR == RO_CLR && OBCA_ROLL_MAXSUB == CL_SMAX, "ABI limits must match the kernels");
 static_assert(OBCA_TRK_OUT == TK_OUT, "ABI limits must match the kernels");
+static_assert(OBCA_ADV_OUT == AV_OUT, "ABI limits must match the kernels");
 static_assert(OBCA_CERT_OUT == CT_OUT && OBCA_CERT_TICKS == CT_TICKS, "ABI limits must match the kernels");
 static_assert(OBCA_VMAX == OB_VMAX && OBCA_NOBMAX == OB_NOBMAX && OBCA_NMAX == OB_NMAX && OBCA_MMAX == OB_MMAX, "ABI limits must match the kernels");
 
@@ -390,6 +394,28 @@ __global__ __launch_bounds__(QNT) void obca_ensemble_quad_kernel(int B, int N, c
                                 out + (size_t)inst * EN_OUT);
 }
 
+// one closed-loop step (obca_advance.h): one wavefront per instance; the batch's buffers (the restart rewrites prob and z0; b.d is its scratch), the sub-steps, `aux` (s_aux
+// doubles per instance: the kick, for the quadcopter xF_new behind it; has_* 0: none), the two regions of the work buffer, the plant states (nx per instance), the log (s_log
+// doubles per instance, this step's rows at `log_at`; NULL: none) and field [15] of the record
+template <int VM>
+__global__ __launch_bounds__(OB_NT) void obca_advance_parking_kernel(int B, int N, int shift, DevBufs b, int S, const double *aux, int has_kick, double need, double *pose, size_t s_pose,
+                                                                     double *X, size_t s_X, double *st, double *log, size_t s_log, size_t log_at, double logged, double *out) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    adv::advance_parking_instance<VM>(N, shift, b.prob + (size_t)inst * b.s_prob, b.z + (size_t)inst * b.s_z, b.z0 + (size_t)inst * b.s_z, b.d + (size_t)inst * b.s_z, S,
+                                      has_kick ? aux + (size_t)inst * 4 : nullptr, need, 0, pose + (size_t)inst * s_pose, X + (size_t)inst * s_X, st + (size_t)inst * 4,
+                                      log ? log + (size_t)inst * s_log + log_at : nullptr, logged, out + (size_t)inst * AV_OUT);
+}
+__global__ __launch_bounds__(QNT) void obca_advance_quad_kernel(int B, int N, int shift, QDevBufs b, int S, const double *aux, int has_kick, int has_xF, double need, double *pose, size_t s_pose,
+                                                                double *X, size_t s_X, double *st, double *log, size_t s_log, size_t log_at, double logged, double *out) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    const double *a = aux + (size_t)inst * 2 * QX;
+    adv::advance_quad_instance(N, shift, b.prob + (size_t)inst * b.s_prob, b.z + (size_t)inst * b.s_z, b.info + (size_t)inst * 8, S, has_kick ? a : nullptr, has_xF ? a + QX : nullptr,
+                               need, 0, pose + (size_t)inst * s_pose, X + (size_t)inst * s_X, st + (size_t)inst * QX, log ? log + (size_t)inst * s_log + log_at : nullptr, logged,
+                               out + (size_t)inst * AV_OUT);
+}
+
 // clearance certificate (obca_certify.h): one wavefront per instance; the arguments of the clearance kernels with need, slack and max_steps in place of the sub-steps, then
 // the interval array (2 (N + 1) per instance).  The item table is the launch's dynamic LDS: cert::certify_work_len(N, the batch's most obstacles) doubles
 template <int VM>
@@ -615,6 +641,10 @@ struct BatchCore {
     ValBufs ens;                                            // ... and for the ensemble calls (obca_ensemble.h), again with buffers of their own
     DevBuf ens_w, ens_K, ens_mem, ens_fin;                  // [A|B] N nx (nx + nu) x B; the gains; the member records M x EN_MEM x B; the final states M x nx x B
     int ens_B = 0, ens_N = 0, ens_M = 0;                    // the instances, horizon and members of the last ensemble call (0: none yet)
+    ValBufs adv;                                            // ... and for the advance calls (obca_advance.h): a previous rollout's states stay valid
+    DevBuf adv_w, adv_st, adv_log;                          // [ sample poses 3 x (shift S + 1) | node states nx x (shift + 1) ] x B; the plant states nx x B; the log B x adv_cap x nx
+    int adv_B = 0, adv_N = 0;                               // the instances and horizon of the last advance (0: none yet): adv_st holds its plant states
+    int adv_cap = 0, adv_n = 0;                             // the log's rows per instance (0: no log) and the nodes in it
     ValBufs cer;                                            // ... and for the certify calls (obca_certify.h)
     DevBuf cer_iv;                                          // their interval arrays, 2 (N + 1) x B
     int cer_B = 0, cer_N = 0;                               // the instances and horizon of the last certify call (0: none yet)
@@ -681,7 +711,8 @@ static int core_phase_cycles(BatchCore *bt, const double *prof, double *out /* B
 static void core_release(BatchCore *bt) {
     bt->rol_w.release(); bt->trk_w.release(); bt->trk_K.release();
     bt->ens_w.release(); bt->ens_K.release(); bt->ens_mem.release(); bt->ens_fin.release(); bt->cer_iv.release();
-    for (ValBufs *pv : {&bt->val, &bt->clr, &bt->rol, &bt->trk, &bt->ens, &bt->cer}) {
+    bt->adv_w.release(); bt->adv_st.release(); bt->adv_log.release();
+    for (ValBufs *pv : {&bt->val, &bt->clr, &bt->rol, &bt->trk, &bt->ens, &bt->cer, &bt->adv}) {
         ValBufs &v = *pv;
         v.d_in.release(); v.d_out.release(); v.h_in.release(); v.h_out.release(); v.ev.release();
     }
@@ -851,7 +882,7 @@ static int batch_reserve_shape(obca_batch *bt, int nObMax, int MMax) {
 static int batch_upload_range(obca_batch *bt, const ParkIn &in, int lo, int n) {
     const int N = bt->N, N1 = N + 1;
     if (n < 1 || n > bt->cap) { bt->err = "obca_batch_upload: more instances than the batch was created for"; return -1; }
-    bt->B = n; bt->solved = 0; bt->val_rl = 0;
+    bt->B = n; bt->solved = 0; bt->val_rl = 0; bt->adv_n = 0;      // (an upload empties the log of obca_advance.h)
     bt->nOb.assign(n, 0); bt->M.assign(n, 0); bt->obOff.assign(n + 1, 0); bt->rowOff.assign(n + 1, 0); bt->vmx.assign(n, 0);
     int nObMax = 0, MMax = 0; bt->vmax = 0;
     for (int i = 0; i < n; i++) {
@@ -1280,6 +1311,78 @@ static int batch_ensemble_range(obca_batch *bt, bool host, const double *ts, int
     return ensemble_finish(bt, rc, d, lo, mem, fin);
 }
 
+// What the two advance calls share (obca_advance.h).  advance_refuse: the refusals, before anything is launched or written.  advance_reserve: the work buffer and the plant
+// states for B instances.  advance_finish: the bookkeeping after the kernel -- the batch counts as unsolved, as after a shift; the log has grown.
+static int advance_refuse(BatchCore *bt, const char *entry, int shift, int substeps, double need, const double *out) {
+    std::string &err = bt->ctx->err;
+    if (!out) { err = std::string(entry) + ": NULL argument"; return -1; }
+    if (!bt->uploaded || !bt->solved) { err = std::string(entry) + ": nothing has been solved since the last upload, shift or advance"; return -1; }
+    if (const char *bad = adv::advance_check_args(bt->N, shift, substeps, need)) { err = std::string(entry) + ": " + bad; return -1; }
+    if (bt->adv_cap && bt->adv_n + shift > bt->adv_cap) { err = std::string(entry) + ": the log is full (obca_batch_advance_log sets its capacity)"; return -1; }
+    return 0;
+}
+static int advance_reserve(BatchCore *bt, int nx, int shift, int S) {
+    use_device(bt->device);
+    if (bt->adv_w.reserve((size_t)bt->B * (adv::advance_pose_len(shift, S) + adv::advance_state_len(shift, nx)), bt->stream) != hipSuccess ||
+        bt->adv_st.reserve((size_t)bt->cap * nx, bt->stream) != hipSuccess) { bt->err = "hipMalloc(advance work buffer) failed"; return -2; }
+    return 0;
+}
+static int advance_finish(BatchCore *bt, int rc, int shift) {
+    bt->adv_B = bt->adv_N = 0;
+    if (rc) return rc;
+    bt->adv_B = bt->B; bt->adv_N = bt->N;
+    if (bt->adv_cap) bt->adv_n += shift;
+    bt->solved = 0;      // d.z still holds the previous solution, but the problem (x0, reference / warm start) has moved on
+    return 0;
+}
+static int advance_state(BatchCore *bt, int nx, double *X, const char *entry) {
+    if (!X) { bt->ctx->err = std::string(entry) + ": NULL argument"; return -1; }
+    if (!bt->adv_B || bt->adv_B != bt->B || bt->adv_N != bt->N) { bt->ctx->err = std::string(entry) + ": no advance has run on this batch since it was last filled"; return -1; }
+    use_device(bt->device);
+    if (hipStreamSynchronize(bt->stream) != hipSuccess || hipMemcpy(X, (const double *)bt->adv_st, (size_t)bt->B * nx * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+        bt->ctx->err = std::string(entry) + ": D2H failed"; return -2;
+    }
+    return 0;
+}
+static int advance_log(BatchCore *bt, int nx, int capacity, const char *entry) {
+    if (capacity < 0 || (size_t)capacity > ((size_t)1 << 31) / ((size_t)bt->cap * nx)) { bt->ctx->err = std::string(entry) + ": capacity out of range"; return -1; }
+    use_device(bt->device);
+    if (hipStreamSynchronize(bt->stream) != hipSuccess) { bt->ctx->err = std::string(entry) + ": hipStreamSynchronize failed"; return -2; }
+    bt->adv_log.release(); bt->adv_cap = bt->adv_n = 0;
+    if (!capacity) return 0;
+    if (bt->adv_log.reserve((size_t)bt->cap * capacity * nx, bt->stream) != hipSuccess) { bt->ctx->err = std::string(entry) + ": hipMalloc(log) failed"; return -2; }
+    bt->adv_cap = capacity;
+    return 0;
+}
+static int advance_log_states(BatchCore *bt, int nx, double *X, int *nodes, const char *entry) {
+    if (!nodes) { bt->ctx->err = std::string(entry) + ": NULL argument"; return -1; }
+    if (!bt->adv_cap) { bt->ctx->err = std::string(entry) + ": this batch has no log (obca_batch_advance_log allocates one)"; return -1; }
+    *nodes = bt->adv_n;
+    if (!X || !bt->adv_n) return 0;
+    use_device(bt->device);
+    const size_t row = (size_t)bt->adv_n * nx * sizeof(double);      // the filled rows of every instance, dense
+    if (hipStreamSynchronize(bt->stream) != hipSuccess ||
+        hipMemcpy2D(X, row, (const double *)bt->adv_log, (size_t)bt->adv_cap * nx * sizeof(double), row, (size_t)bt->B, hipMemcpyDeviceToHost) != hipSuccess) {
+        bt->ctx->err = std::string(entry) + ": D2H failed"; return -2;
+    }
+    return 0;
+}
+// One step of the batch's parking instances: the kick (4 per instance, or nullptr) travels up
+static int batch_advance_run(obca_batch *bt, int shift, int S, const double *kick, double need, double *out) {
+    const int B = bt->B, N = bt->N;
+    if (int rc = advance_reserve(bt, 4, shift, S)) return rc;
+    const size_t sp = adv::advance_pose_len(shift, S), sx = adv::advance_state_len(shift, 4);
+    const int rc = run_validate(bt, bt->adv, 4, kick != nullptr, AV_OUT, [&](int i, double *a) { memcpy(a, kick + (size_t)i * 4, sizeof(double) * 4); }, [&] {
+        double *log = bt->adv_cap ? (double *)bt->adv_log : nullptr;
+        const double logged = bt->adv_cap ? (double)(bt->adv_n + shift) : -1.0;
+#define ADV_LAUNCH(VM) hipLaunchKernelGGL(obca_advance_parking_kernel<VM>, dim3(B), dim3(OB_NT), 0, bt->stream, B, N, shift, bt->d, S, (const double *)bt->adv.d_in, kick ? 1 : 0, need, \
+                                          (double *)bt->adv_w, sp, bt->adv_w + (size_t)B * sp, sx, (double *)bt->adv_st, log, (size_t)bt->adv_cap * 4, (size_t)bt->adv_n * 4, logged, (double *)bt->adv.d_out)
+        if (bt->vmax <= 2) ADV_LAUNCH(2); else if (bt->vmax <= OB_VMID) ADV_LAUNCH(OB_VMID); else ADV_LAUNCH(OB_VMAX);      // (the row class of launch_dualws)
+#undef ADV_LAUNCH
+    }, [&](int i, const double *o) { memcpy(out + (size_t)i * AV_OUT, o, sizeof(double) * AV_OUT); });
+    return advance_finish(bt, rc, shift);
+}
+
 // What the two certify routes share (obca_certify.h): the interval arrays for B instances before the kernel; after it the bookkeeping of the *_intervals calls and, for a
 // host-pointer call, the chunk's interval arrays into the caller's iv.
 static int certify_reserve(BatchCore *bt) {
@@ -1601,6 +1704,18 @@ int obca_parking_ensemble_batch(obca_ctx *ctx, int B, int N, const double *Ts, d
     return parking_chunks(ctx, 0, B, N, in, [&](obca_batch *bt, int lo) { return batch_ensemble_range(bt, true, timeScale, substeps, members, feedback, clamp, w, dx0, dub, need, lo, out, mem, fin); });
 }
 
+int obca_batch_advance(obca_batch *bt, int shift, int substeps, const double *kick, double need, double *out) {
+    if (!bt) return -1;
+    if (int rc = advance_refuse(bt, "obca_batch_advance", shift, substeps, need, out)) return rc;
+    const int rc = batch_advance_run(bt, shift, substeps, kick, need, out);
+    if (!rc) bt->have_duals = 1;                        // the shifted multipliers are the dual warm start: DualMultWS is skipped
+    return fin(bt, rc);
+}
+int obca_batch_advance_ms(obca_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->adv.ev, ms, "obca_batch_advance_ms: no advance has run on this batch") : -1; }
+int obca_batch_advance_state(obca_batch *bt, double *X) { return bt ? advance_state(bt, 4, X, "obca_batch_advance_state") : -1; }
+int obca_batch_advance_log(obca_batch *bt, int capacity_nodes) { return bt ? advance_log(bt, 4, capacity_nodes, "obca_batch_advance_log") : -1; }
+int obca_batch_advance_log_states(obca_batch *bt, double *X, int *nodes) { return bt ? advance_log_states(bt, 4, X, nodes, "obca_batch_advance_log_states") : -1; }
+
 int obca_batch_certify(obca_batch *bt, double need, double slack, int max_steps, double *out) {
     if (!bt) return -1;
     if (!out) { bt->ctx->err = "obca_batch_certify: NULL argument"; return -1; }
@@ -1862,7 +1977,7 @@ struct QuadIn { const double *Ts; double R; const double *x0, *xF, *ob, *xWS, *t
 struct QuadOut { double *xp, *up, *ts; int *exitflag; double *lp, *slp, *info; };
 static int quad_upload_range(obca_quad_batch *bt, const QuadIn &in, int lo, int n) {
     if (n < 1 || n > bt->cap) { bt->err = "obca_quad_batch_upload: more instances than the batch was created for"; return -1; }
-    bt->B = n; bt->solved = 0;
+    bt->B = n; bt->solved = 0; bt->adv_n = 0;      // (an upload empties the log of obca_advance.h)
     const int N1 = bt->N + 1; const QDevBufs &d = bt->d;
     if (bt->h_prob.reserve(bt->err, (size_t)bt->cap * d.s_prob)) return -2;
     for (int i = 0; i < n; i++) {
@@ -2052,6 +2167,21 @@ static int quad_ensemble_range(obca_quad_batch *bt, const double *u, const doubl
     return ensemble_finish(bt, rc, d, lo, mem, fin);
 }
 // the certificate of the batch's quadcopter instances (obca_certify.h): quad_clearance_range with need, slack and max_steps, then the caller's iv
+// one step of the batch's quadcopter instances (obca_advance.h): per instance [ kick 12 | xF_new 12 ] travels up where either is given
+static int quad_advance_run(obca_quad_batch *bt, int shift, int S, const double *kick, const double *xF_new, double need, double *out) {
+    const int B = bt->B, N = bt->N;
+    if (int rc = advance_reserve(bt, QX, shift, S)) return rc;
+    const size_t sp = adv::advance_pose_len(shift, S), sx = adv::advance_state_len(shift, QX);
+    const int rc = run_validate(bt, bt->adv, 2 * QX, kick || xF_new, AV_OUT, [&](int i, double *a) {
+        if (kick) memcpy(a, kick + (size_t)i * QX, sizeof(double) * QX); else memset(a, 0, sizeof(double) * QX);
+        if (xF_new) memcpy(a + QX, xF_new + (size_t)i * QX, sizeof(double) * QX); else memset(a + QX, 0, sizeof(double) * QX);
+    }, [&] {
+        hipLaunchKernelGGL(obca_advance_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, shift, bt->d, S, (const double *)bt->adv.d_in, kick ? 1 : 0, xF_new ? 1 : 0, need, (double *)bt->adv_w, sp,
+                           bt->adv_w + (size_t)B * sp, sx, (double *)bt->adv_st, bt->adv_cap ? (double *)bt->adv_log : nullptr, (size_t)bt->adv_cap * QX, (size_t)bt->adv_n * QX,
+                           bt->adv_cap ? (double)(bt->adv_n + shift) : -1.0, (double *)bt->adv.d_out);
+    }, [&](int i, const double *o) { memcpy(out + (size_t)i * AV_OUT, o, sizeof(double) * AV_OUT); });
+    return advance_finish(bt, rc, shift);
+}
 static int quad_certify_range(obca_quad_batch *bt, const double *ts, double need, double slack, int max_steps, int lo, double *out, double *iv) {
     const int B = bt->B, N = bt->N, N1 = N + 1; const QDevBufs &d = bt->d;
     quad::QLay l; quad::q_make_layout(N, l);
@@ -2221,6 +2351,18 @@ int obca_quadcopter_ensemble_batch(obca_ctx *ctx, int B, int N, const double *Ts
     const trk::Weights w = trk::make_weights(q, r, qf, QX, QU);
     return quad_chunks(ctx, B, N, in, [&](obca_quad_batch *bt, int lo) { return quad_ensemble_range(bt, u, timeScale, substeps, members, feedback, clamp, w, dx0, dub, need, lo, out, mem, fin); });
 }
+int obca_quad_batch_advance(obca_quad_batch *bt, int shift, int substeps, const double *kick, const double *xF_new, double need, double *out) {
+    if (!bt) return -1;
+    if (int rc = advance_refuse(bt, "obca_quad_batch_advance", shift, substeps, need, out)) return rc;
+    for (size_t i = 0; xF_new && i < (size_t)bt->B * QX; i++)
+        if (!(xF_new[i] - xF_new[i] == 0.0)) { bt->ctx->err = "obca_quad_batch_advance: non-finite entry in xF_new"; return -1; }
+    return fin(bt, quad_advance_run(bt, shift, substeps, kick, xF_new, need, out));
+}
+int obca_quad_batch_advance_ms(obca_quad_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->adv.ev, ms, "obca_quad_batch_advance_ms: no advance has run on this batch") : -1; }
+int obca_quad_batch_advance_state(obca_quad_batch *bt, double *X) { return bt ? advance_state(bt, QX, X, "obca_quad_batch_advance_state") : -1; }
+int obca_quad_batch_advance_log(obca_quad_batch *bt, int capacity_nodes) { return bt ? advance_log(bt, QX, capacity_nodes, "obca_quad_batch_advance_log") : -1; }
+int obca_quad_batch_advance_log_states(obca_quad_batch *bt, double *X, int *nodes) { return bt ? advance_log_states(bt, QX, X, nodes, "obca_quad_batch_advance_log_states") : -1; }
+
 int obca_quad_batch_certify(obca_quad_batch *bt, double need, double slack, int max_steps, double *out) {
     if (!bt) return -1;
     if (!out) { bt->ctx->err = "obca_quad_batch_certify: NULL argument"; return -1; }

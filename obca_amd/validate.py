@@ -396,6 +396,61 @@ def rollout_record(x, X, c, substeps, restart, need, finite=True):
     return r
 
 
+# ---------------------------------------------------------------- one step of the closed receding-horizon loop (obca_amd/csrc/obca_advance.h)
+ADV_OUT = 40          # doubles of a record: the ROLL_OUT layout with [10] 0, [11] S, [12] shift, [13] the driven time, [14] the distance to the goal, [15] the nodes logged
+
+
+def _advance(roll, nx, x, u, t, Ts, shift, substeps, x0, kick):
+    x = np.asarray(x, float); shift = int(shift)
+    xs = np.array(x[:, :shift + 1], float); xs[:, 0] = np.asarray(x0, float).reshape(nx)      # the chain starts at the record's X0, not at the solution's node 0
+    X, P = roll(xs, np.asarray(u, float)[:, :shift], float(t), Ts, substeps)
+    st = X[:, shift] + np.asarray(kick, float).reshape(nx) if kick is not None else X[:, shift].copy()
+    ok = bool(np.isfinite(X).all() and np.isfinite(st).all() and np.isfinite(x[:, :shift + 1]).all() and np.isfinite(np.asarray(u, float)[:, :shift]).all()
+              and np.isfinite(xs[:, 0]).all() and np.isfinite(float(t) * float(Ts)))
+    return X, P, (st if ok else np.full(nx, np.nan)), ok
+
+
+def advance_parking(x, u, t, Ts, L, shift, substeps=8, x0=None, kick=None):
+    """The plant of one closed-loop step: _rollout (rollout_parking's chain) truncated to the first `shift` intervals of the solution x (4,N+1), u (2,N) with its one time
+    scale t, started at x0 (the record's X0; None: the solution's node 0).  Returns (X (4, shift+1) the driven node states BEFORE the kick, samples (shift S + 1, 3), state
+    (4,) = X[:, shift] + kick, ok); not ok (a number that is not finite among what is read or rolled): state is NaN."""
+    x = np.asarray(x, float)
+    return _advance(lambda a, b, c, d, e: rollout_parking(a, b, c, d, L, e, False), 4, x, u, t, Ts, shift, substeps, x[:, 0] if x0 is None else x0, kick)
+
+
+def advance_quad(x, u, t, Ts, shift, substeps=8, x0=None, kick=None):
+    """the same for a quadcopter solution x (12,N+1), u (4,N): rollout_quad's chain over `shift` intervals (a step across cos x[3] = 0 is not ok)"""
+    x = np.asarray(x, float)
+    return _advance(lambda a, b, c, d, e: rollout_quad(a, b, c, d, e, False), 12, x, u, t, Ts, shift, substeps, x[:, 0] if x0 is None else x0, kick)
+
+
+def advance_record(x, X, c, state, xF, shift, substeps, need, step_time, logged=-1, ok=True):
+    """the ADV_OUT doubles of a step: rollout_record of the solution's nodes 0 .. shift against the driven states X (before the kick) with the clearances c (shift S + 1,
+    nOb) of the driven samples, then [10] 0, [11] S, [12] shift, [13] shift * step_time (step_time = t Ts), [14] the position distance (2 coordinates for nx = 4, else 3) of
+    `state` to xF, [15] logged.  shift 0: the maxima are 0, the node -1, [6..9] compare X_0 with the solution's node 0.  No obstacle (c has no column): min and min_nodes
+    +inf, sample and obstacle -1.  Not ok: as a bad rollout record, [13] and [14] NaN."""
+    x = np.asarray(x, float)[:, :shift + 1]; X = np.asarray(X, float); c = np.asarray(c, float); nx = x.shape[0]; S = int(substeps); npos = 2 if nx == 4 else 3
+    ok = bool(ok and np.isfinite(X).all() and np.isfinite(c).all() and np.isfinite(state).all())
+    if not ok:
+        r = rollout_record(x, np.full_like(X, np.nan), np.full((shift * S + 1, max(1, c.shape[1])), np.nan), S, False, need, False)
+        r[13] = r[14] = np.nan
+    else:
+        r = np.zeros(ROLL_OUT); r[11] = S
+        if c.shape[1]:
+            r[16:] = clearance_record(c, S, need, True)
+        else:
+            r[16:] = 0.0; r[[16, 17]] = np.inf; r[[18, 19]] = -1; r[21] = shift * S + 1; r[24:] = np.inf
+        xx = x if shift else np.c_[x, x]; XX = X if shift else np.c_[X, X]      # (shift 0: node 0 stands in for "node shift")
+        h = rollout_record(xx, XX, np.zeros((xx.shape[1] * S - S + 1, 1)), S, False, need, True)
+        r[:10] = h[:10]
+        if not shift:
+            r[1] = r[3] = r[4] = r[5] = 0.0; r[2] = -1
+        e = np.asarray(state, float)[:npos] - np.asarray(xF, float)[:npos]
+        r[13] = shift * step_time; r[14] = np.sqrt(sum(float(v) * float(v) for v in e))
+    r[10] = 0; r[12] = shift; r[15] = logged
+    return r
+
+
 # ---------------------------------------------------------------- closed-loop rollout: TVLQR gains about a trajectory (obca_amd/csrc/obca_track.h)
 TRK_OUT = 48          # doubles of a record: the ROLL_OUT doubles of the chain, feedback, clamp, saturated, du_max, du_node, dx0_pos, 2 x 0
 # Default weights: the values the first prototype ran with.  UNTUNED.
