@@ -66,6 +66,7 @@ def _load():
     cabi.bind(_lib, "obca_track.h")                       # ... and tracked on them by a time-varying LQR
     cabi.bind(_lib, "obca_ensemble.h")                    # ... from a spread of start offsets and input biases at once
     cabi.bind(_lib, "obca_advance.h")                     # the closed loop: the plant advanced under a solution and the next solve restarted from where it got
+    cabi.bind(_lib, "obca_scene_edit.h")                  # the obstacles of a resident batch moved and inflated in place
     cabi.bind(_lib, "obca_certify.h")                     # the clearance certified along the whole path
     return _lib
 
@@ -121,6 +122,9 @@ ENSEMBLE_EXPORTS = ["obca_batch_ensemble", "obca_batch_ensemble_ms", "obca_batch
 # advance_ms)
 ADVANCE_EXPORTS = ["obca_batch_advance", "obca_batch_advance_ms", "obca_batch_advance_state", "obca_batch_advance_log", "obca_batch_advance_log_states",
                    "obca_quad_batch_advance", "obca_quad_batch_advance_ms", "obca_quad_batch_advance_state", "obca_quad_batch_advance_log", "obca_quad_batch_advance_log_states"]
+# include/obca_scene_edit.h: the obstacles of a resident batch moved and inflated on the device (Batch.move_obstacles, QuadBatch.move_obstacles, obstacles, move_obstacles_ms)
+SCENE_EDIT_EXPORTS = ["obca_batch_move_obstacles", "obca_batch_move_obstacles_ms", "obca_batch_obstacles_download",
+                      "obca_quad_batch_move_obstacles", "obca_quad_batch_move_obstacles_ms", "obca_quad_batch_obstacles_download"]
 # include/obca_certify.h: the clearance of solutions and trajectories certified along the whole path by conservative advancement (Batch.certify, QuadBatch.certify,
 # certify_intervals, certify_ms, parking_certify_batch, quadcopter_certify_batch)
 CERTIFY_EXPORTS = ["obca_batch_certify", "obca_batch_certify_ms", "obca_batch_certify_intervals", "obca_parking_certify_batch", "obca_quad_batch_certify",
@@ -278,6 +282,31 @@ def _rollout_dict(rec, substeps, nOb):
     return dict(dev_pos=rec[:, 1], dev_node=rec[:, 2].astype(np.int64), dev_att=rec[:, 3], dev_vel=rec[:, 4], dev_rate=rec[:, 5], end_pos=rec[:, 6], end_att=rec[:, 7],
                 end_vel=rec[:, 8], end_rate=rec[:, 9], restart=rec[:, 10] != 0, substeps=rec[:, 11].astype(np.int64), finite=rec[:, 0] == 0,
                 clearance=_clearance_dict(rec[:, 16:], substeps, nOb))
+
+
+def _per_obstacle(v, nObs, width):
+    """a parameter of Batch.move_obstacles as the ABI takes it, (nOb_total, width) (width 0: (nOb_total,)) in upload order: one value ((width,) / a scalar) goes to every
+    obstacle, B rows go over each instance's obstacles, nOb_total rows are taken as they are; None stays NULL"""
+    if v is None:
+        return None
+    a = np.asarray(v, float); B, nt = len(nObs), int(np.sum(nObs)); tail = (width,) if width else ()
+    if a.shape == tail:
+        return _in(np.broadcast_to(a, (nt,) + tail))
+    if a.shape == (nt,) + tail:
+        return _in(a)
+    if a.shape == (B,) + tail:
+        return _in(np.repeat(a, np.asarray(nObs, np.int64), axis=0))
+    raise ValueError("move_obstacles: need a value of shape %s, (B,)+ it or (nOb_total,) + it, got %s" % (tail, a.shape))
+
+
+def _per_box(v, B, width):
+    """the same for QuadBatch.move_obstacles, 5 boxes per instance: (width,) / a scalar, (5,) + it, (B,) + it (B != 5) or (B, 5) + it -> (B, 5) + it"""
+    if v is None:
+        return None
+    a = np.asarray(v, float); tail = (width,) if width else ()
+    if a.shape == (B,) + tail and B != 5:
+        a = a.reshape((B, 1) + tail)
+    return _in(np.broadcast_to(a, (B, 5) + tail))
 
 
 def _advance(B, substeps, nOb, call):
@@ -536,7 +565,8 @@ class _DeviceBatch(_Handle):
 
     def certify_intervals(self):
         """[lb_k, seen_k] of the last certify(), fetched from the device: (B, N+1, 2) -- per interval (row N: node N) the proven bound and the smallest sampled clearance over
-        the obstacles; lb_k = -inf where an item of the interval was left undecided, NaN for an instance that was not finite."""
+        the obstacles; lb_k = -inf where an item of the interval was left undecided, NaN for an instance that was not finite.  They describe the scene
+        certify() ran in: a later move_obstacles() does not change them."""
         iv = np.zeros((self.B, self.N + 1, 2))
         self._call("certify_intervals", iv)
         return iv
@@ -550,7 +580,8 @@ class _DeviceBatch(_Handle):
 
     def rollout_states(self):
         """The node states of the last rollout(), fetched from the device: (B, N+1, nx), nx = 4 (parking) or 12 (quadcopter); NaN for an instance that was not finite.
-        rollout_states()[:, shift] of a chain-mode rollout is the state the vehicle reaches after `shift` intervals: the x0_new of shift_warm_start(shift, x0_new=...)."""
+        rollout_states()[:, shift] of a chain-mode rollout is the state the vehicle reaches after `shift` intervals: the x0_new of shift_warm_start(shift, x0_new=...).
+        The states do not depend on the obstacles; the clearances rollout() returned with them describe the scene it ran in, whatever move_obstacles() did later."""
         X = np.zeros((self.B, self.N + 1, self._nx))
         self._call("rollout_states", X)
         return X
@@ -589,6 +620,10 @@ class _DeviceBatch(_Handle):
     def advance_ms(self):
         """HIP-event duration of the last advance kernel"""
         return self._floats("advance_ms")
+
+    def move_obstacles_ms(self):
+        """HIP-event duration of the last move_obstacles kernel"""
+        return self._floats("move_obstacles_ms")
 
     def _track(self, nOb, defaults, substeps, dx0, Q, R, Qf, feedback, clamp, need):
         q, r, qf = _track_weights(self._nx, self._nu, Q, R, Qf, defaults)
@@ -810,6 +845,29 @@ class Batch(_DeviceBatch):
         of max_steps (undecided).  Returns the dict of _certify; 16 numbers per instance are downloaded, certify_intervals() fetches the per-interval bounds."""
         return self._certify(need, slack, max_steps)
 
+
+    def move_obstacles(self, motion=None, pivot=None, inflate=None):
+        """The obstacles of the uploaded batch MOVED AND INFLATED IN PLACE, ON THE DEVICE (obca_batch_move_obstacles; the numpy statement is
+        obca_amd.validate.move_obstacles_parking): obstacle j = {p : A p <= b} becomes its image under p' = R(dth)(p - c) + c + d and then grows by m metres (m < 0
+        shrinks it).  motion: (dx, dy, dth) as (3,) for every obstacle, (B,3) over each instance's obstacles or (nOb_total,3) packed in upload order; pivot: (cx, cy) as
+        (2,), (B,2) or (nOb_total,2), None: the world origin; inflate: m as a scalar, (B,) or (nOb_total,).  The batch may be solved or not, and stays what it was: the
+        solved state, the start iterate, the last solution and its multipliers, the plant state and the advance log are not touched, so shift_warm_start() / advance()
+        and a solve with warm_restart_opts() restart in the moved scene, validate() / clearance() / certify() of the held solution answer "is my plan still clear in the
+        scene as it is now", plan_warm_start() replans in the moved field, and refine() + move_obstacles(inflate=m) on the result is the parking margin.  What earlier
+        calls computed and kept -- certify_intervals(), rollout_states(), track_states(), ensemble_members(), plan_paths() -- describes the scene it was computed in.
+        Returns status (B,) int32: 0 moved; 1 marks an instance with a non-finite motion, pivot, inflation or result, ALONE -- its record keeps every bit.  With dth == 0
+        the words of A keep their bits; an obstacle with nothing to do keeps every bit.  obstacles(), move_obstacles_ms()."""
+        st = np.zeros(self.B, np.int32)
+        self._call("move_obstacles", _per_obstacle(motion, self.nObs, 3), _per_obstacle(pivot, self.nObs, 2), _per_obstacle(inflate, self.nObs, 0), st)
+        return st
+
+    def obstacles(self):
+        """The obstacle rows as the device holds them now: (A (M_total,2), b (M_total,)) packed as upload() takes them.  They are the UNIT-LENGTH rows of the problem
+        records -- not scaled back by the row lengths upload() divided out (the same half-planes; download() still returns lambda in the caller's scaling)."""
+        Mt = int(self.Ms.sum())
+        A = np.zeros((Mt, 2)); b = np.zeros(Mt)
+        self._call("obstacles_download", A, b)
+        return A, b
 
     def refine(self, factor=2, select=None, duals=False, into=None):
         """The solved instances `select` (an index array or a boolean mask over this batch's instances; None: all, duplicates allowed) on the horizon factor * N, ON THE
@@ -1218,6 +1276,21 @@ class QuadBatch(_DeviceBatch):
         on the continuous rigid body with kick (12,) or (B,12), restarted as shift_warm_start(shift, x0_new=<the plant state>, xF_new) restarts (xF_new: (12,) or (B,12),
         a moving goal).  Solve with quad_warm_restart_opts()."""
         return self._advance(5, shift, substeps, need, kick, xF_new)
+
+    def move_obstacles(self, motion=None, inflate=None):
+        """The five boxes of every instance moved and inflated in place, on the device (obca_quad_batch_move_obstacles; numpy: obca_amd.validate.move_obstacles_quad):
+        Batch.move_obstacles for axis-aligned boxes -- motion (dx, dy, dz) as (3,), (5,3), (B,3) or (B,5,3), inflate m as a scalar, (5,), (B,) or (B,5); a box
+        [ub, -lb] becomes [ub + d + m, -(lb + d) + m]; R is not touched.  Returns status (B,) int32 (1: non-finite, that instance keeps every bit).  Results earlier
+        calls kept (certify_intervals(), rollout_states(), ...) describe the scene they were computed in."""
+        st = np.zeros(self.B, np.int32)
+        self._call("move_obstacles", _per_box(motion, self.B, 3), _per_box(inflate, self.B, 0), st)
+        return st
+
+    def obstacles(self):
+        """The boxes as the device holds them now: (B, 5, 6), [ub(3), -lb(3)] per box"""
+        ob = np.zeros((self.B, 5, 6))
+        self._call("obstacles_download", ob)
+        return ob
 
     def track(self, substeps=8, dx0=None, Q=None, R=None, Qf=None, feedback=True, clamp=True, need=0.0):
         """The last solution tracked on the continuous rigid body by a time-varying LQR about it, on the device (obca_quad_batch_track; numpy:

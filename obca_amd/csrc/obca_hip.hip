@@ -11,6 +11,7 @@
 //   obca_track_*_kernel     : one wavefront per instance, TVLQR gains about a solution or a caller's trajectory and the closed loop rolled on the continuous model (obca_track.h).
 //   obca_ensemble_*_kernel  : one wavefront per instance, one member per lane: up to 64 disturbed closed loops about a solution or a caller's trajectory, the gains computed once (obca_ensemble.h).
 //   obca_advance_*_kernel   : one wavefront per instance, one step of the closed receding-horizon loop: the plant over the first `shift` intervals of the solution, the restart from the state it reached (obca_advance.h).
+//   obca_move_*_kernel      : one wavefront per instance, the obstacle words of the problem records moved and inflated in place, all or nothing per instance (obca_scene_edit.h).
 //   obca_certify_*_kernel   : one wavefront per instance, the clearance of a solution or of a caller's trajectory certified along its whole path by conservative advancement (obca_certify.h).
 //   obca_refine_*_kernel    : one wavefront per destination instance, a solved parking instance on a finer horizon (obca_refine.h): into a second resident batch or host-bound arrays.
 //   obca_quad_subdivide_*_kernel : the same for a solved quadcopter instance (obca_quad_subdivide.h): it rewrites a problem record.
@@ -49,6 +50,7 @@
 #include "obca_track.h"
 #include "obca_ensemble.h"
 #include "obca_advance.h"
+#include "obca_scene_edit.h"
 #include "obca_certify.h"
 #include "../../include/obca_hip.h"
 #include "../../include/obca_path_ws.h"
@@ -59,6 +61,7 @@
 #include "../../include/obca_track.h"
 #include "../../include/obca_ensemble.h"
 #include "../../include/obca_advance.h"
+#include "../../include/obca_scene_edit.h"
 #include "../../include/obca_certify.h"
 
 using namespace obca;
@@ -416,6 +419,19 @@ __global__ __launch_bounds__(QNT) void obca_advance_quad_kernel(int B, int N, in
                                out + (size_t)inst * AV_OUT);
 }
 
+// the obstacles of the records moved and inflated in place (obca_scene_edit.h): one wavefront per instance; `in`: s_in doubles per instance (SE_PIN per obstacle / SE_QIN per
+// box), `out`: the status, one double per instance
+__global__ __launch_bounds__(OB_NT) void obca_move_parking_kernel(int B, double *prob, size_t s_prob, const double *in, size_t s_in, double *out) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    sed::move_parking_instance(prob + (size_t)inst * s_prob, in + (size_t)inst * s_in, 0, out + inst);
+}
+__global__ __launch_bounds__(QNT) void obca_move_quad_kernel(int B, double *prob, size_t s_prob, const double *in, double *out) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    sed::move_quad_instance(prob + (size_t)inst * s_prob, in + (size_t)inst * QOB * SE_QIN, 0, out + inst);
+}
+
 // clearance certificate (obca_certify.h): one wavefront per instance; the arguments of the clearance kernels with need, slack and max_steps in place of the sub-steps, then
 // the interval array (2 (N + 1) per instance).  The item table is the launch's dynamic LDS: cert::certify_work_len(N, the batch's most obstacles) doubles
 template <int VM>
@@ -645,6 +661,7 @@ struct BatchCore {
     DevBuf adv_w, adv_st, adv_log;                          // [ sample poses 3 x (shift S + 1) | node states nx x (shift + 1) ] x B; the plant states nx x B; the log B x adv_cap x nx
     int adv_B = 0, adv_N = 0;                               // the instances and horizon of the last advance (0: none yet): adv_st holds its plant states
     int adv_cap = 0, adv_n = 0;                             // the log's rows per instance (0: no log) and the nodes in it
+    ValBufs mov;                                            // ... and for the move calls (obca_scene_edit.h): the motions go up, a status per instance comes down
     ValBufs cer;                                            // ... and for the certify calls (obca_certify.h)
     DevBuf cer_iv;                                          // their interval arrays, 2 (N + 1) x B
     int cer_B = 0, cer_N = 0;                               // the instances and horizon of the last certify call (0: none yet)
@@ -712,7 +729,7 @@ static void core_release(BatchCore *bt) {
     bt->rol_w.release(); bt->trk_w.release(); bt->trk_K.release();
     bt->ens_w.release(); bt->ens_K.release(); bt->ens_mem.release(); bt->ens_fin.release(); bt->cer_iv.release();
     bt->adv_w.release(); bt->adv_st.release(); bt->adv_log.release();
-    for (ValBufs *pv : {&bt->val, &bt->clr, &bt->rol, &bt->trk, &bt->ens, &bt->cer, &bt->adv}) {
+    for (ValBufs *pv : {&bt->val, &bt->clr, &bt->rol, &bt->trk, &bt->ens, &bt->cer, &bt->adv, &bt->mov}) {
         ValBufs &v = *pv;
         v.d_in.release(); v.d_out.release(); v.h_in.release(); v.h_out.release(); v.ev.release();
     }
@@ -1716,6 +1733,46 @@ int obca_batch_advance_state(obca_batch *bt, double *X) { return bt ? advance_st
 int obca_batch_advance_log(obca_batch *bt, int capacity_nodes) { return bt ? advance_log(bt, 4, capacity_nodes, "obca_batch_advance_log") : -1; }
 int obca_batch_advance_log_states(obca_batch *bt, double *X, int *nodes) { return bt ? advance_log_states(bt, 4, X, nodes, "obca_batch_advance_log_states") : -1; }
 
+// obca_scene_edit.h.  The motions are staged through the call's own pinned and device buffers (bt->mov), SE_PIN doubles per obstacle in rows of nObMax obstacles; the
+// kernel edits d.prob in place.  Nothing of the host's state describes the geometry: h_prob is staging, rowLen / vmx / vmax / nOb / M hold lengths and counts, which stand.
+int obca_batch_move_obstacles(obca_batch *bt, const double *motion, const double *pivot, const double *inflate, int *status) {
+    if (!bt) return -1;
+    if (!status) { bt->ctx->err = "obca_batch_move_obstacles: NULL argument"; return -1; }
+    if (!bt->uploaded) { bt->ctx->err = "obca_batch_move_obstacles: nothing uploaded"; return -1; }
+    const int B = bt->B; const size_t s_in = (size_t)SE_PIN * bt->nObMax;
+    return fin(bt, run_validate(bt, bt->mov, s_in, true, 1, [&](int i, double *a) {
+        memset(a, 0, sizeof(double) * s_in);
+        const size_t o = (size_t)(bt->obOff[i] - bt->obOff[0]);
+        for (int j = 0; j < bt->nOb[i]; j++) {
+            double *m = a + SE_PIN * j;
+            if (motion) { m[0] = motion[3 * (o + j)]; m[1] = motion[3 * (o + j) + 1]; m[2] = motion[3 * (o + j) + 2]; }
+            if (pivot) { m[3] = pivot[2 * (o + j)]; m[4] = pivot[2 * (o + j) + 1]; }
+            if (inflate) m[5] = inflate[o + j];
+        }
+    }, [&] {
+        hipLaunchKernelGGL(obca_move_parking_kernel, dim3(B), dim3(OB_NT), 0, bt->stream, B, bt->d.prob, bt->d.s_prob, (const double *)bt->mov.d_in, s_in, (double *)bt->mov.d_out);
+    }, [&](int i, const double *o) { status[i] = o[0] != 0.0; }));
+}
+int obca_batch_move_obstacles_ms(obca_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->mov.ev, ms, "obca_batch_move_obstacles_ms: no move call has run on this batch") : -1; }
+int obca_batch_obstacles_download(obca_batch *bt, double *A, double *b) {
+    if (!bt) return -1;
+    if (!A && !b) { bt->ctx->err = "obca_batch_obstacles_download: NULL arguments"; return -1; }
+    if (!bt->uploaded) { bt->ctx->err = "obca_batch_obstacles_download: nothing uploaded"; return -1; }
+    const DevBufs &d = bt->d; const size_t B = bt->B;
+    use_device(bt->device);
+    // through the pinned problem staging of the batch (an upload refills it): the records as they lie
+    if (bt->h_prob.reserve(bt->err, (size_t)bt->cap * d.s_prob)) return fin(bt, -2);
+    if (hipMemcpyAsync(bt->h_prob, d.prob, B * d.s_prob * sizeof(double), hipMemcpyDeviceToHost, bt->stream) != hipSuccess || hipStreamSynchronize(bt->stream) != hipSuccess) {
+        bt->ctx->err = "obca_batch_obstacles_download: copy failed"; return -2;
+    }
+    for (size_t i = 0; i < B; i++) {
+        const double *p = bt->h_prob + i * d.s_prob; const size_t r0 = (size_t)(bt->rowOff[i] - bt->rowOff[0]), m = (size_t)bt->M[i];
+        if (A) memcpy(A + 2 * r0, p + PH_A, sizeof(double) * 2 * m);
+        if (b) memcpy(b + r0, p + PH_B, sizeof(double) * m);
+    }
+    return 0;
+}
+
 int obca_batch_certify(obca_batch *bt, double need, double slack, int max_steps, double *out) {
     if (!bt) return -1;
     if (!out) { bt->ctx->err = "obca_batch_certify: NULL argument"; return -1; }
@@ -2362,6 +2419,35 @@ int obca_quad_batch_advance_ms(obca_quad_batch *bt, float *ms) { return bt && ms
 int obca_quad_batch_advance_state(obca_quad_batch *bt, double *X) { return bt ? advance_state(bt, QX, X, "obca_quad_batch_advance_state") : -1; }
 int obca_quad_batch_advance_log(obca_quad_batch *bt, int capacity_nodes) { return bt ? advance_log(bt, QX, capacity_nodes, "obca_quad_batch_advance_log") : -1; }
 int obca_quad_batch_advance_log_states(obca_quad_batch *bt, double *X, int *nodes) { return bt ? advance_log_states(bt, QX, X, nodes, "obca_quad_batch_advance_log_states") : -1; }
+
+// obca_scene_edit.h for the quadcopter: SE_QIN doubles per box go up, the kernel edits the QPH_OB words of d.prob in place
+int obca_quad_batch_move_obstacles(obca_quad_batch *bt, const double *motion, const double *inflate, int *status) {
+    if (!bt) return -1;
+    if (!status) { bt->ctx->err = "obca_quad_batch_move_obstacles: NULL argument"; return -1; }
+    if (!bt->uploaded) { bt->ctx->err = "obca_quad_batch_move_obstacles: nothing uploaded"; return -1; }
+    const int B = bt->B;
+    return fin(bt, run_validate(bt, bt->mov, (size_t)QOB * SE_QIN, true, 1, [&](int i, double *a) {
+        for (int j = 0; j < QOB; j++) {
+            const size_t g = (size_t)i * QOB + j;
+            for (int q = 0; q < 3; q++) a[SE_QIN * j + q] = motion ? motion[3 * g + q] : 0.0;
+            a[SE_QIN * j + 3] = inflate ? inflate[g] : 0.0;
+        }
+    }, [&] {
+        hipLaunchKernelGGL(obca_move_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, bt->d.prob, bt->d.s_prob, (const double *)bt->mov.d_in, (double *)bt->mov.d_out);
+    }, [&](int i, const double *o) { status[i] = o[0] != 0.0; }));
+}
+int obca_quad_batch_move_obstacles_ms(obca_quad_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->mov.ev, ms, "obca_quad_batch_move_obstacles_ms: no move call has run on this batch") : -1; }
+int obca_quad_batch_obstacles_download(obca_quad_batch *bt, double *ob) {
+    if (!bt) return -1;
+    if (!ob) { bt->ctx->err = "obca_quad_batch_obstacles_download: NULL argument"; return -1; }
+    if (!bt->uploaded) { bt->ctx->err = "obca_quad_batch_obstacles_download: nothing uploaded"; return -1; }
+    use_device(bt->device);
+    if (hipStreamSynchronize(bt->stream) != hipSuccess ||
+        hipMemcpy2D(ob, sizeof(double) * QOB * QL, bt->d.prob + QPH_OB, bt->d.s_prob * sizeof(double), sizeof(double) * QOB * QL, (size_t)bt->B, hipMemcpyDeviceToHost) != hipSuccess) {
+        bt->ctx->err = "obca_quad_batch_obstacles_download: copy failed"; return -2;
+    }
+    return 0;
+}
 
 int obca_quad_batch_certify(obca_quad_batch *bt, double need, double slack, int max_steps, double *out) {
     if (!bt) return -1;

@@ -451,6 +451,48 @@ def advance_record(x, X, c, state, xF, shift, substeps, need, step_time, logged=
     return r
 
 
+# ---------------------------------------------------------------- the obstacles of a resident batch moved and inflated in place (obca_amd/csrc/obca_scene_edit.h)
+def move_obstacles_parking(A, b, vOb, motion=None, pivot=None, inflate=None):
+    """One instance's unit-length rows A (M,2), b (M,) with the row counts vOb after its obstacles have moved: obstacle j = {p : A p <= b} becomes its image under
+    p' = R(dth)(p - c) + c + d, then grows by m -- motion (nOb,3) = (dx, dy, dth), pivot (nOb,2) = (cx, cy), inflate (nOb,) = m; None: zeros.  Row by row, the kernel's
+    operations in the kernel's order: a' = (cos a1 - sin a2, sin a1 + cos a2) where dth != 0 (else `a` itself, bit for bit), b' = ((b + (a1' (cx + dx) + a2' (cy + dy))) -
+    (a1 cx + a2 cy)) + m where any of dx, dy, dth, m is not 0 (else b itself).  Returns (A', b', ok); not ok (a non-finite parameter or result): A, b are returned as
+    they came, all or nothing."""
+    A = np.array(A, float).reshape(-1, 2); b = np.array(b, float).ravel(); v = np.asarray(vOb, np.int64).ravel(); n = len(v)
+    mo = np.zeros((n, 3)) if motion is None else np.asarray(motion, float).reshape(n, 3)
+    pv = np.zeros((n, 2)) if pivot is None else np.asarray(pivot, float).reshape(n, 2)
+    mg = np.zeros(n) if inflate is None else np.asarray(inflate, float).reshape(n)
+    A2, b2 = A.copy(), b.copy(); r = 0
+    for j in range(n):
+        dx, dy, th = (float(t) for t in mo[j]); cx, cy = (float(t) for t in pv[j]); m = float(mg[j])
+        rot = th != 0.0; any_ = rot or dx != 0.0 or dy != 0.0 or m != 0.0
+        with np.errstate(invalid="ignore"):      # (an infinite angle: NaN, reported as not ok)
+            s, c = (float(np.sin(th)), float(np.cos(th))) if rot else (0.0, 1.0)
+        for _ in range(int(v[j])):
+            o1, o2 = float(A[r, 0]), float(A[r, 1]); a1, a2 = o1, o2
+            if rot:
+                a1 = c * o1 - s * o2; a2 = s * o1 + c * o2
+                A2[r] = a1, a2
+            if any_:
+                b2[r] = ((float(b[r]) + (a1 * (cx + dx) + a2 * (cy + dy))) - (o1 * cx + o2 * cy)) + m
+            r += 1
+    ok = bool(np.isfinite(mo).all() and np.isfinite(pv).all() and np.isfinite(mg).all() and np.isfinite(A2).all() and np.isfinite(b2).all())
+    return (A2, b2, True) if ok else (A, b, False)
+
+
+def move_obstacles_quad(ob, motion=None, inflate=None):
+    """One instance's five boxes ob (5,6) = [ub(3), -lb(3)] after a motion (5,3) = (dx, dy, dz) and an inflation (5,) per box (None: zeros): word i < 3 becomes
+    (ob[i] + d_i) + m, word 3 + i becomes (ob[3 + i] - d_i) + m, a word whose d_i and m are both 0 keeps its bits.  Returns (ob', ok); not ok: ob as it came."""
+    ob = np.array(ob, float).reshape(5, 6)
+    d = np.zeros((5, 3)) if motion is None else np.asarray(motion, float).reshape(5, 3)
+    m = np.zeros(5) if inflate is None else np.asarray(inflate, float).reshape(5)
+    dd = np.c_[d, -d]; mm = np.repeat(m[:, None], 6, 1)
+    with np.errstate(invalid="ignore"):
+        out = np.where((dd != 0.0) | (mm != 0.0), (ob + dd) + mm, ob)
+    ok = bool(np.isfinite(d).all() and np.isfinite(m).all() and np.isfinite(out).all())
+    return (out, True) if ok else (ob, False)
+
+
 # ---------------------------------------------------------------- closed-loop rollout: TVLQR gains about a trajectory (obca_amd/csrc/obca_track.h)
 TRK_OUT = 48          # doubles of a record: the ROLL_OUT doubles of the chain, feedback, clamp, saturated, du_max, du_node, dx0_pos, 2 x 0
 # Default weights: the values the first prototype ran with.  UNTUNED.
