@@ -22,7 +22,7 @@ import numpy as np
 from . import buildflags, cabi, planner
 from .cabi import Opts      # `typedef struct obca_opts` of include/obca_hip.h, read from the header
 from .validate import (VIOL_NAMES, QUAD_VIOL_NAMES, DMIN, CLR_OUT, ROLL_OUT, TRK_OUT, TRACK_Q_PARKING, TRACK_R_PARKING, TRACK_QF_PARKING, TRACK_Q_QUAD, TRACK_R_QUAD,
-                       TRACK_QF_QUAD, ENS_MEM, ENS_OUT, ENS_MMAX, CERT_OUT, CERT_TICKS, ADV_OUT)
+                       TRACK_QF_QUAD, ENS_MEM, ENS_OUT, ENS_MMAX, CERT_OUT, CERT_TICKS, ADV_OUT, PRD_OUT)
 
 _LIBPATH = os.environ.get("OBCA_HIP_LIBRARY") or buildflags.PIECES["hip"].out   # override: diagnostic builds
 _lib = None
@@ -68,6 +68,7 @@ def _load():
     cabi.bind(_lib, "obca_advance.h")                     # the closed loop: the plant advanced under a solution and the next solve restarted from where it got
     cabi.bind(_lib, "obca_scene_edit.h")                  # the obstacles of a resident batch moved and inflated in place
     cabi.bind(_lib, "obca_certify.h")                     # the clearance certified along the whole path
+    cabi.bind(_lib, "obca_predict.h")                     # the clearance of a held plan against obstacles that move
     return _lib
 
 
@@ -129,6 +130,10 @@ SCENE_EDIT_EXPORTS = ["obca_batch_move_obstacles", "obca_batch_move_obstacles_ms
 # certify_intervals, certify_ms, parking_certify_batch, quadcopter_certify_batch)
 CERTIFY_EXPORTS = ["obca_batch_certify", "obca_batch_certify_ms", "obca_batch_certify_intervals", "obca_parking_certify_batch", "obca_quad_batch_certify",
                    "obca_quad_batch_certify_ms", "obca_quad_batch_certify_intervals", "obca_quadcopter_certify_batch"]
+# include/obca_predict.h: the clearance of held solutions and trajectories against obstacles that move at given rates (Batch.predict_clearance, QuadBatch.predict_clearance,
+# predict_profile, predict_clearance_ms, parking_predict_batch, quadcopter_predict_batch)
+PREDICT_EXPORTS = ["obca_batch_predict_clearance", "obca_batch_predict_clearance_ms", "obca_batch_predict_profile", "obca_parking_predict_batch",
+                   "obca_quad_batch_predict_clearance", "obca_quad_batch_predict_clearance_ms", "obca_quad_batch_predict_profile", "obca_quadcopter_predict_batch"]
 QUAD_PLAN_STATUS = {0: "no path", -1: "more way-points than cap", -2: "the start or goal point is blocked, or a coordinate of the record is not finite",
                     -3: "the relaxation hit its sweep bound", -4: "not selected"}
 QUAD_REFINE_STATUS = {0: "refined from the solution", 1: "interpolated from the uploaded warm start (the last solve failed, or its iterate is not finite)",
@@ -307,6 +312,38 @@ def _per_box(v, B, width):
     if a.shape == (B,) + tail and B != 5:
         a = a.reshape((B, 1) + tail)
     return _in(np.broadcast_to(a, (B, 5) + tail))
+
+
+def _parking_rates(nObs, rates, pivot, grow):
+    """the rate records of Batch.predict_clearance as the ABI takes them, (nOb_total, 6) = [vx, vy, w, cx, cy, g] per obstacle in upload order: each of the three
+    parameters goes through _per_obstacle, as move_obstacles packs its motion, pivot and inflate; None: zeros"""
+    out = np.zeros((int(np.sum(nObs)), 6))
+    for v, cols, width in ((rates, slice(0, 3), 3), (pivot, slice(3, 5), 2), (grow, 5, 0)):
+        a = _per_obstacle(v, nObs, width)
+        if a is not None:
+            out[:, cols] = a
+    return out
+
+
+def _quad_rates(B, rates, grow):
+    """the same for QuadBatch.predict_clearance through _per_box: (B, 5, 4) = [vx, vy, vz, g] per box"""
+    out = np.zeros((B, 5, 4))
+    for v, cols, width in ((rates, slice(0, 3), 3), (grow, 3, 0)):
+        a = _per_box(v, B, width)
+        if a is not None:
+            out[:, :, cols] = a
+    return out
+
+
+def _predict(B, substeps, nOb, call):
+    """the records of a predict entry point, `call(out)` with out (B, PRD_OUT), and the dict they are returned in: the dict of _clearance for the samples measured against
+    the obstacles where they will be when the vehicle reaches them, and first (B,) the first sample whose smallest clearance is < need (-1: none), t_first its time in
+    seconds (+inf: none; finite: an instance to re-solve now), first_obstacle (-1: none), t_min the time of `sample`, horizon the time of the last sample, moving the
+    obstacles with a rate that is not 0.  finite False: a non-finite number in the trajectory or the rates, or a moved row that is not finite -- the times are NaN"""
+    rec = np.zeros((B, PRD_OUT))
+    call(rec)
+    return dict(_clearance_dict(rec, substeps, nOb), first=rec[:, 24].astype(np.int64), t_first=rec[:, 25], first_obstacle=rec[:, 26].astype(np.int64), t_min=rec[:, 27],
+                horizon=rec[:, 28], moving=rec[:, 29].astype(np.int64))
 
 
 def _advance(B, substeps, nOb, call):
@@ -625,6 +662,25 @@ class _DeviceBatch(_Handle):
         """HIP-event duration of the last move_obstacles kernel"""
         return self._floats("move_obstacles_ms")
 
+    def _predict(self, nOb, rates, substeps, need, profile):
+        r = _predict(self.B, substeps, nOb, lambda out: self._call("predict_clearance", _in(rates).reshape(-1), int(substeps), float(need), int(bool(profile)), out))
+        if profile:
+            self._predict_S = int(substeps)
+        return r
+
+    def predict_profile(self):
+        """The clearance-over-time profile of the last predict_clearance(profile=True), fetched from the device: (B, N substeps + 1) -- per sample the smallest predicted
+        clearance over the obstacles; a row of NaN for an instance that was not finite.  Sample q is reached at the time the numpy statement
+        obca_amd.validate.predict_times gives.  The buffer costs 8 B (N substeps + 1) bytes of device memory and stays with the batch."""
+        S = getattr(self, "_predict_S", 0)
+        out = np.zeros((self.B, self.N * S + 1))
+        self._call("predict_profile", out.reshape(-1), out.size if S else 0)
+        return out
+
+    def predict_clearance_ms(self):
+        """HIP-event duration of the last predict_clearance kernel"""
+        return self._floats("predict_clearance_ms")
+
     def _track(self, nOb, defaults, substeps, dx0, Q, R, Qf, feedback, clamp, need):
         q, r, qf = _track_weights(self._nx, self._nu, Q, R, Qf, defaults)
         return _track(self.B, substeps, nOb, lambda out: self._call("track", int(substeps), int(feedback), int(clamp), q, r, qf, _track_dx0(dx0, self.B, self._nx), float(need), out))
@@ -845,6 +901,16 @@ class Batch(_DeviceBatch):
         of max_steps (undecided).  Returns the dict of _certify; 16 numbers per instance are downloaded, certify_intervals() fetches the per-interval bounds."""
         return self._certify(need, slack, max_steps)
 
+    def predict_clearance(self, rates=None, pivot=None, grow=None, substeps=8, need=DMIN, profile=False):
+        """Clearance of the last solution against obstacles that MOVE while it is driven, ON THE DEVICE (obca_batch_predict_clearance; the numpy statement is
+        obca_amd.validate.predict_parking + predict_record).  clearance() holds the scene as it stands now for the whole horizon; here sample q, reached at the time
+        tau_q = (sum of the t_k before its interval + (s / S) t_k) Ts, is measured against the scene move_obstacles(rates * tau_q, pivot, grow * tau_q) WOULD make --
+        nothing is written to the batch.  rates: (vx, vy, w) per second as (3,), (B,3) or (nOb_total,3); pivot: (cx, cy) as move_obstacles takes it; grow: g metres per
+        second of margin (prediction uncertainty that widens with time) as a scalar, (B,) or (nOb_total,); None: zeros.  Returns the dict of _predict: the dict of
+        clearance() and first / t_first (the first sample under `need` and its time: an instance with a finite t_first is one to re-solve now), first_obstacle, t_min,
+        horizon, moving.  With all rates 0 it is clearance().  inflate = rate x horizon can be checked here before a refine() pays for it; after advance() and
+        move_obstacles() the same call answers for the new step.  profile=True keeps the smallest clearance of every sample on the device: predict_profile()."""
+        return self._predict(int(self.nObs.max()), _parking_rates(self.nObs, rates, pivot, grow), substeps, need, profile)
 
     def move_obstacles(self, motion=None, pivot=None, inflate=None):
         """The obstacles of the uploaded batch MOVED AND INFLATED IN PLACE, ON THE DEVICE (obca_batch_move_obstacles; the numpy statement is
@@ -1130,6 +1196,22 @@ def parking_clearance_batch(N, Ts, L, ego, vOb, A, b, x, u, timeScale=None, subs
     return _clearance(B, substeps, int(nObs.max()), lambda out: ctx._check(_load().obca_parking_clearance_batch(ctx._h, B, N, *ins, out), "obca_parking_clearance_batch"))
 
 
+def parking_predict_batch(N, Ts, L, ego, vOb, A, b, x, u, timeScale=None, rates=None, pivot=None, grow=None, substeps=8, need=DMIN, device=0, profile=False):
+    """Batch.predict_clearance for arbitrary trajectories (obca_parking_predict_batch): the arguments of parking_clearance_batch up to timeScale, then those of
+    Batch.predict_clearance.  Returns its dict, with `profile` (B, N substeps + 1) if asked for."""
+    x = np.asarray(x, float); u = np.asarray(u, float); N = int(N); B = x.shape[0]
+    if x.shape != (B, 4, N + 1) or u.shape != (B, 2, N):
+        raise ObcaError(f"x must be (B,4,N+1) and u (B,2,N); got {x.shape}, {u.shape}")
+    ctx = _ctx(device)
+    nObs, vflat, Aflat, bflat = _norm_obstacles(B, vOb, A, b)
+    ins = (_per_instance(Ts, B), L, _in(ego), _in(nObs, np.int32), _in(vflat, np.int32), _in(Aflat), _in(bflat), _in(np.transpose(x, (0, 2, 1))), _in(np.transpose(u, (0, 2, 1))),
+           None if timeScale is None else _time_scale(timeScale, B, N + 1), int(substeps), float(need))
+    rt = _parking_rates(nObs, rates, pivot, grow).reshape(-1); pr = np.zeros((B, N * max(int(substeps), 0) + 1)) if profile else None
+    r = _predict(B, substeps, int(nObs.max()), lambda out: ctx._check(_load().obca_parking_predict_batch(ctx._h, B, N, *ins, out, rt, None if pr is None else pr.reshape(-1)),
+                                                                     "obca_parking_predict_batch"))
+    return dict(r, profile=pr) if profile else r
+
+
 def ParkingConstraints(x0, xF, N, Ts, L, ego, XYbounds, nOb, vOb, A, b, x, u, l, n, timeScale, fixTime, sd, device=0):
     """Drop-in for ParkingConstraints.jl:29 (one instance): 1 if the reference's own acceptance test passes at 5e-5, else 0 (sd = 1: signed-distance formulation)."""
     assert int(nOb) == len(np.ravel(vOb))
@@ -1314,6 +1396,12 @@ class QuadBatch(_DeviceBatch):
         certify_record): Batch.certify on the straight segment of every interval, speed bound |v_k|, clearance = distance of the point to a box - R."""
         return self._certify(need, slack, max_steps)
 
+    def predict_clearance(self, rates=None, grow=None, substeps=8, need=0.0, profile=False):
+        """Clearance of the last solution against boxes that move while it is flown, on the device (obca_quad_batch_predict_clearance; numpy:
+        obca_amd.validate.predict_quad + predict_record): Batch.predict_clearance for axis-aligned boxes -- rates (vx, vy, vz) per second as (3,), (5,3), (B,3) or
+        (B,5,3), grow g per second as a scalar, (5,), (B,) or (B,5); sample q is measured against the boxes move_obstacles(rates * tau_q, grow * tau_q) would make."""
+        return self._predict(5, _quad_rates(self.B, rates, grow), substeps, need, profile)
+
     def refine(self, factor=2, select=None, margin=0.0, into=None):
         """The solved instances `select` (an index array or a boolean mask over this batch's instances; None: all, duplicates allowed) on the horizon factor * N, ON THE
         DEVICE (obca_quad_batch_subdivide_into; the numpy statement is obca_amd.validate.refine_quad): the same NLP with Ts / factor and the radius R + margin, and as
@@ -1388,6 +1476,20 @@ def quadcopter_clearance_batch(x, timeScale, Ts, ob, R, substeps=8, need=0.0, de
     ctx = _ctx(device)
     ins = (_per_instance(Ts, B), R, _boxes(ob, B), _in(np.transpose(x, (0, 2, 1))), _time_scale(1.0 if timeScale is None else timeScale, B, N1), int(substeps), float(need))
     return _clearance(B, substeps, 5, lambda out: ctx._check(_load().obca_quadcopter_clearance_batch(ctx._h, B, N1 - 1, *ins, out), "obca_quadcopter_clearance_batch"))
+
+
+def quadcopter_predict_batch(x, timeScale, Ts, ob, R, rates=None, grow=None, substeps=8, need=0.0, device=0, profile=False):
+    """QuadBatch.predict_clearance for arbitrary trajectories (obca_quadcopter_predict_batch): the arguments of quadcopter_clearance_batch up to R, then those of
+    QuadBatch.predict_clearance.  Returns its dict, with `profile` (B, N substeps + 1) if asked for."""
+    x = np.asarray(x, float); B, _, N1 = x.shape
+    if x.shape != (B, 12, N1):
+        raise ObcaError(f"x must be (B,12,N+1); got {x.shape}")
+    ctx = _ctx(device)
+    ins = (_per_instance(Ts, B), R, _boxes(ob, B), _in(np.transpose(x, (0, 2, 1))), _time_scale(1.0 if timeScale is None else timeScale, B, N1), int(substeps), float(need))
+    rt = _quad_rates(B, rates, grow).reshape(-1); pr = np.zeros((B, (N1 - 1) * max(int(substeps), 0) + 1)) if profile else None
+    r = _predict(B, substeps, 5, lambda out: ctx._check(_load().obca_quadcopter_predict_batch(ctx._h, B, N1 - 1, *ins, out, rt, None if pr is None else pr.reshape(-1)),
+                                                        "obca_quadcopter_predict_batch"))
+    return dict(r, profile=pr) if profile else r
 
 
 def quadcopter_certify_batch(x, timeScale, Ts, ob, R, need=0.0, slack=0.01, max_steps=CERT_TICKS, device=0, intervals=True):

@@ -65,10 +65,11 @@ CHECK_PIECES = {"clearance_emu": _piece(GXX, ["-O1"], os.path.join(_EMU, "libobc
 # track_emu: obca_amd/csrc/obca_track.h over it for the host (tests/test_track_cpu.py); ensemble_emu: obca_amd/csrc/obca_ensemble.h over both (tests/test_ensemble_cpu.py);
 # certify_emu: obca_amd/csrc/obca_certify.h over obca_clearance.h (tests/test_certify_cpu.py); shift_emu: obca_amd/csrc/obca_shift.h, the parking receding-horizon
 # restart (tests/test_shift_cpu.py); advance_emu: obca_amd/csrc/obca_advance.h over the rollout and both shifts, the closed-loop step (tests/test_advance_cpu.py);
-# scene_edit_emu: obca_amd/csrc/obca_scene_edit.h over obca_validate.h, the obstacles of a resident batch moved in place (tests/test_scene_edit_cpu.py).
+# scene_edit_emu: obca_amd/csrc/obca_scene_edit.h over obca_validate.h, the obstacles of a resident batch moved in place (tests/test_scene_edit_cpu.py);
+# predict_emu: obca_amd/csrc/obca_predict.h over obca_clearance.h, the clearance of a held plan against obstacles that move (tests/test_predict_cpu.py).
 EMU_PIECES = {_n: _piece(GXX, ["-O1"], os.path.join(_EMU, "libobca_%s.so" % _n), os.path.join(_EMU, _n + ".cpp"))
               for _n in ("refine_emu", "quad_subdivide_emu", "hybrid_emu", "scenes_emu", "plan_resident_emu", "quad_plan_resident_emu", "rollout_emu", "track_emu", "ensemble_emu", "certify_emu",
-                         "shift_emu", "advance_emu", "scene_edit_emu")}
+                         "shift_emu", "advance_emu", "scene_edit_emu", "predict_emu")}
 DEFAULT = [n for n in PIECES if n not in ("hip_prof", "hip_poison", "hip_poison_1e30")]      # what __graft_entry__.build() compiles
 
 

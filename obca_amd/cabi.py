@@ -1,4 +1,4 @@
-"""The C ABI as the Python side sees it, read ONCE from the public headers (include/obca_hip.h, obca_path_ws.h, obca_clearance.h, obca_refine.h, obca_quad_subdivide.h, obca_plan_device.h, obca_plan_scenes.h, obca_plan_resident.h, obca_plan_resident_check.h, obca_quad_plan_resident.h, obca_rollout.h, obca_track.h, obca_ensemble.h, obca_advance.h, obca_scene_edit.h, obca_certify.h, obca_plan.h, obca_plan3d.h, obca_diag.h): `bind(lib, header)` gives every
+"""The C ABI as the Python side sees it, read ONCE from the public headers (include/obca_hip.h, obca_path_ws.h, obca_clearance.h, obca_refine.h, obca_quad_subdivide.h, obca_plan_device.h, obca_plan_scenes.h, obca_plan_resident.h, obca_plan_resident_check.h, obca_quad_plan_resident.h, obca_rollout.h, obca_track.h, obca_ensemble.h, obca_advance.h, obca_scene_edit.h, obca_certify.h, obca_predict.h, obca_plan.h, obca_plan3d.h, obca_diag.h): `bind(lib, header)` gives every
 function `lib` exports the `restype` and `argtypes` its prototype declares, `Opts` is `typedef struct obca_opts`.  The call sites of api.py, planner.py and diag.py then pass
 Python numbers and prepared numpy arrays and say nothing about C types; a miscounted argument, an array of another dtype, a non-contiguous view or a read-only output buffer
 is a TypeError on the CPU, before anything reaches the library.  The subset of C the headers use is all that is parsed; a parameter of another kind raises when the library is

@@ -12,6 +12,7 @@
 //   obca_ensemble_*_kernel  : one wavefront per instance, one member per lane: up to 64 disturbed closed loops about a solution or a caller's trajectory, the gains computed once (obca_ensemble.h).
 //   obca_advance_*_kernel   : one wavefront per instance, one step of the closed receding-horizon loop: the plant over the first `shift` intervals of the solution, the restart from the state it reached (obca_advance.h).
 //   obca_move_*_kernel      : one wavefront per instance, the obstacle words of the problem records moved and inflated in place, all or nothing per instance (obca_scene_edit.h).
+//   obca_predict_*_kernel   : one wavefront per instance, the clearance of a solution or of a caller's trajectory against obstacles that move at given rates while it is executed (obca_predict.h).
 //   obca_certify_*_kernel   : one wavefront per instance, the clearance of a solution or of a caller's trajectory certified along its whole path by conservative advancement (obca_certify.h).
 //   obca_refine_*_kernel    : one wavefront per destination instance, a solved parking instance on a finer horizon (obca_refine.h): into a second resident batch or host-bound arrays.
 //   obca_quad_subdivide_*_kernel : the same for a solved quadcopter instance (obca_quad_subdivide.h): it rewrites a problem record.
@@ -52,6 +53,7 @@
 #include "obca_advance.h"
 #include "obca_scene_edit.h"
 #include "obca_certify.h"
+#include "obca_predict.h"
 #include "../../include/obca_hip.h"
 #include "../../include/obca_path_ws.h"
 #include "../../include/obca_clearance.h"
@@ -63,6 +65,7 @@
 #include "../../include/obca_advance.h"
 #include "../../include/obca_scene_edit.h"
 #include "../../include/obca_certify.h"
+#include "../../include/obca_predict.h"
 
 using namespace obca;
 #ifdef OBCA_POISON
@@ -432,6 +435,25 @@ __global__ __launch_bounds__(QNT) void obca_move_quad_kernel(int B, double *prob
     sed::move_quad_instance(prob + (size_t)inst * s_prob, in + (size_t)inst * QOB * SE_QIN, 0, out + inst);
 }
 
+// clearance against obstacles that move (obca_predict.h): one wavefront per instance; the arguments of the clearance kernels, with `in` holding per instance s_in doubles,
+// [ the rates, s_rt doubles (PR_PIN per obstacle / PR_QIN per box) | timeScale (N + 1) of a host-pointer call ], and the profile rows (s_prof doubles each) or nullptr
+template <int VM>
+__global__ __launch_bounds__(OB_NT) void obca_predict_parking_kernel(int B, int N, const double *prob, size_t s_prob, const double *z, size_t s_z, const double *in, size_t s_in, size_t s_rt, int has_ts,
+                                                                     int S, double need, double *out, double *prof, size_t s_prof) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    const double *a = in + (size_t)inst * s_in;
+    prd::predict_parking_instance<VM>(N, prob + (size_t)inst * s_prob, z + (size_t)inst * s_z, has_ts ? a + s_rt : nullptr, a, S, need, 0, out + (size_t)inst * PR_OUT,
+                                      prof ? prof + (size_t)inst * s_prof : nullptr);
+}
+__global__ __launch_bounds__(QNT) void obca_predict_quad_kernel(int B, int N, const double *prob, size_t s_prob, const double *x, size_t s_x, const double *ts, size_t s_ts, int tstride,
+                                                                const double *in, size_t s_in, int S, double need, double *out, double *prof, size_t s_prof) {
+    const int inst = blockIdx.x;
+    if (inst >= B) return;
+    prd::predict_quad_instance(N, prob + (size_t)inst * s_prob, x + (size_t)inst * s_x, ts + (size_t)inst * s_ts, tstride, in + (size_t)inst * s_in, S, need, 0,
+                               out + (size_t)inst * PR_OUT, prof ? prof + (size_t)inst * s_prof : nullptr);
+}
+
 // clearance certificate (obca_certify.h): one wavefront per instance; the arguments of the clearance kernels with need, slack and max_steps in place of the sub-steps, then
 // the interval array (2 (N + 1) per instance).  The item table is the launch's dynamic LDS: cert::certify_work_len(N, the batch's most obstacles) doubles
 template <int VM>
@@ -665,6 +687,9 @@ struct BatchCore {
     ValBufs cer;                                            // ... and for the certify calls (obca_certify.h)
     DevBuf cer_iv;                                          // their interval arrays, 2 (N + 1) x B
     int cer_B = 0, cer_N = 0;                               // the instances and horizon of the last certify call (0: none yet)
+    ValBufs prd;                                            // ... and for the predict calls (obca_predict.h): the rates go up in a buffer set of the call's own, PR_OUT doubles per instance come down
+    DevBuf prd_w;                                           // their profile, (N S + 1) x B: allocated by the first call that keeps one, sized for that call, grown on demand
+    int prd_B = 0, prd_N = 0, prd_S = 0;                    // the instances, horizon and sub-steps of the last call that kept a profile (0: none yet)
     BatchCore(obca_ctx *c, int dev, hipStream_t s, int B_, int N_) : ctx(c), device(dev), stream(s), B(B_), cap(B_), N(N_) {}
 };
 struct obca_quad_batch : BatchCore {
@@ -727,9 +752,9 @@ static int core_phase_cycles(BatchCore *bt, const double *prof, double *out /* B
 // everything of the core that a batch's destroy releases, except `stage` (it goes with the family's device buffers); the batch's device is selected
 static void core_release(BatchCore *bt) {
     bt->rol_w.release(); bt->trk_w.release(); bt->trk_K.release();
-    bt->ens_w.release(); bt->ens_K.release(); bt->ens_mem.release(); bt->ens_fin.release(); bt->cer_iv.release();
+    bt->ens_w.release(); bt->ens_K.release(); bt->ens_mem.release(); bt->ens_fin.release(); bt->cer_iv.release(); bt->prd_w.release();
     bt->adv_w.release(); bt->adv_st.release(); bt->adv_log.release();
-    for (ValBufs *pv : {&bt->val, &bt->clr, &bt->rol, &bt->trk, &bt->ens, &bt->cer, &bt->adv, &bt->mov}) {
+    for (ValBufs *pv : {&bt->val, &bt->clr, &bt->rol, &bt->trk, &bt->ens, &bt->cer, &bt->adv, &bt->mov, &bt->prd}) {
         ValBufs &v = *pv;
         v.d_in.release(); v.d_out.release(); v.h_in.release(); v.h_out.release(); v.ev.release();
     }
@@ -1443,6 +1468,55 @@ static int batch_certify_range(obca_batch *bt, bool host, const double *ts, doub
     return certify_finish(bt, rc, lo, iv);
 }
 
+// What the two predict routes share (obca_predict.h).  Before the kernel: the profile buffer for B instances of horizon N at S sub-steps if the call keeps one (grown on
+// demand).  After it: the bookkeeping of the *_predict_profile calls and, for a host-pointer call, the chunk's profile rows into the caller's array.
+static int predict_reserve(BatchCore *bt, int S, bool keep) {
+    if (!keep) return 0;
+    use_device(bt->device);
+    if (bt->prd_w.reserve((size_t)bt->B * ((size_t)bt->N * S + 1), bt->stream) != hipSuccess) { bt->err = "hipMalloc(predict profile) failed"; return -2; }
+    return 0;
+}
+static int predict_finish(BatchCore *bt, int rc, int S, bool keep, int lo, double *profile) {
+    if (!keep) return rc;      // (a call without a profile leaves the last kept one as it is)
+    bt->prd_B = bt->prd_N = bt->prd_S = 0;
+    if (rc) return rc;
+    bt->prd_B = bt->B; bt->prd_N = bt->N; bt->prd_S = S;
+    const size_t n = (size_t)bt->N * S + 1;
+    if (profile) HIPCHK(bt, hipMemcpy(profile + (size_t)lo * n, (const double *)bt->prd_w, (size_t)bt->B * n * sizeof(double), hipMemcpyDeviceToHost));      // (run_validate has synchronised the stream)
+    return 0;
+}
+static int predict_fetch(BatchCore *bt, double *out, int capacity, const char *entry) {
+    if (!out) { bt->ctx->err = std::string(entry) + ": NULL argument"; return -1; }
+    if (!bt->prd_B || bt->prd_B != bt->B || bt->prd_N != bt->N) { bt->ctx->err = std::string(entry) + ": no predict call has kept a profile on this batch since it was last filled"; return -1; }
+    const size_t n = (size_t)bt->B * ((size_t)bt->N * bt->prd_S + 1);
+    if (capacity < 0 || (size_t)capacity < n) { bt->ctx->err = std::string(entry) + ": capacity is below B (N substeps + 1)"; return -1; }
+    use_device(bt->device);
+    if (hipStreamSynchronize(bt->stream) != hipSuccess || hipMemcpy(out, (const double *)bt->prd_w, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+        bt->ctx->err = std::string(entry) + ": D2H failed"; return -2;
+    }
+    return 0;
+}
+// The prediction for the batch's parking instances: the arguments of batch_clearance_range, then the rates (PR_PIN per obstacle, packed over the obstacles of the call),
+// whether a profile is kept and the caller's profile array (host-pointer calls; nullptr: the profile stays on the device).  The rates travel in rows of nObMax obstacles.
+static int batch_predict_range(obca_batch *bt, bool host, const double *ts, const double *rates, int S, double need, bool keep, int lo, double *out, double *profile) {
+    const int B = bt->B, N = bt->N, N1 = N + 1;
+    if (int rc = predict_reserve(bt, S, keep)) return rc;
+    const size_t s_rt = (size_t)PR_PIN * bt->nObMax, s_in = s_rt + (ts ? (size_t)N1 : 0);
+    const int rc = run_validate(bt, bt->prd, s_in, true, PR_OUT, [&](int i, double *a) {
+        memset(a, 0, sizeof(double) * s_rt);
+        const size_t o = (size_t)(host ? bt->obOff[i] : bt->obOff[i] - bt->obOff[0]);
+        memcpy(a, rates + (size_t)PR_PIN * o, sizeof(double) * PR_PIN * bt->nOb[i]);
+        if (ts) memcpy(a + s_rt, ts + ((size_t)lo + i) * N1, sizeof(double) * N1);
+    }, [&] {
+        const double *z = host ? bt->d.z0 : bt->d.z;
+#define PRD_LAUNCH(VM) hipLaunchKernelGGL(obca_predict_parking_kernel<VM>, dim3(B), dim3(OB_NT), 0, bt->stream, B, N, (const double *)bt->d.prob, bt->d.s_prob, z, bt->d.s_z, (const double *)bt->prd.d_in, s_in, s_rt, \
+                                          ts ? 1 : 0, S, need, (double *)bt->prd.d_out, keep ? (double *)bt->prd_w : nullptr, (size_t)N * S + 1)
+        if (bt->vmax <= 2) PRD_LAUNCH(2); else if (bt->vmax <= OB_VMID) PRD_LAUNCH(OB_VMID); else PRD_LAUNCH(OB_VMAX);      // (the row class of launch_dualws)
+#undef PRD_LAUNCH
+    }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * PR_OUT, o, sizeof(double) * PR_OUT); });
+    return predict_finish(bt, rc, S, keep, lo, profile);
+}
+
 // ---- chunked execution of a host-pointer call over the slots of the context (work queue)
 template <typename F>
 static int run_chunks(obca_ctx *ctx, int B, int chunk, F &&fn /* int(Slot &, int lo, int n, std::string &err) */) {
@@ -1643,6 +1717,29 @@ int obca_parking_clearance_batch(obca_ctx *ctx, int B, int N, const double *Ts, 
     ParkIn in = {Ts, L, ego, XYb, 0, nullptr, nullptr, nOb, vOb, A, b, zero.data(), zero.data(), zero.data(), x, u, nullptr, nullptr, {}, {}};
     if (int rc = park_prefix(ctx->err, B, nOb, vOb, in)) return rc;
     return parking_chunks(ctx, 0, B, N, in, [&](obca_batch *bt, int lo) { return batch_clearance_range(bt, true, timeScale, substeps, need, lo, out); });
+}
+
+int obca_batch_predict_clearance(obca_batch *bt, const double *rates, int substeps, double need, int keep_profile, double *out) {
+    if (!bt) return -1;
+    if (!out || !rates) { bt->ctx->err = "obca_batch_predict_clearance: NULL argument"; return -1; }
+    if (const char *bad = clr::clearance_check_args(substeps, need)) { bt->ctx->err = std::string("obca_batch_predict_clearance: ") + bad; return -1; }
+    if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_batch_predict_clearance: nothing has been solved since the last upload or shift"; return -1; }
+    if (bt->N < 1) { bt->ctx->err = "obca_batch_predict_clearance: needs a horizon N>=1"; return -1; }
+    return fin(bt, batch_predict_range(bt, false, nullptr, rates, substeps, need, keep_profile != 0, 0, out, nullptr));
+}
+int obca_batch_predict_clearance_ms(obca_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->prd.ev, ms, "obca_batch_predict_clearance_ms: no predict call has run on this batch") : -1; }
+int obca_batch_predict_profile(obca_batch *bt, double *out, int capacity) { return bt ? predict_fetch(bt, out, capacity, "obca_batch_predict_profile") : -1; }
+int obca_parking_predict_batch(obca_ctx *ctx, int B, int N, const double *Ts, double L, const double ego[4], const int *nOb, const int *vOb, const double *A, const double *b,
+                               const double *x, const double *u, const double *timeScale, int substeps, double need, double *out, const double *rates, double *profile) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 1 || N > OBCA_NMAX) { ctx->err = "obca_parking_predict_batch: need B>=1, 1<=N<=OBCA_NMAX"; return -1; }
+    if (!Ts || !ego || !nOb || !vOb || !A || !b || !x || !u || !out || !rates) { ctx->err = "obca_parking_predict_batch: NULL argument"; return -1; }
+    if (const char *bad = clr::clearance_check_args(substeps, need)) { ctx->err = std::string("obca_parking_predict_batch: ") + bad; return -1; }
+    const std::vector<double> zero((size_t)B * (N + 1), 0.0);      // the tracking reference of a solve: the check does not read it (nor the bounds, the start and the goal)
+    const double XYb[4] = {0, 0, 0, 0};
+    ParkIn in = {Ts, L, ego, XYb, 0, nullptr, nullptr, nOb, vOb, A, b, zero.data(), zero.data(), zero.data(), x, u, nullptr, nullptr, {}, {}};
+    if (int rc = park_prefix(ctx->err, B, nOb, vOb, in)) return rc;
+    return parking_chunks(ctx, 0, B, N, in, [&](obca_batch *bt, int lo) { return batch_predict_range(bt, true, timeScale, rates, substeps, need, profile != nullptr, lo, out, profile); });
 }
 
 int obca_batch_rollout(obca_batch *bt, int substeps, int restart, double need, double *out) {
@@ -2162,6 +2259,25 @@ static int quad_clearance_range(obca_quad_batch *bt, const double *ts, int S, do
         else hipLaunchKernelGGL(obca_clearance_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)d.z + l.x, d.s_z, (const double *)d.z + l.t, d.s_z, 0, S, need, bt->clr.d_out);
     }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * CL_OUT, o, sizeof(double) * CL_OUT); });
 }
+// the prediction for the batch's quadcopter instances (obca_predict.h): quad_clearance_range with the rates (PR_QIN x 5 per instance of the call), whether a profile is kept
+// and the caller's profile array; the rates and a host-pointer call's timeScale travel up as [ rates | timeScale (N + 1) ] per instance
+static int quad_predict_range(obca_quad_batch *bt, const double *ts, const double *rates, int S, double need, bool keep, int lo, double *out, double *profile) {
+    const int B = bt->B, N = bt->N, N1 = N + 1; const QDevBufs &d = bt->d;
+    quad::QLay l; quad::q_make_layout(N, l);
+    if (int rc = predict_reserve(bt, S, keep)) return rc;
+    const size_t s_rt = (size_t)PR_QIN * QOB, s_in = s_rt + (ts ? (size_t)N1 : 0), s_prof = (size_t)N * S + 1;
+    const int rc = run_validate(bt, bt->prd, s_in, true, PR_OUT, [&](int i, double *a) {
+        memcpy(a, rates + ((size_t)lo + i) * s_rt, sizeof(double) * s_rt);
+        if (ts) memcpy(a + s_rt, ts + ((size_t)lo + i) * N1, sizeof(double) * N1);
+    }, [&] {
+        const double *in = (const double *)bt->prd.d_in; double *prof = keep ? (double *)bt->prd_w : nullptr;
+        if (ts) hipLaunchKernelGGL(obca_predict_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)d.prob + QPH_SIZE, d.s_prob, in + s_rt, s_in, 1,
+                                   in, s_in, S, need, (double *)bt->prd.d_out, prof, s_prof);
+        else hipLaunchKernelGGL(obca_predict_quad_kernel, dim3(B), dim3(QNT), 0, bt->stream, B, N, (const double *)d.prob, d.s_prob, (const double *)d.z + l.x, d.s_z, (const double *)d.z + l.t, d.s_z, 0,
+                                in, s_in, S, need, (double *)bt->prd.d_out, prof, s_prof);
+    }, [&](int i, const double *o) { memcpy(out + ((size_t)lo + i) * PR_OUT, o, sizeof(double) * PR_OUT); });
+    return predict_finish(bt, rc, S, keep, lo, profile);
+}
 // the rollout of the batch's quadcopter instances (obca_rollout.h): resident (ts == nullptr: the last solution in d.z, its one t) or a caller's trajectory -- x as
 // quad_upload_range has put it behind the problem header, timeScale and u of the call travelling up as [ timeScale (N + 1) | u 4 x N ] per instance
 static int quad_rollout_range(obca_quad_batch *bt, const double *u, const double *ts, int S, int restart, double need, int lo, double *out, double *X) {
@@ -2344,6 +2460,25 @@ int obca_quadcopter_clearance_batch(obca_ctx *ctx, int B, int N, const double *T
     const std::vector<double> zero((size_t)B * QX, 0.0), one((size_t)B, 1.0);      // start, goal and timeWS of a solve: the check reads none of them
     const QuadIn in = {Ts, R, zero.data(), zero.data(), ob, x, one.data(), 0, 0};
     return quad_chunks(ctx, B, N, in, [&](obca_quad_batch *bt, int lo) { return quad_clearance_range(bt, timeScale, substeps, need, lo, out); });
+}
+int obca_quad_batch_predict_clearance(obca_quad_batch *bt, const double *rates, int substeps, double need, int keep_profile, double *out) {
+    if (!bt) return -1;
+    if (!out || !rates) { bt->ctx->err = "obca_quad_batch_predict_clearance: NULL argument"; return -1; }
+    if (const char *bad = clr::clearance_check_args(substeps, need)) { bt->ctx->err = std::string("obca_quad_batch_predict_clearance: ") + bad; return -1; }
+    if (!bt->uploaded || !bt->solved) { bt->ctx->err = "obca_quad_batch_predict_clearance: nothing has been solved since the last upload or shift"; return -1; }
+    return fin(bt, quad_predict_range(bt, nullptr, rates, substeps, need, keep_profile != 0, 0, out, nullptr));
+}
+int obca_quad_batch_predict_clearance_ms(obca_quad_batch *bt, float *ms) { return bt && ms ? core_elapsed_ms(bt->ctx, bt->prd.ev, ms, "obca_quad_batch_predict_clearance_ms: no predict call has run on this batch") : -1; }
+int obca_quad_batch_predict_profile(obca_quad_batch *bt, double *out, int capacity) { return bt ? predict_fetch(bt, out, capacity, "obca_quad_batch_predict_profile") : -1; }
+int obca_quadcopter_predict_batch(obca_ctx *ctx, int B, int N, const double *Ts, double R, const double *ob, const double *x, const double *timeScale, int substeps, double need, double *out,
+                                  const double *rates, double *profile) {
+    if (!ctx) return -1;
+    if (B < 1 || N < 2 || N > OBCA_QUAD_NMAX) { ctx->err = "obca_quadcopter_predict_batch: need B>=1, 2<=N<=OBCA_QUAD_NMAX"; return -1; }
+    if (!Ts || !ob || !x || !timeScale || !out || !rates) { ctx->err = "obca_quadcopter_predict_batch: NULL argument"; return -1; }
+    if (const char *bad = clr::clearance_check_args(substeps, need)) { ctx->err = std::string("obca_quadcopter_predict_batch: ") + bad; return -1; }
+    const std::vector<double> zero((size_t)B * QX, 0.0), one((size_t)B, 1.0);      // start, goal and timeWS of a solve: the call reads none of them
+    const QuadIn in = {Ts, R, zero.data(), zero.data(), ob, x, one.data(), 0, 0};
+    return quad_chunks(ctx, B, N, in, [&](obca_quad_batch *bt, int lo) { return quad_predict_range(bt, timeScale, rates, substeps, need, profile != nullptr, lo, out, profile); });
 }
 int obca_quad_batch_rollout(obca_quad_batch *bt, int substeps, int restart, double need, double *out) {
     if (!bt) return -1;

@@ -493,6 +493,86 @@ def move_obstacles_quad(ob, motion=None, inflate=None):
     return (out, True) if ok else (ob, False)
 
 
+# ---------------------------------------------------------------- clearance of a held plan against obstacles that move (obca_amd/csrc/obca_predict.h)
+PRD_OUT = 32          # doubles of a record: the CLR_OUT clearance record, first, t_first, first_obstacle, t_min, horizon, moving, 2 x 0
+
+
+def predict_times(timeScale, Ts, N, substeps):
+    """tau (N S + 1,): the time [s] at which sample q = k S + s of a trajectory is reached -- cum[0] = 0, cum[k+1] = cum[k] + timeScale[k] summed in stage order,
+    tau_q = (cum[k] + (s / S) timeScale[k]) Ts, cum[k] Ts at s = 0 and for the last sample."""
+    S = int(substeps); ts = _stage_scale(timeScale, N); cum = np.zeros(N + 1)
+    for k in range(N):
+        cum[k + 1] = cum[k] + ts[k]
+    tau = np.zeros(N * S + 1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for q in range(N * S + 1):
+            k, s = divmod(q, S)
+            tau[q] = (cum[k] + (s / S) * ts[k]) * Ts if s else cum[k] * Ts
+    return tau
+
+
+def predict_parking(x, u, timeScale, Ts, L, vOb, A, b, rates, dist, substeps):
+    """The clearance table of a parking trajectory x (4,N+1), u (2,N) against obstacles that MOVE while it is driven: rates (nOb,6) = [vx, vy, w, cx, cy, g] per obstacle.
+    Sample q is the pose parking_samples gives; the scene it is measured in is the one move_obstacles_parking makes of the unit-length rows A (M,2), b (M,) with motion
+    (vx, vy, w) tau_q, pivot (cx, cy) and inflation g tau_q -- "clearance() in the scene move_obstacles would have made at that time".  dist(pose, A_j, b_j): the distance
+    of the car at pose (x, y, yaw) to the polygon with rows A_j, b_j (an exact polygon distance, the host build's DualMultWS); below CLR_TOUCH it counts as 0.
+    Returns (c (N S + 1, nOb), tau (N S + 1,), finite); not finite (a number of the trajectory, a rate or a moved row is not): c is NaN."""
+    x = np.asarray(x, float); u = np.asarray(u, float); N = x.shape[1] - 1; S = int(substeps); ts = _stage_scale(timeScale, N)
+    v = np.asarray(vOb, np.int64).ravel(); n = len(v); A = np.asarray(A, float).reshape(-1, 2); b = np.asarray(b, float).ravel(); rt = np.asarray(rates, float).reshape(n, 6)
+    tau = predict_times(ts, Ts, N, S); c = np.full((N * S + 1, n), np.nan)
+    if not (np.isfinite(x).all() and np.isfinite(u).all() and np.isfinite(ts).all() and np.isfinite(Ts) and np.isfinite(rt).all()):
+        return c, tau, False
+    poses = parking_samples(x, u, ts, Ts, L, S); r0 = np.concatenate([[0], np.cumsum(v)])
+    for q in range(N * S + 1):
+        with np.errstate(invalid="ignore", over="ignore"):
+            A2, b2, ok = move_obstacles_parking(A, b, v, rt[:, :3] * tau[q], rt[:, 3:5], rt[:, 5] * tau[q])
+        if not ok:
+            return np.full_like(c, np.nan), tau, False
+        for j in range(n):
+            d = dist(poses[q], A2[r0[j]:r0[j + 1]], b2[r0[j]:r0[j + 1]])
+            c[q, j] = 0.0 if d < CLR_TOUCH else d
+    return c, tau, True
+
+
+def predict_quad(x, timeScale, Ts, ob, R, rates, substeps):
+    """the same for a quadcopter trajectory x (12,N+1): rates (5,4) = [vx, vy, vz, g] per box; sample q is the point quad_clearance measures, the boxes are those
+    move_obstacles_quad makes of ob (5,6) with motion (vx, vy, vz) tau_q and inflation g tau_q.  Returns (c (N S + 1, 5), tau, finite)."""
+    x = np.asarray(x, float); N = x.shape[1] - 1; S = int(substeps); ts = _stage_scale(timeScale, N); ob = np.asarray(ob, float).reshape(5, 6)
+    rt = np.asarray(rates, float).reshape(5, 4); tau = predict_times(ts, Ts, N, S); c = np.full((N * S + 1, 5), np.nan)
+    if not (np.isfinite(x).all() and np.isfinite(ts).all() and np.isfinite(Ts) and np.isfinite(rt).all()):
+        return c, tau, False
+    with np.errstate(invalid="ignore", over="ignore"):
+        for q in range(N * S + 1):
+            k, s = divmod(q, S)
+            pt = x[:3, k] + s / S * ts[k] * Ts * x[6:9, k] if s else x[:3, k]
+            ob2, ok = move_obstacles_quad(ob, rt[:, :3] * tau[q], rt[:, 3] * tau[q])
+            if not ok:
+                return np.full_like(c, np.nan), tau, False
+            c[q] = quad_point_clearance(pt[None, :], ob2, R)[0]
+    return c, tau, True
+
+
+def predict_record(c, tau, rates, substeps, need, finite=True):
+    """(record (PRD_OUT,), profile (N S + 1,)) of a table c of predicted clearances with the sample times tau: [0..23] clearance_record(c); [24] first = the first sample
+    whose smallest clearance is < need (-1: none), [25] t_first = its tau (+inf: none), [26] first_obstacle = the smallest j under need at that sample (-1), [27] t_min =
+    tau of sample [2], [28] horizon = tau of the last sample, [29] moving = the obstacles with a velocity, a turn rate or a growth rate that is not 0 (a pivot alone moves
+    nothing), [30], [31] 0; profile = the smallest clearance of every sample.  Not finite: the bad clearance record, [24] = [26] = -1, [25] = [27] = [28] = NaN, [29] = 0,
+    profile NaN."""
+    c = np.asarray(c, float); tau = np.asarray(tau, float); rt = np.asarray(rates, float); r = np.zeros(PRD_OUT)
+    r[:CLR_OUT] = clearance_record(c, substeps, need, finite)
+    if r[6]:
+        r[[24, 26]] = -1; r[[25, 27, 28]] = np.nan
+        return r, np.full(c.shape[0], np.nan)
+    prof = c.min(axis=1); under = np.flatnonzero(prof < need)
+    if len(under):
+        q = int(under[0]); r[24] = q; r[25] = tau[q]; r[26] = int(np.flatnonzero(c[q] < need)[0])
+    else:
+        r[24] = r[26] = -1; r[25] = np.inf
+    r[27] = tau[int(r[2])]; r[28] = tau[-1]
+    r[29] = int((np.delete(rt, [3, 4], axis=1) != 0).any(axis=1).sum()) if rt.shape[1] == 6 else int((rt != 0).any(axis=1).sum())
+    return r, prof
+
+
 # ---------------------------------------------------------------- closed-loop rollout: TVLQR gains about a trajectory (obca_amd/csrc/obca_track.h)
 TRK_OUT = 48          # doubles of a record: the ROLL_OUT doubles of the chain, feedback, clamp, saturated, du_max, du_node, dx0_pos, 2 x 0
 # Default weights: the values the first prototype ran with.  UNTUNED.
